@@ -22,9 +22,17 @@ data-path collective (dQ/dK/dV of a graph depend only on that graph).
   --scaling weak   (default, the driver contract): every rank owns its own bs=1024 batch; `value` = all edges / time.
   --scaling strong: the ONE seed-1 bs=1024 batch is cut into N shards of whole graphs, balanced by edge
                    count (DFGNN/parallel/sharding.py:shard_graph); `value` = its edges / max-over-ranks time.
-With N > 1 the line also carries the other mode's measurement ("strong_scaling" / "weak_scaling") and the
+With N > 1 and --full the line also carries the other mode's measurement ("strong_scaling" / "weak_scaling") and the
 forward-output all-gather an inference caller may want ("inference_allgather": kernel + RCCL all-gather of the padded
 per-shard outputs) -- never part of `value`.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the line (`value`, `ms_per_step`, the
+workload).  --full adds everything else this script measures, each in runs of its own after the timed region: the
+per-kernel device-event times and the roofline, the fp32 VALU step, the secondary figures (other pairs, weighted edges, GAT
+training, preprocessing, the step as a HIP graph, C4), the CPU baseline and, with N > 1, the figures named above.
+--dump-outputs DIR writes what the last timed step computed -- the forward output and dQ, dK, dV, what a caller of the
+step receives -- as float32 .npy files (rank 0; see dump_outputs).  The inputs are seeded: the same arguments give the
+same inputs on every run, so two builds can be compared output for output.
 
 Prints ONE JSON line on rank 0.
 """
@@ -46,6 +54,8 @@ import torch.distributed as dist  # noqa: E402
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md; ~6.3 TB/s is the measured copy rate)
 PMC_PROFILE = os.path.join("profiles", "r03_pmc_dense_kernels.json")  # HBM bytes per launch from rocprofv3 --pmc passes
 SETUP_STEPS = 40  # untimed steps inside Workload(): plan build, allocator pools, device clocks (~10 ms of continuous work; reported as "setup_steps")
+DUMP_BYTES = 32 << 20  # --dump-outputs: bytes of arrays at most; larger outputs are written as a fixed sample of node rows
+OUTPUT_NAMES = ("out", "dQ", "dK", "dV")  # what Workload.step returns
 
 
 def parse():
@@ -57,16 +67,23 @@ def parse():
     ap.add_argument("--dim", type=int, default=128)
     ap.add_argument("--heads", type=int, default=1)
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-c4", action="store_true", help="skip the reddit-like GAT 'tiling' secondary figure")
-    ap.add_argument("--cpu-sample-graphs", type=int, default=128)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: per-kernel times, roofline, secondary figures, CPU baseline (N > 1: the other "
+                         "scaling mode and the inference all-gather)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-c4", action="store_true", help="(--full) skip the reddit-like GAT 'tiling' secondary figure")
+    ap.add_argument("--cpu-sample-graphs", type=int, default=128, help="(--full) graphs the CPU baseline runs on")
     # rehearsal only: "gloo" lets several ranks share ONE GPU (collectives on host tensors) to exercise the N > 1
     # code path on a single-GPU box; the driver's multi-GPU runs use the default (RCCL).
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"])
     # no GPU work at all: ranks are started / joined, the process group comes up (gloo), the collectives the timed region
     # uses are exercised on dummy numbers, rank 0 prints a line with "dry_run": true and no value -- what the CPU suite runs
     ap.add_argument("--dry-run", action="store_true")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def algorithmic_bytes_stats(m, nnz, h, f):
@@ -170,9 +187,24 @@ class Workload:
         torch.cuda.synchronize(dev)
 
     def step(self):
+        """-> out, dQ, dK, dV (OUTPUT_NAMES)"""
         out = self._op(self.rows, self.row_ptr, self.col_ind, self.val, self.col_ptr, self.row_ind, self.val_idx,
                        self.smem, self.Q, self.K, self.V)
-        return torch.autograd.grad(out, (self.Q, self.K, self.V), self.dO)
+        return (out,) + torch.autograd.grad(out, (self.Q, self.K, self.V), self.dO)
+
+
+def dump_outputs(directory, outputs):
+    """--dump-outputs: `outputs` (one step's OUTPUT_NAMES, [m, h, f] each) as DIR/<name>.npy in float32.  Above DUMP_BYTES
+    together, every array is cut to the same rows: a sample drawn with a fixed seed, sorted, that depends on m alone."""
+    os.makedirs(directory, exist_ok=True)
+    m = outputs[0].shape[0]
+    rows = min(m, DUMP_BYTES // (4 * sum(t[0].numel() for t in outputs)))
+    idx = None
+    if rows < m:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(m, rows, replace=False))).to(outputs[0].device)
+    for name, t in zip(OUTPUT_NAMES, outputs):
+        t = t.detach() if idx is None else t.detach().index_select(0, idx)
+        np.save(os.path.join(directory, name + ".npy"), t.float().cpu().numpy())
 
 
 def spawn_ranks(args):
@@ -276,7 +308,8 @@ def main():
 
     def timed(w, steps, warmup):
         """`warmup` untimed steps, then exactly `steps` timed ones between barriers (barrier = device synchronise + process
-        barrier).  The collector is held off for the timed steps: a collection pass in a 13 ms region shows up as +10 %."""
+        barrier) -> (seconds, the last step's outputs).  The collector is held off for the timed steps: a collection pass
+        in a 13 ms region shows up as +10 %."""
         import gc
         mode = os.environ.get("DFGNN_BENCH_GC", "setup")   # (A/B switch: where the collection pass goes)
         if mode == "early":
@@ -294,20 +327,52 @@ def main():
             gc.disable()
         try:
             t0 = time.perf_counter()
-            for _ in range(steps):
+            for _ in range(steps - 1):
                 w.step()
+            last = w.step()
             barrier()
-            return allmax(time.perf_counter() - t0)
+            return allmax(time.perf_counter() - t0), last
         finally:
             gc.enable()
 
     # ---- the timed region -------------------------------------------------------------------------------------------
     W = make(args.scaling)
     m, nnz = W.m, W.nnz
-    elapsed = timed(W, args.steps, args.warmup)
+    elapsed, last = timed(W, args.steps, args.warmup)
     total_edges = allsum(nnz)
     ms_per_step = elapsed / args.steps * 1e3
     value = total_edges * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+    del last
+
+    uses_stats = fused_gtconv.gt_stats_pair_chosen(W.row_ptr, W.col_ind, W.val, W.Q)  # what the timed step launches
+    ranked_can = fused_gtconv.gt_ranked_pair_chosen(W.row_ptr, W.col_ind, W.val, W.Q)
+    line = {
+        "metric": "edges/s (fwd+bwd) fused GT conv, PATTERN bs=1024 dim=128",
+        "value": value, "unit": "edges/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "setup_steps": SETUP_STEPS,
+        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": args.scaling if world > 1 else "weak",
+        "vs_baseline": None, "dtype": "f32", "arithmetic": {
+            "io": "f32", "accumulate": "f32",
+            "products": "matrix cores (v_mfma_f32_16x16x32_f16): every operand as fp16 hi + lo halves under a power-of-two "
+                        "scale, hi*hi + hi*lo + lo*hi accumulated in fp32 (~3 x 2^-24 relative error per product, that of an "
+                        "fp32 FMA chain; tests/test_gpu_parity.py::test_dense_kernels_are_fp32_equivalent)"},
+        "data": "synthetic",
+        "config": {"workload": f"GT conv 'hyper' fwd+bwd, PATTERN-like batch bs={args.batch_size} "
+                               f"dim={args.dim} heads={h} (BASELINE.json configs[2])",
+                   "training_pair": "row statistics (dfgnn_gt_hyper_fwd_stats / dfgnn_gt_bwd_stats)" if uses_stats is not None
+                   else "attn_edge in rank order (dfgnn_gt_hyper_fwd_ranked / dfgnn_gt_bwd_ranked)" if ranked_can is not None
+                   else "attn_edge (dfgnn_gt_hyper_fwd / dfgnn_gt_bwd)",
+                   "nodes_per_gpu": m, "edges_per_gpu": nnz, "total_edges": total_edges,
+                   "parallelism": (f"graph-sharded x{world} ({args.scaling} scaling), no data-path collective")},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line))
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- the other scaling mode and the inference-side exchange step (N > 1 only) -------------------------------
     other = gather = None
@@ -315,7 +380,7 @@ def main():
         try:   # (secondary figures: a failure here must not cost the line its headline; every rank takes the same path)
             other_mode = "strong" if args.scaling == "weak" else "weak"
             Wo = make(other_mode)
-            t_o = timed(Wo, args.steps, args.warmup)
+            t_o = timed(Wo, args.steps, args.warmup)[0]
             e_o = allsum(Wo.nnz)
             other = {"ms_per_step": round(t_o / args.steps * 1e3, 4), "edges_per_s": e_o * args.steps / t_o,
                      "total_edges": e_o, "edges_this_rank": Wo.nnz,
@@ -373,7 +438,6 @@ def main():
     plan, plan_meta, _ = get_plan(W.row_ptr, W.col_ind, f, fused_gtconv.USE_BLOCK_PLAN)
     VP = val_ptr(W.val)  # NULL for unit edge values, exactly as the binding passes it (fused_gtconv.py)
 
-    uses_stats = fused_gtconv.gt_stats_pair_chosen(W.row_ptr, W.col_ind, W.val, W.Q)  # what the timed step launches
     stats_can = fused_gtconv.gt_stats_pair_applies(W.row_ptr, W.col_ind, W.val, W.Q)  # ... and whether the other pair could run
     with torch.no_grad():
         rmax, rsum = torch.empty(m, h, device=dev), torch.empty(m, h, device=dev)
@@ -403,8 +467,7 @@ def main():
     reps = max(10, args.steps)
     attn_us = {"gt_hyper_fwd": ev_us(checked(fwd_call(VP)), reps), "gt_bwd": ev_us(checked(bwd_call(VP)), reps)}
     attn_bytes = algorithmic_bytes(m, nnz, h, f)
-    # one head, all dense, unit values: the attn_edge pair in rank order is what the step launches
-    ranked_can = fused_gtconv.gt_ranked_pair_chosen(W.row_ptr, W.col_ind, W.val, W.Q)
+    # one head, all dense, unit values: the attn_edge pair in rank order is what the step launches (ranked_can)
     ranked_us = None
     if ranked_can is not None:
         ranked_us = {
@@ -480,18 +543,14 @@ def main():
                                     "frac": round(abytes[k] / (v * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)}
                                 for k, v in kernel_us.items()}}
     valu_step_us = valu_us["gt_hyper_fwd"] + valu_us["gt_bwd"]
-    arithmetic = {
-        "io": "f32", "accumulate": "f32",
-        "products": "matrix cores (v_mfma_f32_16x16x32_f16): every operand as fp16 hi + lo halves under a power-of-two scale, "
-                    "hi*hi + hi*lo + lo*hi accumulated in fp32 (~3 x 2^-24 relative error per product, that of an fp32 FMA "
-                    "chain; tests/test_gpu_parity.py::test_dense_kernels_are_fp32_equivalent)",
+    line["arithmetic"].update({
         "f32_valu_step": {"what": "the attn_edge pair's fwd+bwd launches with every product as an fp32 FMA on the VALU (edge "
                                   "values passed explicitly to dfgnn_gt_hyper_fwd / dfgnn_gt_bwd, which have no matrix-core "
                                   "form for them)",
                           "fwd_us": round(valu_us["gt_hyper_fwd"], 2), "bwd_us": round(valu_us["gt_bwd"], 2),
                           "edges_per_s": nnz / (valu_step_us * 1e-6),
                           "frac_fwd": round(attn_bytes["gt_hyper_fwd"] / (valu_us["gt_hyper_fwd"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
-                          "frac_bwd": round(attn_bytes["gt_bwd"] / (valu_us["gt_bwd"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)}}
+                          "frac_bwd": round(attn_bytes["gt_bwd"] / (valu_us["gt_bwd"] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)}})
 
     # ---- secondary figures (never part of `value`), rank 0 at N = 1 only ----------------------------------------
     secondary = None
@@ -592,21 +651,7 @@ def main():
                                   "edges_per_s": gc.num_edges() / c_dt, "cores": oracle.num_threads()}
 
     if rank == 0:
-        line = {
-            "metric": "edges/s (fwd+bwd) fused GT conv, PATTERN bs=1024 dim=128",
-            "value": value, "unit": "edges/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "setup_steps": SETUP_STEPS,
-            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": args.scaling if world > 1 else "weak",
-            "vs_baseline": None, "dtype": "f32", "arithmetic": arithmetic, "data": "synthetic",
-            "config": {"workload": f"GT conv 'hyper' fwd+bwd, PATTERN-like batch bs={args.batch_size} "
-                                   f"dim={args.dim} heads={h} (BASELINE.json configs[2])",
-                       "training_pair": "row statistics (dfgnn_gt_hyper_fwd_stats / dfgnn_gt_bwd_stats)" if uses_stats is not None
-                       else "attn_edge in rank order (dfgnn_gt_hyper_fwd_ranked / dfgnn_gt_bwd_ranked)" if ranked_us is not None
-                       else "attn_edge (dfgnn_gt_hyper_fwd / dfgnn_gt_bwd)",
-                       "nodes_per_gpu": m, "edges_per_gpu": nnz, "total_edges": total_edges,
-                       "parallelism": (f"graph-sharded x{world} ({args.scaling} scaling), no data-path collective")},
-            "roofline": roofline, "cpu_baseline": cpu,
-        }
+        line.update(roofline=roofline, cpu_baseline=cpu)
         if other:
             line["strong_scaling" if args.scaling == "weak" else "weak_scaling"] = other
         if gather:

@@ -263,3 +263,31 @@ def test_bench_gpus_n_starts_its_own_ranks():
     bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--dry-run"],
                          env=dict(env, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0"), capture_output=True, text=True, timeout=600)
     assert bad.returncode != 0 and "refusing" in bad.stderr
+
+
+def test_bench_dump_outputs_whole_or_a_fixed_row_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 .npy per output; whole while they fit in DUMP_BYTES, else the same sorted, seeded
+    sample of rows from every array, identical from run to run and within the budget."""
+    import bench
+    m, h, f = 1000, 2, 8
+    rows = torch.arange(m, dtype=torch.float64)[:, None, None].expand(m, h, f)
+    outs = tuple(rows + k / 8 for k in range(len(bench.OUTPUT_NAMES)))   # every element says its row and its array
+
+    def load(d):
+        return {k: np.load(str(d / (k + ".npy"))) for k in bench.OUTPUT_NAMES}
+
+    bench.dump_outputs(str(tmp_path / "whole"), outs)
+    for k, (name, a) in enumerate(load(tmp_path / "whole").items()):
+        assert a.dtype == np.float32 and a.shape == (m, h, f)
+        np.testing.assert_array_equal(a, outs[k].float().numpy(), err_msg=name)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 100 * 4 * h * f * len(outs) + 7)
+    bench.dump_outputs(str(tmp_path / "a"), outs)
+    bench.dump_outputs(str(tmp_path / "b"), outs)
+    a, b = load(tmp_path / "a"), load(tmp_path / "b")
+    assert sum(x.nbytes for x in a.values()) <= bench.DUMP_BYTES
+    idx = a["out"][:, 0, 0].astype(np.int64)
+    assert len(idx) == 100 and (np.diff(idx) > 0).all() and idx[0] >= 0 and idx[-1] < m
+    for k, name in enumerate(bench.OUTPUT_NAMES):
+        assert a[name].dtype == np.float32 and a[name].shape == (100, h, f)
+        np.testing.assert_array_equal(a[name], outs[k][idx].float().numpy(), err_msg=name)
+        np.testing.assert_array_equal(a[name], b[name], err_msg=name)
