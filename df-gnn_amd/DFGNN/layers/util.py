@@ -20,8 +20,8 @@ from .AGNN import (AGNNConv_csr, AGNNConv_csr_gm, AGNNConv_hyper, AGNNConv_softm
 from .GAT_DOT import DOTGATConv_csr, DOTGATConv_hyper, DOTGATConv_softmax
 from .GAT import (GATConv_dgNN, GATConv_hyper, GATConv_hyper_ablation, GATConv_hyper_recompute, GATConv_hyper_v2,
                   GATConv_softmax, GATConv_softmax_gm, GATConv_tiling)
-from .GT import (SparseMHA_CSR, SparseMHA_CSR_GM, SparseMHA_forward_timing, SparseMHA_hyper, SparseMHA_softmax,
-                 SparseMHA_softmax_gm, SparseMHA_tiling)
+from .GT import (SparseMHA_CSR, SparseMHA_CSR_GM, SparseMHA_forward_timing, SparseMHA_hyper, SparseMHA_rowstats_timing,
+                 SparseMHA_softmax, SparseMHA_softmax_gm, SparseMHA_tiling)
 
 WARP_SIZE = 32  # only used by the smem_consume formula kept from the reference
 
@@ -103,6 +103,7 @@ _GT_LAYERS = {
     "csr": SparseMHA_CSR, "csr_gm": SparseMHA_CSR_GM, "tiling": SparseMHA_tiling, "hyper": SparseMHA_hyper,
     "nofuse": SparseMHA_hyper, "softmax": SparseMHA_softmax, "softmax_gm": SparseMHA_softmax_gm,
     "forward": SparseMHA_forward_timing,
+    "forward_rowstats": SparseMHA_rowstats_timing,  # this build's addition: row statistics instead of attn_edge, any graph
     "hyper_ablation": SparseMHA_hyper,  # reference :385-386 (ablation entry; served by the production kernel)
 }
 _GAT_LAYERS = {
@@ -167,6 +168,6 @@ def load_prepfunc(args):
         return preprocess_Hyper
     if args.format in ("softmax", "softmax_gm"):
         return preprocess_softmax
-    if args.format == "forward":
+    if args.format in ("forward", "forward_rowstats"):
         return preprocess_Hyper_fw_bw
     raise ValueError(f"Unsupported format {args.format}")

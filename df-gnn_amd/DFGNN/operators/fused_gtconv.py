@@ -75,6 +75,37 @@ def GTConvFuse_hyper(rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, sme
         rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V)
 
 
+class FusedGTFunction_rowstats(torch.autograd.Function):
+    """FusedGTFunction_hyper for ANY graph without per-edge saved state (opt-in; include/dfgnn.h: dfgnn_gt_fwd_rowstats /
+    dfgnn_gt_bwd_rowstats, csrc/gt_train.hip).  Saved between forward and backward: Q, K, V, out, the row statistics
+    row_max / row_sum [m, h] and the graph arrays -- nothing of size nnz in floating point (the reference's form keeps
+    attn_edge[h, nnz] and allocates grad_edge[h, nnz] in its backward).  The backward recomputes each edge's attention
+    from the rows it gathers anyway."""
+
+    @staticmethod
+    def forward(ctx, rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V):
+        out_feat, row_max, row_sum = fused_gt.gt_forward_rowstats(row_ptr, col_ind, val, Q, K, V)
+        # unit edge values (what every reference flow passes) are not kept: the kernels never read them
+        keep_val = () if fused_gt.val_ptr(val) is None else (val,)
+        ctx.save_for_backward(row_ptr, col_ind, col_ptr, row_ind, val_idx, Q, K, V, out_feat, row_max, row_sum, *keep_val)
+        return out_feat
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        row_ptr, col_ind, col_ptr, row_ind, val_idx, Q, K, V, out_feat, row_max, row_sum, *val = ctx.saved_tensors
+        val = val[0] if val else None
+        grad_Q, grad_K, grad_V = fused_gt.gt_backward_rowstats(row_ptr, col_ind, val, col_ptr, row_ind, val_idx, Q, K, V,
+                                                               out_feat, row_max, row_sum, grad_out.contiguous())
+        return (None,) * 8 + (grad_Q, grad_K, grad_V)
+
+
+def GTConvFuse_rowstats(rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V):
+    """Differentiable conv of any graph that saves row statistics instead of attn_edge; the argument list of
+    GTConvFuse_hyper (`rows` and `smem_consume` are accepted and not used)."""
+    return FusedGTFunction_rowstats.apply(
+        rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V)
+
+
 def GTConvFuse_inference_softmax(indptr, indices, rows, val, smem_consume, Q, K, V):
     """softmax: two kernels (COO SDDMM, then softmax + SpMM).  reference :238-259"""
     return fused_gt.gt_softmax_inference(indptr, indices, rows, val, smem_consume, Q, K, V)[0]

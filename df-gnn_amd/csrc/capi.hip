@@ -228,6 +228,31 @@ int dfgnn_gt_bwd_ranked(int m, int nnz, int h, int f, const int *row_ptr, const 
   return launch_gt_dense_bwd(g, p, Q, K, V, attn_ranked, grad_out, dQ, dK, dV, as_stream(stream), true);
 }
 
+// ---- the general statistics pair (gt_train.hip): any graph, no plan, nothing of size nnz saved or parked ----------------
+int dfgnn_gt_fwd_rowstats(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                          const float *Q, const float *K, const float *V, float *row_max, float *row_sum, float *out,
+                          dfgnn_stream_t stream) {
+  if (int c = check_common(m, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (!Q || !K || !V || !out || (!row_max != !row_sum)) return kErrBadArg;  // (both statistics or neither: inference)
+  const Csr g{m, nnz, h, f, row_ptr, col_ind, nullptr, val};
+  return launch_gt_train_fwd(g, Q, K, V, row_max, row_sum, out, as_stream(stream));
+}
+
+int dfgnn_gt_bwd_rowstats(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                          const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q, const float *K,
+                          const float *V, const float *out, const float *row_max, const float *row_sum,
+                          const float *grad_out, float *delta, float *dQ, float *dK, float *dV, dfgnn_stream_t stream) {
+  if (int c = check_common(m, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (!Q || !K || !V || !out || !row_max || !row_sum || !grad_out || !delta || !dQ || !dK || !dV || !col_ptr)
+    return kErrBadArg;
+  if (nnz > 0 && (!row_ind || (val && !val_idx))) return kErrBadArg;  // (unit values never read val_idx)
+  const Csr g{m, nnz, h, f, row_ptr, col_ind, nullptr, val};
+  if (int rc = launch_gt_train_bwd_rows(g, Q, K, V, out, row_max, row_sum, grad_out, delta, dQ, as_stream(stream)))
+    return rc;
+  return launch_gt_train_bwd_cols(g, col_ptr, row_ind, val_idx, Q, K, V, row_max, row_sum, delta, grad_out, dK, dV,
+                                  as_stream(stream));
+}
+
 int dfgnn_gt_tiling_fwd(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
                         const float *Q, const float *K, const float *V, float *out, dfgnn_stream_t stream) {
   if (int c = check_common(m, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;

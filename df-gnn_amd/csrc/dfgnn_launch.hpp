@@ -176,6 +176,17 @@ int launch_gt_lowdeg_fwd(const Csr &g, const float *Q, const float *K, const flo
 int launch_gt_lowdeg_bwd(const Csr &g, const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q,
                          const float *K, const float *V, const float *attn_edge, const float *grad_out,
                          float *grad_edge, float *dQ, float *dK, float *dV, hipStream_t s);
+// GT training pair without per-edge saved state (gt_train.hip): any graph, no plan.  The forward saves row_max / row_sum
+// [m, h] (both nullable: inference); the backward is the CSR pass (delta [m, h] = <dO_i, out_i>, dQ) then the CSC pass
+// (dK, dV), each recomputing the attention of the edges it walks.
+int launch_gt_train_fwd(const Csr &g, const float *Q, const float *K, const float *V, float *row_max, float *row_sum,
+                        float *out, hipStream_t s);
+int launch_gt_train_bwd_rows(const Csr &g, const float *Q, const float *K, const float *V, const float *out,
+                             const float *row_max, const float *row_sum, const float *grad_out, float *delta, float *dQ,
+                             hipStream_t s);
+int launch_gt_train_bwd_cols(const Csr &g, const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q,
+                             const float *K, const float *V, const float *row_max, const float *row_sum,
+                             const float *delta, const float *grad_out, float *dK, float *dV, hipStream_t s);
 // graphs with fewer than kBlockMinAvgDegree edges per row on average take the row-per-lane-group kernels
 inline bool low_degree(int m, int nnz) { return (long)nnz < (long)kBlockMinAvgDegree * m; }
 int launch_gat_hyper_fwd(const Csr &g, const float *attn_row, const float *attn_col, float slope,

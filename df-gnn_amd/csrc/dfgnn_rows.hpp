@@ -2,6 +2,7 @@
 //
 //  * sddmm_range          edge-parallel <lhs[row], rhs[col]> for a contiguous edge range, one group
 //                         of lanes per edge, 4 edges in flight per group.
+//  * tile_dots            <a, X[col]> for the (<= 64) edges of a tile against one row held in registers.
 //  * row_softmax_spmm_lds the node-parallel phase of the 'hyper'/'softmax' variants: the row's
 //                         logits already sit in LDS.
 //  * gt_row_online /      the 'tiling' variant: 64-edge tiles + online softmax, no degree limit.
@@ -51,6 +52,34 @@ __device__ __forceinline__ void sddmm_range(int ebeg, int eend, int first, int s
     frag_load<C>(b0, B + (size_t)cb[e] * hf, f, gl);
     const float d0 = lanes_sum<C::G>(frag_dot<C>(a0, b0));
     if (gl == 0) wr(e, val ? d0 * val[e] : d0);
+  }
+}
+
+// d_e = <a, X[cols[e]]> for the nt (<= 64) edges of a tile; lane 0 of each group writes sw[e].  4 gathers in flight.
+template <class C>
+__device__ __forceinline__ void tile_dots(const Frag<C> &a, const int *cols, int nt, const float *__restrict__ X,
+                                          size_t hf, int f, int gid, int gl, float *sw) {
+  int e = gid;
+  for (; e + 3 * C::EPW < nt; e += 4 * C::EPW) {
+    Frag<C> x0, x1, x2, x3;
+    frag_load<C>(x0, X + (size_t)cols[e] * hf, f, gl);
+    frag_load<C>(x1, X + (size_t)cols[e + C::EPW] * hf, f, gl);
+    frag_load<C>(x2, X + (size_t)cols[e + 2 * C::EPW] * hf, f, gl);
+    frag_load<C>(x3, X + (size_t)cols[e + 3 * C::EPW] * hf, f, gl);
+    const float d0 = lanes_sum<C::G>(frag_dot<C>(a, x0)), d1 = lanes_sum<C::G>(frag_dot<C>(a, x1));
+    const float d2 = lanes_sum<C::G>(frag_dot<C>(a, x2)), d3 = lanes_sum<C::G>(frag_dot<C>(a, x3));
+    if (gl == 0) {
+      sw[e] = d0;
+      sw[e + C::EPW] = d1;
+      sw[e + 2 * C::EPW] = d2;
+      sw[e + 3 * C::EPW] = d3;
+    }
+  }
+  for (; e < nt; e += C::EPW) {
+    Frag<C> x0;
+    frag_load<C>(x0, X + (size_t)cols[e] * hf, f, gl);
+    const float d0 = lanes_sum<C::G>(frag_dot<C>(a, x0));
+    if (gl == 0) sw[e] = d0;
   }
 }
 

@@ -24,34 +24,6 @@
 
 namespace dfgnn {
 
-// d_e = <a, X[cols[e]]> for the nt (<= 64) edges of a tile; lane 0 of each group writes sw[e].  4 gathers in flight.
-template <class C>
-__device__ __forceinline__ void tile_dots(const Frag<C> &a, const int *cols, int nt, const float *__restrict__ X,
-                                          size_t hf, int f, int gid, int gl, float *sw) {
-  int e = gid;
-  for (; e + 3 * C::EPW < nt; e += 4 * C::EPW) {
-    Frag<C> x0, x1, x2, x3;
-    frag_load<C>(x0, X + (size_t)cols[e] * hf, f, gl);
-    frag_load<C>(x1, X + (size_t)cols[e + C::EPW] * hf, f, gl);
-    frag_load<C>(x2, X + (size_t)cols[e + 2 * C::EPW] * hf, f, gl);
-    frag_load<C>(x3, X + (size_t)cols[e + 3 * C::EPW] * hf, f, gl);
-    const float d0 = lanes_sum<C::G>(frag_dot<C>(a, x0)), d1 = lanes_sum<C::G>(frag_dot<C>(a, x1));
-    const float d2 = lanes_sum<C::G>(frag_dot<C>(a, x2)), d3 = lanes_sum<C::G>(frag_dot<C>(a, x3));
-    if (gl == 0) {
-      sw[e] = d0;
-      sw[e + C::EPW] = d1;
-      sw[e + 2 * C::EPW] = d2;
-      sw[e + 3 * C::EPW] = d3;
-    }
-  }
-  for (; e < nt; e += C::EPW) {
-    Frag<C> x0;
-    frag_load<C>(x0, X + (size_t)cols[e] * hf, f, gl);
-    const float d0 = lanes_sum<C::G>(frag_dot<C>(a, x0));
-    if (gl == 0) sw[e] = d0;
-  }
-}
-
 // Rows (CSR pass) / columns (CSC pass) a launch covers: all of them, grid-strided -- or, next to the matrix-core
 // kernels on a batch with a block plan, only the closed ranges those kernels do not serve: two lists of (n0, n1) pairs
 // (the plan's non-dense fit ranges, whose n1 carries flag bits, and its spill chunks), one workgroup per pair.

@@ -205,6 +205,69 @@ std::vector<Tensor> gt_bwd_stats(const Tensor &row_ptr, const Tensor &col_ind, c
   return {dQ, dK, dV};
 }
 
+// ---- the general statistics pair (include/dfgnn.h: dfgnn_gt_fwd_rowstats / dfgnn_gt_bwd_rowstats): any graph, no plan ----
+// val: edge values in CSR order, or nothing (unit values)
+GtDims gt_rowstats_checks(const Tensor &row_ptr, const Tensor &col_ind, const c10::optional<Tensor> &val, const Tensor &Q,
+                          const Tensor &K, const Tensor &V) {
+  const GtDims d = gt_stats_checks(row_ptr, col_ind, Q, K, V);
+  if (val.has_value()) {
+    check_f32(*val, "val");
+    check_edges(*val, d.nnz, "val");
+    check_same_device(Q, {&*val});
+  }
+  return d;
+}
+inline const float *edge_val_ptr(const c10::optional<Tensor> &val, bool unit_val) {
+  return (unit_val || !val.has_value()) ? nullptr : val->data_ptr<float>();
+}
+
+std::vector<Tensor> gt_fwd_rowstats(const Tensor &row_ptr, const Tensor &col_ind, const c10::optional<Tensor> &val, const Tensor &Q,
+                                    const Tensor &K, const Tensor &V, bool unit_val) {
+  const GtDims d = gt_rowstats_checks(row_ptr, col_ind, val, Q, K, V);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
+  Tensor out = torch::empty_like(Q);
+  Tensor row_max = torch::empty({d.m, d.h}, Q.options()), row_sum = torch::empty({d.m, d.h}, Q.options());
+  check_rc(dfgnn_gt_fwd_rowstats(d.m, d.nnz, d.h, d.f, row_ptr.data_ptr<int>(), col_ind.data_ptr<int>(),
+                                 edge_val_ptr(val, unit_val), Q.data_ptr<float>(), K.data_ptr<float>(),
+                                 V.data_ptr<float>(), row_max.data_ptr<float>(), row_sum.data_ptr<float>(),
+                                 out.data_ptr<float>(), cur_stream()),
+           "gt_forward_rowstats");
+  return {out, row_max, row_sum};
+}
+
+std::vector<Tensor> gt_bwd_rowstats(const Tensor &row_ptr, const Tensor &col_ind, const c10::optional<Tensor> &val, const Tensor &col_ptr,
+                                    const Tensor &row_ind, const Tensor &val_idx, const Tensor &Q, const Tensor &K,
+                                    const Tensor &V, const Tensor &out, const Tensor &row_max, const Tensor &row_sum,
+                                    const Tensor &grad, bool unit_val) {
+  const GtDims d = gt_rowstats_checks(row_ptr, col_ind, val, Q, K, V);
+  check_i32(col_ptr, "col_ptr");
+  check_i32(row_ind, "row_ind");
+  check_i32(val_idx, "val_idx");
+  check_edges(row_ind, d.nnz, "row_ind");
+  check_edges(val_idx, d.nnz, "val_idx");
+  TORCH_CHECK(col_ptr.dim() == 1 && col_ptr.size(0) == d.m + 1, "col_ptr must have shape (", d.m + 1,
+              ",): the adjacency must be square");
+  check_feat3(out, Q, "out");
+  check_feat3(grad, Q, "grad");
+  check_f32(row_max, "row_max");
+  check_f32(row_sum, "row_sum");
+  for (const Tensor *t : {&row_max, &row_sum})
+    TORCH_CHECK(t->dim() == 2 && t->size(0) == d.m && t->size(1) == d.h, "row_max / row_sum must have shape (", d.m, ", ", d.h,
+                "), got ", t->sizes());
+  check_same_device(Q, {&col_ptr, &row_ind, &val_idx, &out, &row_max, &row_sum, &grad});
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
+  Tensor delta = torch::empty({d.m, d.h}, Q.options());
+  Tensor dQ = torch::empty_like(Q), dK = torch::empty_like(K), dV = torch::empty_like(V);
+  check_rc(dfgnn_gt_bwd_rowstats(d.m, d.nnz, d.h, d.f, row_ptr.data_ptr<int>(), col_ind.data_ptr<int>(),
+                                 edge_val_ptr(val, unit_val), col_ptr.data_ptr<int>(), row_ind.data_ptr<int>(),
+                                 val_idx.data_ptr<int>(), Q.data_ptr<float>(), K.data_ptr<float>(), V.data_ptr<float>(),
+                                 out.data_ptr<float>(), row_max.data_ptr<float>(), row_sum.data_ptr<float>(),
+                                 grad.data_ptr<float>(), delta.data_ptr<float>(), dQ.data_ptr<float>(), dK.data_ptr<float>(),
+                                 dV.data_ptr<float>(), cur_stream()),
+           "gt_backward_rowstats");
+  return {dQ, dK, dV};
+}
+
 // ---- the attn_edge pair in rank order (include/dfgnn.h: dfgnn_gt_hyper_fwd_ranked / dfgnn_gt_bwd_ranked) ----------------
 std::vector<Tensor> gt_hyper_fwd_ranked(const Tensor &row_ptr, const Tensor &col_ind, const Tensor &Q, const Tensor &K,
                                         const Tensor &V, int64_t plan, int64_t meta) {
@@ -490,6 +553,8 @@ PYBIND11_MODULE(_dfgnn_ext, m) {
   m.def("gt_bwd", &gt_bwd, "fused GT conv backward");
   m.def("gt_hyper_fwd_stats", &gt_hyper_fwd_stats, "fused GT conv 'hyper' training forward, row statistics instead of attn_edge");
   m.def("gt_bwd_stats", &gt_bwd_stats, "fused GT conv backward from the row statistics");
+  m.def("gt_fwd_rowstats", &gt_fwd_rowstats, "fused GT conv training forward of any graph, row statistics instead of attn_edge");
+  m.def("gt_bwd_rowstats", &gt_bwd_rowstats, "fused GT conv backward of any graph from the forward's output and row statistics");
   m.def("gt_hyper_fwd_ranked", &gt_hyper_fwd_ranked, "fused GT conv 'hyper' training forward, attention values in rank order");
   m.def("gt_bwd_ranked", &gt_bwd_ranked, "fused GT conv backward from rank-ordered attention values");
   m.def("plan_dense_weights", &plan_dense_weights, "edge values of a plan's dense ranges in dense form (dfgnn_plan_dense_weights)");

@@ -28,6 +28,8 @@ SIGNATURES = {
     "dfgnn_plan_dense_weights": [_i, _i] + [_vp] * 6,
     "dfgnn_gt_hyper_fwd_ranked": [_i, _i, _i, _i] + [_vp] * 10,
     "dfgnn_gt_bwd_ranked": [_i, _i, _i, _i] + [_vp] * 13,
+    "dfgnn_gt_fwd_rowstats": [_i, _i, _i, _i] + [_vp] * 10,
+    "dfgnn_gt_bwd_rowstats": [_i, _i, _i, _i] + [_vp] * 18,
     "dfgnn_gt_bwd_rows": [_i, _i, _i, _i] + [_vp] * 11,
     "dfgnn_gt_bwd_cols": [_i, _i, _i, _i] + [_vp] * 11,
     "dfgnn_gt_tiling_fwd": [_i, _i, _i, _i] + [_vp] * 8,

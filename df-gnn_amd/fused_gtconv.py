@@ -333,6 +333,73 @@ def gt_backward_stats(row_ptr, col_ind, Q, K, V, row_max, row_sum, grad, plan=No
     return [dQ, dK, dV]
 
 
+# ---- the general statistics pair (include/dfgnn.h: dfgnn_gt_fwd_rowstats / dfgnn_gt_bwd_rowstats) --------------------
+# Not part of the reference's module.  The same saved state as the pair above -- two floats per (row, head) -- but for
+# ANY graph: no plan, no degree limit, any f (csrc/gt_train.hip).  Opt-in: DFGNN.operators.fused_gtconv.GTConvFuse_rowstats
+# takes it; FusedGTFunction_hyper does not.
+
+
+def _check_rowstats_graph(row_ptr, col_ind, val, Q, K, V):
+    edge_val = {} if val is None else {"val": val}
+    check_device(row_ptr=row_ptr, col_ind=col_ind, **edge_val)
+    check_contiguous(row_ptr=row_ptr, col_ind=col_ind, **edge_val)
+    check_dtype(torch.int32, row_ptr=row_ptr, col_ind=col_ind)
+    check_dtype(torch.float32, **edge_val)
+    _check_qkv(Q, K, V)
+    m, nnz, h, f = _dims(row_ptr, col_ind, Q)
+    _check_graph(row_ptr, col_ind, Q.size(0))
+    _check_edges(nnz, **edge_val)
+    return m, nnz, h, f
+
+
+def gt_forward_rowstats(row_ptr, col_ind, val, Q, K, V):
+    """-> [out, row_max[m, h], row_sum[m, h]]: the training forward of any graph without attn_edge.
+    val: edge values fp32[nnz] in CSR order; None or all ones: unit values."""
+    ext = _n.ext()
+    if ext is not None and hasattr(ext, "gt_fwd_rowstats"):
+        return ext.gt_fwd_rowstats(row_ptr, col_ind, val, Q, K, V, val_ptr(val) is None)
+    m, nnz, h, f = _check_rowstats_graph(row_ptr, col_ind, val, Q, K, V)
+    with torch.cuda.device(Q.device):
+        out = torch.empty_like(Q)
+        row_max = torch.empty((m, h), dtype=torch.float32, device=Q.device)
+        row_sum = torch.empty((m, h), dtype=torch.float32, device=Q.device)
+        _n.check(_n.lib().dfgnn_gt_fwd_rowstats(m, nnz, h, f, ptr(row_ptr), ptr(col_ind), val_ptr(val), ptr(Q), ptr(K),
+                                                ptr(V), ptr(row_max), ptr(row_sum), ptr(out), stream_ptr(Q.device)),
+                 "gt_forward_rowstats")
+    return [out, row_max, row_sum]
+
+
+def gt_backward_rowstats(row_ptr, col_ind, val, col_ptr, row_ind, val_idx, Q, K, V, out, row_max, row_sum, grad):
+    """-> [dQ, dK, dV] from the forward's output and row statistics (the attention is recomputed edge by edge).
+    val as in gt_forward_rowstats."""
+    val_idx = as_int32(val_idx)
+    ext = _n.ext()
+    if ext is not None and hasattr(ext, "gt_bwd_rowstats"):
+        return ext.gt_bwd_rowstats(row_ptr, col_ind, val, col_ptr, row_ind, val_idx, Q, K, V, out, row_max, row_sum, grad,
+                                   val_ptr(val) is None)
+    m, nnz, h, f = _check_rowstats_graph(row_ptr, col_ind, val, Q, K, V)
+    check_device(col_ptr=col_ptr, row_ind=row_ind, val_idx=val_idx, out=out, row_max=row_max, row_sum=row_sum, grad=grad)
+    check_contiguous(col_ptr=col_ptr, row_ind=row_ind, val_idx=val_idx, out=out, row_max=row_max, row_sum=row_sum,
+                     grad=grad)
+    check_dtype(torch.int32, col_ptr=col_ptr, row_ind=row_ind)
+    check_dtype(torch.float32, out=out, row_max=row_max, row_sum=row_sum, grad=grad)
+    check_feat3(Q=Q, out=out, grad=grad)
+    _check_edges(nnz, row_ind=row_ind, val_idx=val_idx)
+    if col_ptr.dim() != 1 or col_ptr.size(0) != m + 1:
+        raise RuntimeError(f"col_ptr must have shape ({m + 1},): the adjacency must be square")
+    for name, t in (("row_max", row_max), ("row_sum", row_sum)):
+        if tuple(t.shape) != (m, h):
+            raise RuntimeError(f"{name} must have shape ({m}, {h}), got {tuple(t.shape)}")
+    with torch.cuda.device(Q.device):
+        delta = torch.empty((m, h), dtype=torch.float32, device=Q.device)
+        dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
+        _n.check(_n.lib().dfgnn_gt_bwd_rowstats(m, nnz, h, f, ptr(row_ptr), ptr(col_ind), val_ptr(val), ptr(col_ptr),
+                                                ptr(row_ind), ptr(val_idx), ptr(Q), ptr(K), ptr(V), ptr(out),
+                                                ptr(row_max), ptr(row_sum), ptr(grad), ptr(delta), ptr(dQ), ptr(dK),
+                                                ptr(dV), stream_ptr(Q.device)), "gt_backward_rowstats")
+    return [dQ, dK, dV]
+
+
 def _ext_variant(which, indptr, indices, rows, val, Q, K, V):
     """The CSR-taking inference variants through the torch C++ binding (csrc/torch_ext.cpp: gt_variant_fwd), or None."""
     ext = _n.ext()

@@ -159,6 +159,29 @@ int dfgnn_gt_bwd_ranked(int m, int nnz, int h, int f, const int *row_ptr, const 
                         const float *K, const float *V, const float *attn_ranked, const float *grad_out, float *dQ,
                         float *dK, float *dV, const int *plan, const int *plan_meta, dfgnn_stream_t stream);
 
+/* The statistics-saving training pair for ANY graph (csrc/gt_train.hip): no plan, no degree limit, any f -- full graphs,
+ * batches with a sparse, oversized or spilled range, low-degree batches; everything the dense pair above returns
+ * DFGNN_E_UNSUPPORTED for.  Replaces what FusedGTFunction_hyper (DFGNN/operators/fused_gtconv.py:79-158) keeps between
+ * forward and backward: instead of attn_edge[h, nnz] (gt_hyper_forward, fused_gtconv_hyper.cu:146-149) and the
+ * grad_edge[h, nnz] scratch of gt_backward (fused_gtconv_backward.cu:40-191) -- 8 h nnz bytes alive per layer -- the
+ * forward saves row_max, row_sum: fp32[m, h] (conventions as above: an empty row has out = 0, row_max = -1e38,
+ * row_sum = 0) and the backward, given the forward's `out`, rebuilds each edge from rows it gathers anyway:
+ *   delta_i = <grad_out_i, out_i>,  P_e = exp(val_e <Q_i, K_j> - row_max_i) / row_sum_i,
+ *   dS_e = P_e (<grad_out_i, V_j> - delta_i),  dQ_i = sum dS_e val_e K_j,  dK_j = sum dS_e val_e Q_i,  dV_j = sum P_e grad_out_i
+ * in a CSR pass (delta, dQ; one sweep per row) and a CSC pass (dK, dV).
+ *   val      fp32[nnz], CSR order, NULL = unit values (then val_idx is not read and may be NULL)
+ *   delta    caller scratch fp32[m, h], written by the CSR pass and read by the CSC pass
+ *   row_max = row_sum = NULL in the forward: nothing is saved (inference; same result as dfgnn_gt_tiling_fwd)
+ * dQ, dK, dV are written in full (an empty row / column gives zeros; no pre-zeroing, no atomics: the sums are
+ * deterministic).  Graphs with fewer than 8 edges per row on average run a lane group per row, others a wave per row. */
+int dfgnn_gt_fwd_rowstats(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                          const float *Q, const float *K, const float *V, float *row_max, float *row_sum, float *out,
+                          dfgnn_stream_t stream);
+int dfgnn_gt_bwd_rowstats(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                          const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q, const float *K,
+                          const float *V, const float *out, const float *row_max, const float *row_sum,
+                          const float *grad_out, float *delta, float *dQ, float *dK, float *dV, dfgnn_stream_t stream);
+
 /* weights[256 i + c] = val[e] for the edge e from node i to the c-th node of i's range of the plan, 0 elsewhere:
  * dfgnn_plan_dense_weights_floats(m) = 256 m floats (device, 16-byte aligned), written by one memset + one kernel on
  * `stream`.  val: fp32[nnz] in CSR order.  Only the dense ranges of the plan are filled (dfgnn_gt_stats_applies == 1:
