@@ -25,7 +25,7 @@ class FusedGTFunction_hyper(torch.autograd.Function):
 
     The reference's forward saves the normalised attention (attn_edge[h, nnz]) for the backward.  When the whole batch
     runs on the matrix-core kernels (fused_gt.gt_stats_pair_applies: a block plan of dense ranges) and has at least two
-    heads or edge values other than ones (fused_gt.gt_stats_pair_chosen: there it is the faster pair, measured) the
+    heads or edge values other than ones (fused_gt.gt_training_pair: there it is the faster pair, measured) the
     forward saves two floats per (row, head) instead -- logit maximum and sum of exponentials -- and the backward
     recomputes the attention (include/dfgnn.h: dfgnn_gt_hyper_fwd_stats / dfgnn_gt_bwd_stats): same gradients, 8 h nnz
     bytes less through HBM.  At one head with unit values such a batch keeps the reference's form but with attn_edge in
@@ -35,38 +35,34 @@ class FusedGTFunction_hyper(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V):
         ctx.smem = smem_consume
-        ctx.stats = fused_gt.gt_stats_pair_chosen(row_ptr, col_ind, val, Q)   # the block plan, or None
-        if ctx.stats is not None:
-            out_feat, row_max, row_sum = fused_gt.gt_hyper_forward_stats(row_ptr, col_ind, Q, K, V, ctx.stats, val)
+        ctx.pair, ctx.plan = fused_gt.gt_training_pair(row_ptr, col_ind, val, Q)   # the pair's block plan, or None
+        if ctx.pair == "stats":
+            out_feat, row_max, row_sum = fused_gt.gt_hyper_forward_stats(row_ptr, col_ind, Q, K, V, ctx.plan, val)
             ctx.save_for_backward(row_ptr, col_ind, Q, K, V, row_max, row_sum, val)
-            return out_feat
-        ctx.ranked = fused_gt.gt_ranked_pair_chosen(row_ptr, col_ind, val, Q)   # the block plan, or None
-        if ctx.ranked is not None:   # one head, all dense, unit values: attn_edge in rank order (same pair, cheaper forward)
-            out_feat, attn_ranked = fused_gt.gt_hyper_forward_ranked(row_ptr, col_ind, Q, K, V, ctx.ranked)
+        elif ctx.pair == "ranked":   # one head, all dense, unit values: attn_edge in rank order (same pair, cheaper forward)
+            out_feat, attn_ranked = fused_gt.gt_hyper_forward_ranked(row_ptr, col_ind, Q, K, V, ctx.plan)
             ctx.save_for_backward(row_ptr, col_ind, Q, K, V, attn_ranked)
-            return out_feat
-        out_feat, attn_edge = fused_gt.gt_hyper_forward(
-            row_ptr, col_ind, rows, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V)
-        ctx.save_for_backward(row_ptr, col_ind, rows, val, col_ptr, row_ind, val_idx, Q, K, V, attn_edge)
+        else:
+            out_feat, attn_edge = fused_gt.gt_hyper_forward(
+                row_ptr, col_ind, rows, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V)
+            ctx.save_for_backward(row_ptr, col_ind, rows, val, col_ptr, row_ind, val_idx, Q, K, V, attn_edge)
         return out_feat
 
     @staticmethod
     def backward(ctx, grad_out):
-        if ctx.stats is not None:
+        if ctx.pair == "stats":
             row_ptr, col_ind, Q, K, V, row_max, row_sum, val = ctx.saved_tensors
-            grad_Q, grad_K, grad_V = fused_gt.gt_backward_stats(row_ptr, col_ind, Q, K, V, row_max, row_sum,
-                                                                grad_out.contiguous(), ctx.stats, val)
-            return (None,) * 8 + (grad_Q, grad_K, grad_V)
-        if ctx.ranked is not None:
+            grads = fused_gt.gt_backward_stats(row_ptr, col_ind, Q, K, V, row_max, row_sum, grad_out.contiguous(),
+                                               ctx.plan, val)
+        elif ctx.pair == "ranked":
             row_ptr, col_ind, Q, K, V, attn_ranked = ctx.saved_tensors
-            grad_Q, grad_K, grad_V = fused_gt.gt_backward_ranked(row_ptr, col_ind, Q, K, V, attn_ranked,
-                                                                 grad_out.contiguous(), ctx.ranked)
-            return (None,) * 8 + (grad_Q, grad_K, grad_V)
-        row_ptr, col_ind, rows, val, col_ptr, row_ind, val_idx, Q, K, V, attn_edge = ctx.saved_tensors
-        grad_Q, grad_K, grad_V = fused_gt.gt_backward(
-            row_ptr, col_ind, rows, val, col_ptr, row_ind, val_idx, ctx.smem, Q, K, V, attn_edge,
-            grad_out.contiguous())
-        return (None,) * 8 + (grad_Q, grad_K, grad_V)
+            grads = fused_gt.gt_backward_ranked(row_ptr, col_ind, Q, K, V, attn_ranked, grad_out.contiguous(), ctx.plan)
+        else:
+            row_ptr, col_ind, rows, val, col_ptr, row_ind, val_idx, Q, K, V, attn_edge = ctx.saved_tensors
+            grads = fused_gt.gt_backward(
+                row_ptr, col_ind, rows, val, col_ptr, row_ind, val_idx, ctx.smem, Q, K, V, attn_edge,
+                grad_out.contiguous())
+        return (None,) * 8 + tuple(grads)
 
 
 def GTConvFuse_hyper(rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V):

@@ -1,28 +1,17 @@
-"""Checks shared by the fused_gtconv / fused_gatconv binding modules.
+"""What the fused_gtconv / fused_gatconv / dfgnn_preprocess binding modules share: the argument checks of the ctypes
+transport by family, its call helper, the `val` and block-plan look-ups and their caches.
 
-Mirrors the reference's binding-level checks (DFGNN/src/fused_gtconv/fused_gtconv.cpp:7-13:
-CHECK_DEVICE / CHECK_CONTIGUOUS raise RuntimeError) and turns its compiled-out dtype asserts
+The checks mirror the reference's binding-level ones (DFGNN/src/fused_gtconv/fused_gtconv.cpp:7-13:
+CHECK_DEVICE / CHECK_CONTIGUOUS raise RuntimeError) and turn its compiled-out dtype asserts
 (fused_gtconv.cpp:103-112) into real errors.
 """
+import collections
+import ctypes
+import os
+
 import torch
 
-
-def check_device(**tensors):
-    for name, t in tensors.items():
-        if not t.is_cuda:
-            raise RuntimeError(f"{name} must be on CUDA")
-
-
-def check_contiguous(**tensors):
-    for name, t in tensors.items():
-        if not t.is_contiguous():
-            raise RuntimeError(f"{name} must be contiguous")
-
-
-def check_dtype(dtype, **tensors):
-    for name, t in tensors.items():
-        if t.dtype != dtype:
-            raise RuntimeError(f"{name} must have dtype {dtype}, got {t.dtype}")
+import dfgnn_native as _n
 
 
 def as_int32(t):
@@ -30,23 +19,79 @@ def as_int32(t):
     return t if t.dtype == torch.int32 else t.to(torch.int32)
 
 
-def check_feat3(**tensors):
-    shape = None
+# ---- argument checks of the ctypes transport, by family (csrc/torch_ext.cpp makes the same ones for the extension) ------
+# A family is a set of tensors that must agree in dtype and shape.  `ref` is the tensor whose device the call runs on (the
+# first feature tensor): every family compares its members' device with it -- a pointer of another GPU must not be handed
+# to a kernel of this one.
+def _family(ref, dtype, shape, tensors):
+    """Every tensor of {name: tensor} on ref's GPU, contiguous, of `dtype` and (unless None) of `shape`."""
+    dev = ref.get_device()   # (-1: not on a GPU)
     for name, t in tensors.items():
-        if t.dim() != 3:
-            raise RuntimeError(f"{name} must have shape [nodes, heads, feat], got {tuple(t.shape)}")
-        if shape is None:
-            shape = t.shape
-        elif t.shape != shape:
-            raise RuntimeError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+        if dev < 0 or t.get_device() != dev:
+            if not t.is_cuda:
+                raise RuntimeError(f"{name} must be on CUDA")
+            raise RuntimeError(f"every tensor must live on one device ({ref.device}), got {name} on {t.device}")
+        if not t.is_contiguous():
+            raise RuntimeError(f"{name} must be contiguous")
+        if t.dtype != dtype:
+            raise RuntimeError(f"{name} must have dtype {dtype}, got {t.dtype}")
+        if shape is not None and t.shape != shape:
+            raise RuntimeError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+
+
+def check_family(ref, dtype, **tensors):
+    """Tensors of any shape."""
+    _family(ref, dtype, None, tensors)
+
+
+def check_feats(**tensors):
+    """fp32 feature tensors [nodes, heads, feat] of one shape, the first one being the call's `ref` -> (nodes, h, f)."""
+    name, ref = next(iter(tensors.items()))
+    _family(ref, torch.float32, ref.shape, tensors)
+    if ref.dim() != 3:
+        raise RuntimeError(f"{name} must have shape [nodes, heads, feat], got {tuple(ref.shape)}")
+    return tuple(ref.shape)
+
+
+def check_csr(ref, m, indptr, indices):
+    """The int32 CSR arrays of a graph whose `m` rows are the nodes of the feature tensors -> nnz."""
+    _family(ref, torch.int32, None, {"indptr": indptr, "indices": indices})
+    if indptr.dim() != 1 or indices.dim() != 1:
+        raise RuntimeError("indptr / indices must be 1-D")
+    if indptr.size(0) - 1 != m:
+        raise RuntimeError(f"indptr describes {indptr.size(0) - 1} rows but features have {m} nodes")
+    return indices.size(0)
+
+
+def check_csc(ref, m, nnz, col_ptr, **per_edge):
+    """The int32 CSC arrays next to a CSR structure of m rows and nnz edges: col_ptr and its per-edge arrays."""
+    _family(ref, torch.int32, None, {"col_ptr": col_ptr})
+    if col_ptr.shape != (m + 1,):
+        raise RuntimeError(f"col_ptr must have shape ({m + 1},): the adjacency must be square")
+    _family(ref, torch.int32, (nnz,), per_edge)
+
+
+def check_edges(ref, nnz, dtype, **tensors):
+    """Per-edge arrays [nnz]."""
+    _family(ref, dtype, (nnz,), tensors)
+
+
+def check_2d(ref, n, h, **tensors):
+    """fp32 arrays [n, h]: per-row statistics and scores (n = m), the dropout randoms (n = nnz)."""
+    _family(ref, torch.float32, (n, h), tensors)
 
 
 def stream_ptr(device):
     return torch.cuda.current_stream(device).cuda_stream
 
 
-def ptr(t):
-    return t.data_ptr() if t is not None else None
+def call(symbol, what, device, *args):
+    """The ctypes transport: dfgnn_native.lib().<symbol>(*args, stream) on `device` and on torch's current stream of it.
+    Tensors go as their addresses, None as NULL, numbers as they are; a non-zero return raises the library's RuntimeError
+    under the operator's name `what`."""
+    with torch.cuda.device(device):
+        _n.check(getattr(_n.lib(), symbol)(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args],
+                                           stream_ptr(device)), what)
 
 
 class _KeyedCache:
@@ -57,8 +102,6 @@ class _KeyedCache:
     default 16) is what that costs."""
 
     def __init__(self, entries=None):
-        import collections
-        import os
         self.entries = entries or int(os.environ.get("DFGNN_CACHE_ENTRIES", "16"))
         self.d = collections.OrderedDict()
 
@@ -91,7 +134,6 @@ def plan_dense_weights(plan, row_ptr, val):
     """The edge values `val` (fp32[nnz] / [nnz, 1], CSR order) in the dense form the WEIGHTED matrix-core kernels read
     (include/dfgnn.h: dfgnn_plan_dense_weights): fp32[256 m], built once per (plan, val tensor version) and cached --
     edge weights of a dataset do not change from step to step."""
-    import dfgnn_native as _n
     key = _KeyedCache.key_of(val, extra=(plan.key,))
     w = _weights_cache.get(key)
     if w is not None:
@@ -100,16 +142,12 @@ def plan_dense_weights(plan, row_ptr, val):
     if v.dtype != torch.float32 or not v.is_contiguous():
         raise RuntimeError("val must be contiguous float32")
     ext = _n.ext()
-    pp, mp = plan.ptrs()
-    with torch.cuda.device(val.device):
-        if ext is not None and hasattr(ext, "plan_dense_weights"):
-            w = ext.plan_dense_weights(row_ptr, v, pp, mp)
-        else:
-            L = _n.lib()
-            m, nnz = plan.meta[4], plan.meta[5]
-            w = torch.empty(int(L.dfgnn_plan_dense_weights_floats(m)), dtype=torch.float32, device=val.device)
-            _n.check(L.dfgnn_plan_dense_weights(m, nnz, row_ptr.data_ptr(), v.data_ptr(), pp, mp, w.data_ptr(),
-                                                stream_ptr(val.device)), "plan_dense_weights")
+    if ext is not None:
+        w = ext.plan_dense_weights(row_ptr, v, *plan.ptrs())
+    else:
+        m, nnz = plan.meta[4], plan.meta[5]
+        w = torch.empty(int(_n.lib().dfgnn_plan_dense_weights_floats(m)), dtype=torch.float32, device=val.device)
+        call("dfgnn_plan_dense_weights", "plan_dense_weights", val.device, m, nnz, row_ptr, v, *plan.ptrs(), w)
     return _weights_cache.put(key, w, val, plan)
 
 
@@ -137,12 +175,14 @@ def val_ptr(val):
 
 # ---- block plan cache -----------------------------------------------------------------------------
 class BlockPlan:
-    """Device plan buffer + its 12 host header words (include/dfgnn.h, dfgnn_plan_build)."""
-    __slots__ = ("buf", "meta", "_meta_c", "key", "_stats_ok")
+    """Device plan buffer + its 12 host header words (include/dfgnn.h, dfgnn_plan_build).  key: plan_key() of what it
+    was built from."""
+    __slots__ = ("buf", "meta", "_meta_c", "key", "_ptrs", "_stats_ok")
 
     def __init__(self, buf, meta_c, key):
         self.buf, self._meta_c, self.key = buf, meta_c, key
         self.meta = list(meta_c)
+        self._ptrs = (buf.data_ptr(), ctypes.addressof(meta_c))
         self._stats_ok = {}
 
     def stats_applies(self, h):
@@ -150,11 +190,7 @@ class BlockPlan:
         the matrix-core kernels, so the statistics-saving training pair can run it."""
         ok = self._stats_ok.get(h)
         if ok is None:
-            import ctypes
-
-            import dfgnn_native as _n
-            ok = bool(_n.lib().dfgnn_gt_stats_applies(self.meta[4], self.meta[5], h, self.meta[6],
-                                                      ctypes.addressof(self._meta_c)))
+            ok = bool(_n.lib().dfgnn_gt_stats_applies(self.meta[4], self.meta[5], h, self.meta[6], self._ptrs[1]))
             self._stats_ok[h] = ok
         return ok
 
@@ -181,67 +217,69 @@ class BlockPlan:
         return self.meta[10]
 
     def ptrs(self):
-        import ctypes
-        return self.buf.data_ptr(), ctypes.addressof(self._meta_c)
+        """(plan_ptr, meta_ptr) for the C ABI."""
+        return self._ptrs
+
+
+def plan_ptrs(plan):
+    """BlockPlan | None -> (plan_ptr, meta_ptr) as either transport takes them; 0 is NULL: no plan."""
+    return plan._ptrs if plan is not None else (0, 0)
+
+
+def plan_key(indptr, indices, f):
+    """What a plan is a plan OF: the MEMORY of the two CSR arrays (address, length, version counter) and the feature
+    width.  The key of the plan cache, the test that a plan found on a tensor object is still that tensor's, and (as
+    BlockPlan.key) what plan_dense_weights tells plans apart by."""
+    return (indptr.data_ptr(), indptr.size(0), indptr._version, indices.data_ptr(), indices.size(0), indices._version, f)
 
 
 def build_plan(indptr, indices, f):
     """Run dfgnn_plan_build for this CSR structure and feature width (synchronises the stream once)."""
-    import ctypes
-
-    import dfgnn_native as _n
     m, nnz = indptr.size(0) - 1, indices.size(0)
     ext = _n.ext()
-    if ext is not None and hasattr(ext, "plan_build"):  # torch C++ binding: allocation + call without ctypes marshalling
+    if ext is not None:  # torch C++ binding: allocation + call without ctypes marshalling
         buf, meta_l = ext.plan_build(indptr, indices, int(f))
-        return BlockPlan(buf, (ctypes.c_int * 12)(*meta_l), (indices.data_ptr(), nnz, indptr._version, indices._version, f))
-    L = _n.lib()
-    with torch.cuda.device(indptr.device):
-        buf = torch.empty(int(L.dfgnn_plan_ints(m, nnz)), dtype=torch.int32, device=indptr.device)
+        meta = (ctypes.c_int * 12)(*meta_l)
+    else:
+        buf = torch.empty(int(_n.lib().dfgnn_plan_ints(m, nnz)), dtype=torch.int32, device=indptr.device)
         meta = (ctypes.c_int * 12)()
-        _n.check(L.dfgnn_plan_build(m, nnz, f, indptr.data_ptr(), indices.data_ptr(), buf.data_ptr(),
-                                    ctypes.addressof(meta), stream_ptr(indptr.device)), "dfgnn_plan_build")
-    return BlockPlan(buf, meta, (indices.data_ptr(), nnz, indptr._version, indices._version, f))
+        call("dfgnn_plan_build", "dfgnn_plan_build", indptr.device, m, nnz, f, indptr, indices, buf, ctypes.addressof(meta))
+    return BlockPlan(buf, meta, plan_key(indptr, indices, f))
 
 
-def get_plan_obj(indptr, indices, f, enable=True):
-    """The BlockPlan object behind get_plan (None when there is none)."""
-    if get_plan(indptr, indices, f, enable)[0] is None:
-        return None
-    return indptr.__dict__["_dfgnn_plans"][f]
-
-
-def get_plan(indptr, indices, f, enable=True):
-    """Plan of (indptr, indices, f), built on first use and cached by the identity of the two arrays' MEMORY (address,
-    length, version counter; _KeyedCache) -- the reference's preprocess_* tuples keep those arrays alive across the layers /
-    epochs that reuse a batch (DFGNN/layers/util.py:82-142), so the plan is built once per batch structure, also when
-    the tensors reach the operator re-wrapped (.detach(), views, rebuilt tuples).
-    Returns (plan_ptr, meta_ptr, needs_edge_scratch) for the C ABI, or (None, None, False)."""
+def get_plan_obj(indptr, indices, Q, enable=True):
+    """The BlockPlan of (indptr, indices, f), or None when there is none.  Q: the call's feature tensor -- only
+    [nodes, heads, f] has a plan -- or f itself.  Built on first use and cached by the identity of the two arrays' MEMORY
+    (plan_key; _KeyedCache) -- the reference's preprocess_* tuples keep those arrays alive across the layers / epochs that
+    reuse a batch (DFGNN/layers/util.py:82-142), so the plan is built once per batch structure, also when the tensors
+    reach the operator re-wrapped (.detach(), views, rebuilt tuples)."""
+    f = Q if isinstance(Q, int) else (Q.size(-1) if Q.dim() == 3 else 0)
     if not enable or f <= 0 or f % 4 != 0 or indices.dim() != 1 or indptr.dim() != 1 or indices.size(0) == 0:
-        return None, None, False
+        return None
     if not (indptr.is_cuda and indices.is_cuda and indptr.dtype == torch.int32 and indices.dtype == torch.int32 and
             indptr.is_contiguous() and indices.is_contiguous()):
-        return None, None, False  # (the binding's argument checks raise the matching error right after)
+        return None  # (the binding's argument checks raise the matching error right after)
     if indices.size(0) < 8 * (indptr.size(0) - 1):
-        return None, None, False  # low-degree graphs take the row-per-lane-group kernels (capi.hip:low_degree)
+        return None  # low-degree graphs take the row-per-lane-group kernels (capi.hip:low_degree)
     # first the Python object itself (the common case: the same preprocess_* tuple call after call; a dict lookup and
-    # four cheap reads), then the memory-identity cache (a re-wrapped tensor)
-    fast = (indices.data_ptr(), indices.size(0), indptr._version, indices._version, f)
+    # a few cheap reads), then the memory-identity cache (a re-wrapped tensor)
+    key = plan_key(indptr, indices, f)
     mine = indptr.__dict__.get("_dfgnn_plans")
     plan = mine.get(f) if mine is not None else None
-    if plan is None or plan.key != fast:
-        key = _KeyedCache.key_of(indptr, indices, extra=(f,))
+    if plan is None or plan.key != key:
         plan = _plan_cache.get(key)
         if plan is None:
             plan = _plan_cache.put(key, build_plan(indptr, indices, f), indptr, indices)
-        plan.key = fast
-        try:
-            indptr.__dict__.setdefault("_dfgnn_plans", {})[f] = plan
-        except AttributeError:
-            pass
-    if plan.num_fit == 0:
+        indptr.__dict__.setdefault("_dfgnn_plans", {})[f] = plan   # (mirror on the tensor object: the fast path above)
+    return plan if plan.num_fit else None
+
+
+def get_plan(indptr, indices, f, enable=True):
+    """get_plan_obj as the C ABI's arguments: (plan_ptr, meta_ptr, needs_edge_scratch), or (None, None, False)."""
+    plan = get_plan_obj(indptr, indices, f, enable)
+    if plan is None:
         return None, None, False
-    return plan.ptrs() + (plan.num_edge_global > 0,)
+    return plan._ptrs + (plan.num_edge_global > 0,)
 
 
 def get_rows(row_ptr, nnz):

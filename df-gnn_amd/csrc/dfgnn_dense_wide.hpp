@@ -19,6 +19,9 @@
 #pragma once
 #include "dfgnn_dense.hpp"
 #include "dfgnn_dense_stamp.hpp"
+#ifndef DFGNN_RING160
+#define DFGNN_RING160 2  // prefetch distance (image phases) of the 129..160-node backward
+#endif
 
 namespace dfgnn {
 

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "dfgnn_device.hpp"
 
 namespace dfgnn {
@@ -107,6 +109,18 @@ int dispatch_cfg(int f, bool vec4, F &&fn) {
   return kErrUnsupported;
 }
 
+// The feature widths the matrix-core kernels are instantiated for.  fn is a generic lambda taking the width as a
+// std::integral_constant; returns its int result, or kErrUnsupported.
+template <class Fn>
+int dispatch_dense(int f, Fn &&fn) {
+  if (f == 8) return fn(std::integral_constant<int, 8>{});    // f = 8 / 16: zero-padded onto the 32-wide layout
+  if (f == 16) return fn(std::integral_constant<int, 16>{});
+  if (f == 32) return fn(std::integral_constant<int, 32>{});
+  if (f == 64) return fn(std::integral_constant<int, 64>{});
+  if (f == 128) return fn(std::integral_constant<int, 128>{});
+  return kErrUnsupported;
+}
+
 inline int launch_status() { return static_cast<int>(hipGetLastError()); }
 // hipFuncSetAttribute(fn, MaxDynamicSharedMemorySize, 160 KB), issued once per (device, kernel) and remembered (capi.hip)
 int set_max_lds_cached_ptr(const void *fn);
@@ -120,6 +134,10 @@ int launch_gt_block_fwd(const Csr &g, const Plan &p, const float *Q, const float
 // matrix-core kernels over the first p.num_dense fit ranges (GT: unit edge values only); DFGNN_DENSE=0 in the
 // environment (diagnostic switch, read once) keeps every range on the edge-walking kernels
 bool dense_enabled();
+// this batch takes the 256-thread forward, two workgroups per CU (dfgnn_dense_lean.hpp): one head of 64 or 128 features and
+// no range of more than 128 nodes; DFGNN_LEAN=0 in the environment (diagnostic switch, read once) keeps every dense range
+// on the 512-thread forward
+bool dense_lean_batch(const Csr &g, const Plan &p);
 int launch_gt_dense_fwd(const Csr &g, const Plan &p, const float *Q, const float *K, const float *V,
                         float *attn_edge, float *out, hipStream_t s);
 int launch_gt_dense_bwd(const Csr &g, const Plan &p, const float *Q, const float *K, const float *V,

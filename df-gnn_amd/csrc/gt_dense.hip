@@ -36,9 +36,6 @@
 #ifndef DFGNN_FW128
 #define DFGNN_FW128 128
 #endif
-#ifndef DFGNN_RING160
-#define DFGNN_RING160 2  // prefetch distance (image phases) of the 129..160-node backward
-#endif
 #include "dfgnn_dense_wide.hpp"
 #include "dfgnn_dense_lean.hpp"
 #include "dfgnn_dense_heads.hpp"
@@ -213,14 +210,9 @@ bool dense_enabled() {
   return on;
 }
 
-template <class Fn>
-static int dispatch_dense(int f, Fn &&fn) {
-  if (f == 8) return fn(std::integral_constant<int, 8>{});    // f = 8 / 16: zero-padded onto the 32-wide layout
-  if (f == 16) return fn(std::integral_constant<int, 16>{});
-  if (f == 32) return fn(std::integral_constant<int, 32>{});
-  if (f == 64) return fn(std::integral_constant<int, 64>{});
-  if (f == 128) return fn(std::integral_constant<int, 128>{});
-  return kErrUnsupported;
+bool dense_lean_batch(const Csr &g, const Plan &p) {
+  static const bool on = [] { const char *e = getenv("DFGNN_LEAN"); return !e || atoi(e) != 0; }();
+  return on && (g.f == 64 || g.f == 128) && g.h == 1 && p.num_dense_wide == 0;
 }
 
 // Heads a workgroup of the multi-head backward walks (ranges of <= 128 nodes): all of them (8 heads of 16: 393 us with
@@ -229,12 +221,6 @@ static int dispatch_dense(int f, Fn &&fn) {
 static int heads_walk() {
   static const int w = [] { const char *e = getenv("DFGNN_HEADS_WALK"); return e ? max(0, atoi(e)) : 64; }();
   return w;
-}
-
-// DFGNN_LEAN=0 in the environment (diagnostic switch, read once): every dense range on the 512-thread forward
-static bool lean_enabled() {
-  static const bool on = [] { const char *e = getenv("DFGNN_LEAN"); return !e || atoi(e) != 0; }();
-  return on;
 }
 
 static int launch_gt_dense_fwd_single(const Csr &g_in, const Plan &p, const float *Q, const float *K, const float *V,
@@ -263,8 +249,7 @@ static int launch_gt_dense_fwd_single(const Csr &g_in, const Plan &p, const floa
 int launch_gt_dense_fwd(const Csr &g_in, const Plan &p, const float *Q, const float *K, const float *V,
                         float *attn_edge, float *out, hipStream_t s) {
   if (p.num_dense == 0) return 0;
-  const bool lean = (g_in.f == 64 || g_in.f == 128) && g_in.h == 1 && p.num_dense_wide == 0 && lean_enabled();
-  if (!lean) return launch_gt_dense_fwd_single(g_in, p, Q, K, V, attn_edge, out, s);
+  if (!dense_lean_batch(g_in, p)) return launch_gt_dense_fwd_single(g_in, p, Q, K, V, attn_edge, out, s);
   Csr g = g_in;
   g.coords = p.coords();
   const dim3 grid(p.num_dense, 1);

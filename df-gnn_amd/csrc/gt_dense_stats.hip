@@ -21,9 +21,6 @@
 
 #include "dfgnn_dense.hpp"
 #include "dfgnn_dense_stamp.hpp"
-#ifndef DFGNN_RING160
-#define DFGNN_RING160 2
-#endif
 #include "dfgnn_dense_wide.hpp"
 #include "dfgnn_dense_lean.hpp"
 #include "dfgnn_dense_heads.hpp"
@@ -113,25 +110,10 @@ __global__ __launch_bounds__(kDenseThreads) void gt_dense_bwd_stats_kernel(
     dense_bwd_body<F, kDenseChunkRows, 2, false, true>(lds, g, n0, n, 0, 0, head, Q, K, V, nullptr, dO, dQ, dK, dV, st);
 }
 
-template <class Fn>
-static int dispatch_dense_stats(int f, Fn &&fn) {
-  if (f == 8) return fn(std::integral_constant<int, 8>{});  // f = 8 / 16: zero-padded onto the 32-wide layout
-  if (f == 16) return fn(std::integral_constant<int, 16>{});
-  if (f == 32) return fn(std::integral_constant<int, 32>{});
-  if (f == 64) return fn(std::integral_constant<int, 64>{});
-  if (f == 128) return fn(std::integral_constant<int, 128>{});
-  return kErrUnsupported;
-}
-
 // widest head the all-heads-in-one-workgroup backward takes (DFGNN_HEADS2_MAXF in the environment: diagnostic switch)
 static int heads2_max_f() {
   static const int v = [] { const char *e = getenv("DFGNN_HEADS2_MAXF"); return e ? atoi(e) : 16; }();
   return v;
-}
-
-static bool stats_lean_enabled() {
-  static const bool on = [] { const char *e = getenv("DFGNN_LEAN"); return !e || atoi(e) != 0; }();
-  return on;
 }
 
 int launch_gt_dense_fwd_stats(const Csr &g_in, const Plan &p, const float *Q, const float *K, const float *V, float *out,
@@ -143,8 +125,8 @@ int launch_gt_dense_fwd_stats(const Csr &g_in, const Plan &p, const float *Q, co
   if (g.wdense) return launch_gt_dense_fwd_stats_w(g, p, Q, K, V, out, stat_max, stat_sum, s);  // edge values
   const dim3 grid(p.num_dense, 1);
   // a batch without ranges of more than 128 nodes: the 256-thread forward, two workgroups per CU (dfgnn_dense_lean.hpp)
-  const bool lean = (g.f == 64 || g.f == 128) && g.h == 1 && p.num_dense_wide == 0 && stats_lean_enabled();
-  return dispatch_dense_stats(g.f, [&](auto fc) {
+  const bool lean = dense_lean_batch(g, p);
+  return dispatch_dense(g.f, [&](auto fc) {
     constexpr int F = decltype(fc)::value;
     if constexpr (F == 64 || F == 128) {
       if (lean) {
@@ -172,7 +154,7 @@ int launch_gt_dense_bwd_stats(const Csr &g_in, const Plan &p, const float *Q, co
   // multi-head: every head of a range of <= 160 nodes in one workgroup (dense_bwd_heads2_body) for heads of at most
   // kHeads2MaxF features; wider heads run per (range, head) on the single-head bodies
   const int heads2 = (g.h > 1 && dense_heads_ok(g.f, g.h) && g.f <= heads2_max_f()) ? 1 : 0;
-  return dispatch_dense_stats(g.f, [&](auto fc) {
+  return dispatch_dense(g.f, [&](auto fc) {
     constexpr int F = decltype(fc)::value;
     if (int rc = set_max_lds_cached(gt_dense_bwd_stats_kernel<F>)) return rc;
     gt_dense_bwd_stats_kernel<F><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.fit(), Q, K, V, stat_max, stat_sum, grad_out, dQ, dK,

@@ -16,9 +16,6 @@
 
 #include "dfgnn_dense.hpp"
 #include "dfgnn_dense_stamp.hpp"
-#ifndef DFGNN_RING160
-#define DFGNN_RING160 2
-#endif
 #include "dfgnn_dense_wide.hpp"
 #include "dfgnn_dense_lean.hpp"
 #include "dfgnn_dense_heads.hpp"
@@ -137,21 +134,11 @@ __global__ __launch_bounds__(kDenseThreads) void gt_dense_fwd_ranked_heads_kerne
     dense_fwd_body<F, true, 2, kDenseChunkRows, 2, false, true, true>(lds, lds_bytes, g, n0, n, e0, ne, 0, g.h, Q, K, V, attn_ranked, out);
 }
 
-template <class Fn>
-static int dispatch_dense_w(int f, Fn &&fn) {
-  if (f == 8) return fn(std::integral_constant<int, 8>{});  // f = 8 / 16: zero-padded onto the 32-wide layout
-  if (f == 16) return fn(std::integral_constant<int, 16>{});
-  if (f == 32) return fn(std::integral_constant<int, 32>{});
-  if (f == 64) return fn(std::integral_constant<int, 64>{});
-  if (f == 128) return fn(std::integral_constant<int, 128>{});
-  return kErrUnsupported;
-}
-
 // g.wdense, g.mask, g.maskT set by the caller (launch_gt_dense_fwd_stats / launch_gt_dense_bwd_stats)
 int launch_gt_dense_fwd_stats_w(const Csr &g, const Plan &p, const float *Q, const float *K, const float *V, float *out,
                                 float *stat_max, float *stat_sum, hipStream_t s) {
   const dim3 grid(p.num_dense, g.h);
-  return dispatch_dense_w(g.f, [&](auto fc) {
+  return dispatch_dense(g.f, [&](auto fc) {
     constexpr int F = decltype(fc)::value;
     if (int rc = set_max_lds_cached(gt_dense_fwd_stats_w_kernel<F>)) return rc;
     gt_dense_fwd_stats_w_kernel<F><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.fit(), Q, K, V, out, stat_max, stat_sum, kLdsBytes);
@@ -163,18 +150,13 @@ int launch_gt_dense_bwd_stats_w(const Csr &g, const Plan &p, const float *Q, con
                                 const float *stat_max, const float *stat_sum, const float *grad_out, float *dQ, float *dK,
                                 float *dV, hipStream_t s) {
   const dim3 grid(p.num_dense, g.h);
-  return dispatch_dense_w(g.f, [&](auto fc) {
+  return dispatch_dense(g.f, [&](auto fc) {
     constexpr int F = decltype(fc)::value;
     if (int rc = set_max_lds_cached(gt_dense_bwd_stats_w_kernel<F>)) return rc;
     gt_dense_bwd_stats_w_kernel<F><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.fit(), Q, K, V, stat_max, stat_sum, grad_out, dQ,
                                                                           dK, dV, g.h == 1 ? bwd_reverse_keep(p.num_dense) : -1);  // (several heads: measured, no gain)
     return launch_status();
   });
-}
-
-static bool ranked_lean_enabled() {  // DFGNN_LEAN=0 (diagnostic switch, read once): every dense range on the 512-thread forward
-  static const bool on = [] { const char *e = getenv("DFGNN_LEAN"); return !e || atoi(e) != 0; }();
-  return on;
 }
 
 int launch_gt_dense_fwd_ranked(const Csr &g_in, const Plan &p, const float *Q, const float *K, const float *V,
@@ -184,8 +166,8 @@ int launch_gt_dense_fwd_ranked(const Csr &g_in, const Plan &p, const float *Q, c
   g.mask = p.mask();
   const dim3 grid(p.num_dense, 1);
   // a one-head batch without ranges of more than 128 nodes: the 256-thread forward, two workgroups per CU
-  const bool lean = (g.f == 64 || g.f == 128) && g.h == 1 && p.num_dense_wide == 0 && ranked_lean_enabled();
-  return dispatch_dense_w(g.f, [&](auto fc) {
+  const bool lean = dense_lean_batch(g, p);
+  return dispatch_dense(g.f, [&](auto fc) {
     constexpr int F = decltype(fc)::value;
     if constexpr (F == 64 || F == 128) {
       if (lean) {

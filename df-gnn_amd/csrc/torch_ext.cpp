@@ -49,8 +49,8 @@ inline void check_edges(const Tensor &t, int64_t nnz, const char *name) {
 }
 inline void check_same_device(const Tensor &ref, std::initializer_list<const Tensor *> ts) {
   for (const Tensor *t : ts)
-    TORCH_CHECK(!t->defined() || t->device() == ref.device(), "every tensor must live on one device (", ref.device(), "), got ",
-                t->device(), ": a pointer of another GPU would be handed to a kernel of this one");
+    TORCH_CHECK(!t || !t->defined() || t->device() == ref.device(), "every tensor must live on one device (", ref.device(),
+                "), got ", t->device(), ": a pointer of another GPU would be handed to a kernel of this one");
 }
 inline void check_rc(int rc, const char *what) {
   TORCH_CHECK(rc == 0, what, " failed: ", dfgnn_error_string(rc), " (code ", rc, ")");
@@ -59,16 +59,22 @@ inline dfgnn_stream_t cur_stream() {  // torch's current stream of the (guarded)
   return reinterpret_cast<dfgnn_stream_t>(c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream());
 }
 inline const int *plan_ptr(int64_t p) { return reinterpret_cast<const int *>(static_cast<intptr_t>(p)); }
+// typed device pointers for the C ABI; an undefined tensor / an empty optional is NULL
+inline int *i32(const Tensor &t) { return t.defined() ? t.data_ptr<int>() : nullptr; }
+inline float *f32(const Tensor &t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
+inline int *i32(const c10::optional<Tensor> &t) { return t ? t->data_ptr<int>() : nullptr; }
+inline float *f32(const c10::optional<Tensor> &t) { return t ? t->data_ptr<float>() : nullptr; }
+inline const Tensor *opt(const c10::optional<Tensor> &t) { return t ? &*t : nullptr; }
 
-struct GtDims {
+struct Dims {
   int m, nnz, h, f;
 };
-GtDims gt_checks(const Tensor &row_ptr, const Tensor &col_ind, const Tensor &rows, const Tensor &val, const Tensor &Q,
-                 const Tensor &K, const Tensor &V) {
+// What every GT entry point checks: the CSR arrays + Q / K / V, and -- where the entry point takes them, else nullptr --
+// the COO rows and the edge values
+Dims gt_checks(const Tensor &row_ptr, const Tensor &col_ind, const Tensor *rows, const Tensor *val, const Tensor &Q,
+               const Tensor &K, const Tensor &V) {
   check_i32(row_ptr, "row_ptr");
   check_i32(col_ind, "col_ind");
-  check_i32(rows, "rows");
-  check_f32(val, "val");
   check_feat3(Q, Q, "Q");
   check_feat3(K, Q, "K");
   check_feat3(V, Q, "V");
@@ -76,27 +82,56 @@ GtDims gt_checks(const Tensor &row_ptr, const Tensor &col_ind, const Tensor &row
   TORCH_CHECK(row_ptr.size(0) - 1 == Q.size(0), "indptr describes ", row_ptr.size(0) - 1, " rows but features have ", Q.size(0),
               " nodes");
   const int64_t nnz = col_ind.size(0);
-  check_edges(rows, nnz, "rows");
-  check_edges(val, nnz, "val");
-  check_same_device(Q, {&row_ptr, &col_ind, &rows, &val, &K, &V});
-  return GtDims{(int)Q.size(0), (int)nnz, (int)Q.size(1), (int)Q.size(2)};
+  if (rows) {
+    check_i32(*rows, "rows");
+    check_edges(*rows, nnz, "rows");
+  }
+  if (val) {
+    check_f32(*val, "val");
+    check_edges(*val, nnz, "val");
+  }
+  check_same_device(Q, {&row_ptr, &col_ind, rows, val, &K, &V});
+  return Dims{(int)Q.size(0), (int)nnz, (int)Q.size(1), (int)Q.size(2)};
+}
+// ... of a backward: the CSC arrays next to the CSR structure,
+void csc_checks(const Dims &d, const Tensor &ref, const Tensor &col_ptr, const Tensor &row_ind, const Tensor &val_idx) {
+  check_i32(col_ptr, "col_ptr");
+  check_i32(row_ind, "row_ind");
+  check_i32(val_idx, "val_idx");
+  check_edges(row_ind, d.nnz, "row_ind");
+  check_edges(val_idx, d.nnz, "val_idx");
+  TORCH_CHECK(col_ptr.dim() == 1 && col_ptr.size(0) == d.m + 1, "col_ptr must have shape (", d.m + 1,
+              ",): the adjacency must be square");
+  check_same_device(ref, {&col_ptr, &row_ind, &val_idx});
+}
+// ... the row statistics [m, h] of a forward,
+void row_stats_checks(const Dims &d, const Tensor &ref, const Tensor &row_max, const Tensor &row_sum) {
+  check_f32(row_max, "row_max");
+  check_f32(row_sum, "row_sum");
+  for (const Tensor *t : {&row_max, &row_sum})
+    TORCH_CHECK(t->dim() == 2 && t->size(0) == d.m && t->size(1) == d.h, "row_max / row_sum must have shape (", d.m, ", ", d.h,
+                "), got ", t->sizes());
+  check_same_device(ref, {&row_max, &row_sum});
+}
+// ... and attention values [h, nnz] in either order
+void attn_checks(const Dims &d, const Tensor &ref, const Tensor &attn, const char *name) {
+  check_f32(attn, name);
+  TORCH_CHECK(attn.numel() == (int64_t)d.h * d.nnz, name, " must have ", d.h, "*", d.nnz, " elements, got ", attn.numel());
+  check_same_device(ref, {&attn});
 }
 
 // fused_gtconv.cpp:278-314 (want_attn = false) and :79-116 (want_attn = true)
 std::vector<Tensor> gt_hyper_fwd(const Tensor &row_ptr, const Tensor &col_ind, const Tensor &rows, const Tensor &val,
                                  const Tensor &Q, const Tensor &K, const Tensor &V, bool want_attn, bool unit_val,
                                  int64_t plan, int64_t meta) {
-  const GtDims d = gt_checks(row_ptr, col_ind, rows, val, Q, K, V);
+  const Dims d = gt_checks(row_ptr, col_ind, &rows, &val, Q, K, V);
   c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
   Tensor out = torch::empty_like(Q);
   Tensor attn, ws;
   if (want_attn) attn = torch::empty({d.h, d.nnz}, Q.options());
   else if (plan) ws = torch::empty({d.h, d.nnz}, Q.options());  // per-edge scratch of the inference call (include/dfgnn.h)
-  check_rc(dfgnn_gt_hyper_fwd(d.m, d.nnz, d.h, d.f, row_ptr.data_ptr<int>(), col_ind.data_ptr<int>(), rows.data_ptr<int>(),
-                              unit_val ? nullptr : val.data_ptr<float>(), Q.data_ptr<float>(), K.data_ptr<float>(),
-                              V.data_ptr<float>(), want_attn ? attn.data_ptr<float>() : nullptr,
-                              ws.defined() ? ws.data_ptr<float>() : nullptr, out.data_ptr<float>(), plan_ptr(plan),
-                              plan_ptr(meta), cur_stream()),
+  check_rc(dfgnn_gt_hyper_fwd(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), i32(rows), unit_val ? nullptr : f32(val), f32(Q),
+                              f32(K), f32(V), f32(attn), f32(ws), f32(out), plan_ptr(plan), plan_ptr(meta), cur_stream()),
            want_attn ? "gt_hyper_forward" : "gt_hyper_inference");
   if (want_attn) return {out, attn};
   return {out};
@@ -107,47 +142,22 @@ std::vector<Tensor> gt_bwd(const Tensor &row_ptr, const Tensor &col_ind, const T
                            const Tensor &col_ptr, const Tensor &row_ind, const Tensor &val_idx, const Tensor &Q,
                            const Tensor &K, const Tensor &V, const Tensor &attn_edge, const Tensor &grad, bool unit_val,
                            int64_t plan, int64_t meta) {
-  const GtDims d = gt_checks(row_ptr, col_ind, rows, val, Q, K, V);
-  check_i32(col_ptr, "col_ptr");
-  check_i32(row_ind, "row_ind");
-  check_i32(val_idx, "val_idx");
-  check_f32(attn_edge, "attn_edge");
+  const Dims d = gt_checks(row_ptr, col_ind, &rows, &val, Q, K, V);
+  csc_checks(d, Q, col_ptr, row_ind, val_idx);
+  attn_checks(d, Q, attn_edge, "attn_edge");
   check_feat3(grad, Q, "grad");
-  check_edges(row_ind, d.nnz, "row_ind");
-  check_edges(val_idx, d.nnz, "val_idx");
-  TORCH_CHECK(col_ptr.dim() == 1 && col_ptr.size(0) == d.m + 1, "col_ptr must have shape (", d.m + 1,
-              ",): the adjacency must be square");
-  TORCH_CHECK(attn_edge.numel() == (int64_t)d.h * d.nnz, "attn_edge must have ", d.h, "*", d.nnz, " elements, got ",
-              attn_edge.numel());
-  check_same_device(Q, {&col_ptr, &row_ind, &val_idx, &attn_edge, &grad});
+  check_same_device(Q, {&grad});
   c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
   Tensor grad_edge = torch::empty({d.h, d.nnz}, Q.options());
   Tensor dQ = torch::empty_like(Q), dK = torch::empty_like(K), dV = torch::empty_like(V);
-  check_rc(dfgnn_gt_bwd(d.m, d.nnz, d.h, d.f, row_ptr.data_ptr<int>(), col_ind.data_ptr<int>(), rows.data_ptr<int>(),
-                        unit_val ? nullptr : val.data_ptr<float>(), col_ptr.data_ptr<int>(), row_ind.data_ptr<int>(),
-                        val_idx.data_ptr<int>(), Q.data_ptr<float>(), K.data_ptr<float>(), V.data_ptr<float>(),
-                        attn_edge.data_ptr<float>(), grad.data_ptr<float>(), grad_edge.data_ptr<float>(),
-                        dQ.data_ptr<float>(), dK.data_ptr<float>(), dV.data_ptr<float>(), plan_ptr(plan), plan_ptr(meta),
-                        cur_stream()),
+  check_rc(dfgnn_gt_bwd(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), i32(rows), unit_val ? nullptr : f32(val), i32(col_ptr),
+                        i32(row_ind), i32(val_idx), f32(Q), f32(K), f32(V), f32(attn_edge), f32(grad), f32(grad_edge), f32(dQ),
+                        f32(dK), f32(dV), plan_ptr(plan), plan_ptr(meta), cur_stream()),
            "gt_backward");
   return {dQ, dK, dV};
 }
 
 // ---- the statistics-saving training pair (include/dfgnn.h: dfgnn_gt_hyper_fwd_stats / dfgnn_gt_bwd_stats) ---------------
-GtDims gt_stats_checks(const Tensor &row_ptr, const Tensor &col_ind, const Tensor &Q, const Tensor &K, const Tensor &V) {
-  check_i32(row_ptr, "row_ptr");
-  check_i32(col_ind, "col_ind");
-  check_feat3(Q, Q, "Q");
-  check_feat3(K, Q, "K");
-  check_feat3(V, Q, "V");
-  TORCH_CHECK(row_ptr.dim() == 1 && col_ind.dim() == 1, "indptr / indices must be 1-D");
-  TORCH_CHECK(row_ptr.size(0) - 1 == Q.size(0), "indptr describes ", row_ptr.size(0) - 1, " rows but features have ", Q.size(0),
-              " nodes");
-  for (const Tensor *t : {&row_ptr, &col_ind, &K, &V})
-    TORCH_CHECK(t->device() == Q.device(), "every tensor must live on the device of Q (", Q.device(), "), got ", t->device());
-  return GtDims{(int)Q.size(0), (int)col_ind.size(0), (int)Q.size(1), (int)Q.size(2)};
-}
-
 // weights: the plan's dense edge values (plan_dense_weights below), or nothing for unit values
 const float *weights_ptr(const c10::optional<Tensor> &weights, const Tensor &Q, int m) {
   if (!weights.has_value()) return nullptr;
@@ -155,15 +165,15 @@ const float *weights_ptr(const c10::optional<Tensor> &weights, const Tensor &Q, 
   check_f32(w, "weights");
   TORCH_CHECK(w.numel() == (int64_t)dfgnn_plan_dense_weights_floats(m), "weights must hold ", dfgnn_plan_dense_weights_floats(m),
               " floats (dfgnn_plan_dense_weights), got ", w.numel());
-  TORCH_CHECK(w.device() == Q.device(), "weights must live on the device of Q");
-  return w.data_ptr<float>();
+  check_same_device(Q, {&w});
+  return f32(w);
 }
 
 // save_stats = false: inference (nothing but `out` is produced; edge values on the matrix cores)
 std::vector<Tensor> gt_hyper_fwd_stats(const Tensor &row_ptr, const Tensor &col_ind, const Tensor &Q, const Tensor &K,
                                        const Tensor &V, int64_t plan, int64_t meta, const c10::optional<Tensor> &weights,
                                        bool save_stats) {
-  const GtDims d = gt_stats_checks(row_ptr, col_ind, Q, K, V);
+  const Dims d = gt_checks(row_ptr, col_ind, nullptr, nullptr, Q, K, V);
   const float *w = weights_ptr(weights, Q, d.m);
   c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
   Tensor out = torch::empty_like(Q);
@@ -172,10 +182,8 @@ std::vector<Tensor> gt_hyper_fwd_stats(const Tensor &row_ptr, const Tensor &col_
     row_max = torch::empty({d.m, d.h}, Q.options());
     row_sum = torch::empty({d.m, d.h}, Q.options());
   }
-  check_rc(dfgnn_gt_hyper_fwd_stats(d.m, d.nnz, d.h, d.f, row_ptr.data_ptr<int>(), col_ind.data_ptr<int>(), w, Q.data_ptr<float>(),
-                                    K.data_ptr<float>(), V.data_ptr<float>(), save_stats ? row_max.data_ptr<float>() : nullptr,
-                                    save_stats ? row_sum.data_ptr<float>() : nullptr, out.data_ptr<float>(), plan_ptr(plan),
-                                    plan_ptr(meta), cur_stream()),
+  check_rc(dfgnn_gt_hyper_fwd_stats(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), w, f32(Q), f32(K), f32(V), f32(row_max),
+                                    f32(row_sum), f32(out), plan_ptr(plan), plan_ptr(meta), cur_stream()),
            "gt_hyper_forward_stats");
   if (!save_stats) return {out};
   return {out, row_max, row_sum};
@@ -184,53 +192,31 @@ std::vector<Tensor> gt_hyper_fwd_stats(const Tensor &row_ptr, const Tensor &col_
 std::vector<Tensor> gt_bwd_stats(const Tensor &row_ptr, const Tensor &col_ind, const Tensor &Q, const Tensor &K,
                                  const Tensor &V, const Tensor &row_max, const Tensor &row_sum, const Tensor &grad,
                                  int64_t plan, int64_t meta, const c10::optional<Tensor> &weights) {
-  const GtDims d = gt_stats_checks(row_ptr, col_ind, Q, K, V);
+  const Dims d = gt_checks(row_ptr, col_ind, nullptr, nullptr, Q, K, V);
   const float *w = weights_ptr(weights, Q, d.m);
   check_feat3(grad, Q, "grad");
-  check_f32(row_max, "row_max");
-  check_f32(row_sum, "row_sum");
-  for (const Tensor *t : {&row_max, &row_sum}) {
-    TORCH_CHECK(t->dim() == 2 && t->size(0) == d.m && t->size(1) == d.h, "row_max / row_sum must have shape (", d.m, ", ", d.h,
-                "), got ", t->sizes());
-    TORCH_CHECK(t->device() == Q.device(), "row statistics must live on the device of Q");
-  }
-  TORCH_CHECK(grad.device() == Q.device(), "grad must live on the device of Q");
+  row_stats_checks(d, Q, row_max, row_sum);
+  check_same_device(Q, {&grad});
   c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
   Tensor dQ = torch::empty_like(Q), dK = torch::empty_like(K), dV = torch::empty_like(V);
-  check_rc(dfgnn_gt_bwd_stats(d.m, d.nnz, d.h, d.f, row_ptr.data_ptr<int>(), col_ind.data_ptr<int>(), w, Q.data_ptr<float>(),
-                              K.data_ptr<float>(), V.data_ptr<float>(), row_max.data_ptr<float>(), row_sum.data_ptr<float>(),
-                              grad.data_ptr<float>(), dQ.data_ptr<float>(), dK.data_ptr<float>(), dV.data_ptr<float>(),
-                              plan_ptr(plan), plan_ptr(meta), cur_stream()),
+  check_rc(dfgnn_gt_bwd_stats(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), w, f32(Q), f32(K), f32(V), f32(row_max),
+                              f32(row_sum), f32(grad), f32(dQ), f32(dK), f32(dV), plan_ptr(plan), plan_ptr(meta), cur_stream()),
            "gt_backward_stats");
   return {dQ, dK, dV};
 }
 
 // ---- the general statistics pair (include/dfgnn.h: dfgnn_gt_fwd_rowstats / dfgnn_gt_bwd_rowstats): any graph, no plan ----
 // val: edge values in CSR order, or nothing (unit values)
-GtDims gt_rowstats_checks(const Tensor &row_ptr, const Tensor &col_ind, const c10::optional<Tensor> &val, const Tensor &Q,
-                          const Tensor &K, const Tensor &V) {
-  const GtDims d = gt_stats_checks(row_ptr, col_ind, Q, K, V);
-  if (val.has_value()) {
-    check_f32(*val, "val");
-    check_edges(*val, d.nnz, "val");
-    check_same_device(Q, {&*val});
-  }
-  return d;
-}
-inline const float *edge_val_ptr(const c10::optional<Tensor> &val, bool unit_val) {
-  return (unit_val || !val.has_value()) ? nullptr : val->data_ptr<float>();
-}
+inline const float *edge_val_ptr(const c10::optional<Tensor> &val, bool unit_val) { return unit_val ? nullptr : f32(val); }
 
 std::vector<Tensor> gt_fwd_rowstats(const Tensor &row_ptr, const Tensor &col_ind, const c10::optional<Tensor> &val, const Tensor &Q,
                                     const Tensor &K, const Tensor &V, bool unit_val) {
-  const GtDims d = gt_rowstats_checks(row_ptr, col_ind, val, Q, K, V);
+  const Dims d = gt_checks(row_ptr, col_ind, nullptr, opt(val), Q, K, V);
   c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
   Tensor out = torch::empty_like(Q);
   Tensor row_max = torch::empty({d.m, d.h}, Q.options()), row_sum = torch::empty({d.m, d.h}, Q.options());
-  check_rc(dfgnn_gt_fwd_rowstats(d.m, d.nnz, d.h, d.f, row_ptr.data_ptr<int>(), col_ind.data_ptr<int>(),
-                                 edge_val_ptr(val, unit_val), Q.data_ptr<float>(), K.data_ptr<float>(),
-                                 V.data_ptr<float>(), row_max.data_ptr<float>(), row_sum.data_ptr<float>(),
-                                 out.data_ptr<float>(), cur_stream()),
+  check_rc(dfgnn_gt_fwd_rowstats(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), edge_val_ptr(val, unit_val), f32(Q), f32(K),
+                                 f32(V), f32(row_max), f32(row_sum), f32(out), cur_stream()),
            "gt_forward_rowstats");
   return {out, row_max, row_sum};
 }
@@ -239,31 +225,18 @@ std::vector<Tensor> gt_bwd_rowstats(const Tensor &row_ptr, const Tensor &col_ind
                                     const Tensor &row_ind, const Tensor &val_idx, const Tensor &Q, const Tensor &K,
                                     const Tensor &V, const Tensor &out, const Tensor &row_max, const Tensor &row_sum,
                                     const Tensor &grad, bool unit_val) {
-  const GtDims d = gt_rowstats_checks(row_ptr, col_ind, val, Q, K, V);
-  check_i32(col_ptr, "col_ptr");
-  check_i32(row_ind, "row_ind");
-  check_i32(val_idx, "val_idx");
-  check_edges(row_ind, d.nnz, "row_ind");
-  check_edges(val_idx, d.nnz, "val_idx");
-  TORCH_CHECK(col_ptr.dim() == 1 && col_ptr.size(0) == d.m + 1, "col_ptr must have shape (", d.m + 1,
-              ",): the adjacency must be square");
+  const Dims d = gt_checks(row_ptr, col_ind, nullptr, opt(val), Q, K, V);
+  csc_checks(d, Q, col_ptr, row_ind, val_idx);
   check_feat3(out, Q, "out");
   check_feat3(grad, Q, "grad");
-  check_f32(row_max, "row_max");
-  check_f32(row_sum, "row_sum");
-  for (const Tensor *t : {&row_max, &row_sum})
-    TORCH_CHECK(t->dim() == 2 && t->size(0) == d.m && t->size(1) == d.h, "row_max / row_sum must have shape (", d.m, ", ", d.h,
-                "), got ", t->sizes());
-  check_same_device(Q, {&col_ptr, &row_ind, &val_idx, &out, &row_max, &row_sum, &grad});
+  row_stats_checks(d, Q, row_max, row_sum);
+  check_same_device(Q, {&out, &grad});
   c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
   Tensor delta = torch::empty({d.m, d.h}, Q.options());
   Tensor dQ = torch::empty_like(Q), dK = torch::empty_like(K), dV = torch::empty_like(V);
-  check_rc(dfgnn_gt_bwd_rowstats(d.m, d.nnz, d.h, d.f, row_ptr.data_ptr<int>(), col_ind.data_ptr<int>(),
-                                 edge_val_ptr(val, unit_val), col_ptr.data_ptr<int>(), row_ind.data_ptr<int>(),
-                                 val_idx.data_ptr<int>(), Q.data_ptr<float>(), K.data_ptr<float>(), V.data_ptr<float>(),
-                                 out.data_ptr<float>(), row_max.data_ptr<float>(), row_sum.data_ptr<float>(),
-                                 grad.data_ptr<float>(), delta.data_ptr<float>(), dQ.data_ptr<float>(), dK.data_ptr<float>(),
-                                 dV.data_ptr<float>(), cur_stream()),
+  check_rc(dfgnn_gt_bwd_rowstats(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), edge_val_ptr(val, unit_val), i32(col_ptr),
+                                 i32(row_ind), i32(val_idx), f32(Q), f32(K), f32(V), f32(out), f32(row_max), f32(row_sum),
+                                 f32(grad), f32(delta), f32(dQ), f32(dK), f32(dV), cur_stream()),
            "gt_backward_rowstats");
   return {dQ, dK, dV};
 }
@@ -271,30 +244,26 @@ std::vector<Tensor> gt_bwd_rowstats(const Tensor &row_ptr, const Tensor &col_ind
 // ---- the attn_edge pair in rank order (include/dfgnn.h: dfgnn_gt_hyper_fwd_ranked / dfgnn_gt_bwd_ranked) ----------------
 std::vector<Tensor> gt_hyper_fwd_ranked(const Tensor &row_ptr, const Tensor &col_ind, const Tensor &Q, const Tensor &K,
                                         const Tensor &V, int64_t plan, int64_t meta) {
-  const GtDims d = gt_stats_checks(row_ptr, col_ind, Q, K, V);
+  const Dims d = gt_checks(row_ptr, col_ind, nullptr, nullptr, Q, K, V);
   c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
   Tensor out = torch::empty_like(Q);
   Tensor attn = torch::empty({d.h, d.nnz}, Q.options());
-  check_rc(dfgnn_gt_hyper_fwd_ranked(d.m, d.nnz, d.h, d.f, row_ptr.data_ptr<int>(), col_ind.data_ptr<int>(), Q.data_ptr<float>(),
-                                     K.data_ptr<float>(), V.data_ptr<float>(), attn.data_ptr<float>(), out.data_ptr<float>(),
-                                     plan_ptr(plan), plan_ptr(meta), cur_stream()),
+  check_rc(dfgnn_gt_hyper_fwd_ranked(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), f32(Q), f32(K), f32(V), f32(attn),
+                                     f32(out), plan_ptr(plan), plan_ptr(meta), cur_stream()),
            "gt_hyper_forward_ranked");
   return {out, attn};
 }
 
 std::vector<Tensor> gt_bwd_ranked(const Tensor &row_ptr, const Tensor &col_ind, const Tensor &Q, const Tensor &K,
                                   const Tensor &V, const Tensor &attn, const Tensor &grad, int64_t plan, int64_t meta) {
-  const GtDims d = gt_stats_checks(row_ptr, col_ind, Q, K, V);
+  const Dims d = gt_checks(row_ptr, col_ind, nullptr, nullptr, Q, K, V);
   check_feat3(grad, Q, "grad");
-  check_f32(attn, "attn_ranked");
-  TORCH_CHECK(attn.numel() == (int64_t)d.h * d.nnz, "attn_ranked must have ", d.h, "*", d.nnz, " elements, got ", attn.numel());
-  TORCH_CHECK(attn.device() == Q.device() && grad.device() == Q.device(), "attn_ranked / grad must live on the device of Q");
+  attn_checks(d, Q, attn, "attn_ranked");
+  check_same_device(Q, {&grad});
   c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
   Tensor dQ = torch::empty_like(Q), dK = torch::empty_like(K), dV = torch::empty_like(V);
-  check_rc(dfgnn_gt_bwd_ranked(d.m, d.nnz, d.h, d.f, row_ptr.data_ptr<int>(), col_ind.data_ptr<int>(), Q.data_ptr<float>(),
-                               K.data_ptr<float>(), V.data_ptr<float>(), attn.data_ptr<float>(), grad.data_ptr<float>(),
-                               dQ.data_ptr<float>(), dK.data_ptr<float>(), dV.data_ptr<float>(), plan_ptr(plan), plan_ptr(meta),
-                               cur_stream()),
+  check_rc(dfgnn_gt_bwd_ranked(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), f32(Q), f32(K), f32(V), f32(attn), f32(grad),
+                               f32(dQ), f32(dK), f32(dV), plan_ptr(plan), plan_ptr(meta), cur_stream()),
            "gt_backward_ranked");
   return {dQ, dK, dV};
 }
@@ -304,21 +273,18 @@ Tensor plan_dense_weights(const Tensor &row_ptr, const Tensor &val, int64_t plan
   check_i32(row_ptr, "row_ptr");
   check_f32(val, "val");
   TORCH_CHECK(row_ptr.dim() == 1 && row_ptr.size(0) >= 1, "indptr must be 1-D");
-  TORCH_CHECK(val.device() == row_ptr.device(), "val must live on the device of indptr");
+  check_same_device(row_ptr, {&val});
   const int m = (int)row_ptr.size(0) - 1, nnz = (int)val.numel();
   c10::hip::HIPGuardMasqueradingAsCUDA guard(row_ptr.device());
   Tensor w = torch::empty({(int64_t)dfgnn_plan_dense_weights_floats(m)}, val.options());
-  check_rc(dfgnn_plan_dense_weights(m, nnz, row_ptr.data_ptr<int>(), val.data_ptr<float>(), plan_ptr(plan), plan_ptr(meta),
-                                    w.data_ptr<float>(), cur_stream()),
+  check_rc(dfgnn_plan_dense_weights(m, nnz, i32(row_ptr), f32(val), plan_ptr(plan), plan_ptr(meta), f32(w), cur_stream()),
            "plan_dense_weights");
   return w;
 }
 
-struct GatDims {
-  int m, nnz, h, f;
-};
-GatDims gat_checks(const Tensor &attn_row, const Tensor &attn_col, const Tensor &indptr, const Tensor &indices,
-                   const Tensor *rows, const Tensor &in_feat) {
+// What every GAT entry point checks: in_feat, the CSR arrays, the per-node scores [m, h] and (or nullptr) the COO rows
+Dims gat_checks(const Tensor &attn_row, const Tensor &attn_col, const Tensor &indptr, const Tensor &indices,
+                const Tensor *rows, const Tensor &in_feat) {
   check_f32(attn_row, "attn_row");
   check_f32(attn_col, "attn_col");
   check_f32(in_feat, "in_feat");
@@ -334,23 +300,29 @@ GatDims gat_checks(const Tensor &attn_row, const Tensor &attn_col, const Tensor 
   if (rows) {
     check_i32(*rows, "rows");
     check_edges(*rows, nnz, "rows");
-    check_same_device(in_feat, {rows});
   }
-  check_same_device(in_feat, {&attn_row, &attn_col, &indptr, &indices});
-  return GatDims{(int)m, (int)nnz, (int)in_feat.size(1), (int)in_feat.size(2)};
+  check_same_device(in_feat, {&attn_row, &attn_col, &indptr, &indices, rows});
+  return Dims{(int)m, (int)nnz, (int)in_feat.size(1), (int)in_feat.size(2)};
+}
+// ... of the training pair: the dropout rate and its randoms [nnz, h] (nothing: no dropout)
+void drop_checks(const Dims &d, const Tensor &ref, double attn_drop, const c10::optional<Tensor> &edge_mask) {
+  TORCH_CHECK(attn_drop >= 0.0 && attn_drop < 1.0, "attn_drop must be in [0, 1), got ", attn_drop);
+  if (!edge_mask) return;
+  check_f32(*edge_mask, "edge_mask");
+  TORCH_CHECK(edge_mask->dim() == 2 && edge_mask->size(0) == d.nnz && edge_mask->size(1) == d.h, "edge_mask must have shape (",
+              d.nnz, ", ", d.h, "), got ", edge_mask->sizes());
+  check_same_device(ref, {&*edge_mask});
 }
 
 // fused_gatconv.cpp:99-119
 Tensor gat_hyper_fwd(const Tensor &attn_row, const Tensor &attn_col, const Tensor &indptr, const Tensor &indices,
                      const Tensor &rows, double slope, const Tensor &in_feat, int64_t plan, int64_t meta, bool need_ws) {
-  const GatDims d = gat_checks(attn_row, attn_col, indptr, indices, &rows, in_feat);
+  const Dims d = gat_checks(attn_row, attn_col, indptr, indices, &rows, in_feat);
   c10::hip::HIPGuardMasqueradingAsCUDA guard(in_feat.device());
   Tensor out = torch::empty_like(in_feat), ws;
   if (need_ws) ws = torch::empty({d.h, d.nnz}, in_feat.options());
-  check_rc(dfgnn_gat_hyper_fwd(d.m, d.nnz, d.h, d.f, indptr.data_ptr<int>(), indices.data_ptr<int>(), rows.data_ptr<int>(),
-                               attn_row.data_ptr<float>(), attn_col.data_ptr<float>(), (float)slope,
-                               in_feat.data_ptr<float>(), ws.defined() ? ws.data_ptr<float>() : nullptr,
-                               out.data_ptr<float>(), plan_ptr(plan), plan_ptr(meta), cur_stream()),
+  check_rc(dfgnn_gat_hyper_fwd(d.m, d.nnz, d.h, d.f, i32(indptr), i32(indices), i32(rows), f32(attn_row), f32(attn_col),
+                               (float)slope, f32(in_feat), f32(ws), f32(out), plan_ptr(plan), plan_ptr(meta), cur_stream()),
            "gat_inference_hyper");
   return out;
 }
@@ -358,14 +330,13 @@ Tensor gat_hyper_fwd(const Tensor &attn_row, const Tensor &attn_col, const Tenso
 // fused_gatconv.cpp:40-61 (use_lds) and :69-90 (global-memory logits)
 Tensor gat_softmax_fwd(const Tensor &attn_row, const Tensor &attn_col, const Tensor &indptr, const Tensor &indices,
                        const Tensor &rows, double slope, const Tensor &in_feat, bool use_lds) {
-  const GatDims d = gat_checks(attn_row, attn_col, indptr, indices, &rows, in_feat);
+  const Dims d = gat_checks(attn_row, attn_col, indptr, indices, &rows, in_feat);
   c10::hip::HIPGuardMasqueradingAsCUDA guard(in_feat.device());
   Tensor out = torch::empty_like(in_feat);
   Tensor logits = torch::empty({d.h, d.nnz}, in_feat.options());
   auto fn = use_lds ? dfgnn_gat_softmax_fwd : dfgnn_gat_softmax_gm_fwd;
-  check_rc(fn(d.m, d.nnz, d.h, d.f, indptr.data_ptr<int>(), indices.data_ptr<int>(), rows.data_ptr<int>(),
-              attn_row.data_ptr<float>(), attn_col.data_ptr<float>(), (float)slope, in_feat.data_ptr<float>(),
-              logits.data_ptr<float>(), out.data_ptr<float>(), cur_stream()),
+  check_rc(fn(d.m, d.nnz, d.h, d.f, i32(indptr), i32(indices), i32(rows), f32(attn_row), f32(attn_col), (float)slope,
+              f32(in_feat), f32(logits), f32(out), cur_stream()),
            use_lds ? "gat_inference_softmax" : "gat_inference_softmax_gm");
   return out;
 }
@@ -373,12 +344,11 @@ Tensor gat_softmax_fwd(const Tensor &attn_row, const Tensor &attn_col, const Ten
 // fused_gatconv.cpp:196-219
 Tensor gat_tiling_fwd(const Tensor &attn_row, const Tensor &attn_col, const Tensor &row_ptr, const Tensor &col_ind,
                       double slope, const Tensor &in_feat) {
-  const GatDims d = gat_checks(attn_row, attn_col, row_ptr, col_ind, nullptr, in_feat);
+  const Dims d = gat_checks(attn_row, attn_col, row_ptr, col_ind, nullptr, in_feat);
   c10::hip::HIPGuardMasqueradingAsCUDA guard(in_feat.device());
   Tensor out = torch::empty_like(in_feat);
-  check_rc(dfgnn_gat_tiling_fwd(d.m, d.nnz, d.h, d.f, row_ptr.data_ptr<int>(), col_ind.data_ptr<int>(),
-                                attn_row.data_ptr<float>(), attn_col.data_ptr<float>(), (float)slope,
-                                in_feat.data_ptr<float>(), out.data_ptr<float>(), cur_stream()),
+  check_rc(dfgnn_gat_tiling_fwd(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), f32(attn_row), f32(attn_col), (float)slope,
+                                f32(in_feat), f32(out), cur_stream()),
            "gat_inference_tiling");
   return out;
 }
@@ -388,22 +358,14 @@ Tensor gat_tiling_fwd(const Tensor &attn_row, const Tensor &attn_col, const Tens
 std::vector<Tensor> gat_fwd_train(const Tensor &attn_row, const Tensor &attn_col, const Tensor &row_ptr, const Tensor &col_ind,
                                   const c10::optional<Tensor> &rows, double slope, const Tensor &in_feat,
                                   const c10::optional<Tensor> &edge_mask, double attn_drop, int64_t plan, int64_t meta) {
-  const GatDims d = gat_checks(attn_row, attn_col, row_ptr, col_ind, rows ? &*rows : nullptr, in_feat);
-  TORCH_CHECK(attn_drop >= 0.0 && attn_drop < 1.0, "attn_drop must be in [0, 1), got ", attn_drop);
-  if (edge_mask) {
-    check_f32(*edge_mask, "edge_mask");
-    TORCH_CHECK(edge_mask->dim() == 2 && edge_mask->size(0) == d.nnz && edge_mask->size(1) == d.h, "edge_mask must have shape (",
-                d.nnz, ", ", d.h, "), got ", edge_mask->sizes());
-    check_same_device(in_feat, {&*edge_mask});
-  }
+  const Dims d = gat_checks(attn_row, attn_col, row_ptr, col_ind, opt(rows), in_feat);
+  drop_checks(d, in_feat, attn_drop, edge_mask);
   c10::hip::HIPGuardMasqueradingAsCUDA guard(in_feat.device());
   Tensor out = torch::empty_like(in_feat);
   Tensor edge_max = torch::empty({d.m, d.h}, in_feat.options()), edge_sum = torch::empty({d.m, d.h}, in_feat.options());
-  check_rc(dfgnn_gat_fwd_train(d.m, d.nnz, d.h, d.f, row_ptr.data_ptr<int>(), col_ind.data_ptr<int>(),
-                               rows ? rows->data_ptr<int>() : nullptr, attn_row.data_ptr<float>(), attn_col.data_ptr<float>(),
-                               (float)slope, in_feat.data_ptr<float>(), edge_mask ? edge_mask->data_ptr<float>() : nullptr,
-                               (float)attn_drop, edge_max.data_ptr<float>(), edge_sum.data_ptr<float>(), out.data_ptr<float>(),
-                               plan_ptr(plan), plan_ptr(meta), cur_stream()),
+  check_rc(dfgnn_gat_fwd_train(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), i32(rows), f32(attn_row), f32(attn_col),
+                               (float)slope, f32(in_feat), f32(edge_mask), (float)attn_drop, f32(edge_max), f32(edge_sum),
+                               f32(out), plan_ptr(plan), plan_ptr(meta), cur_stream()),
            "gat_forward");
   return {out, edge_max, edge_sum};
 }
@@ -414,8 +376,7 @@ std::vector<Tensor> gat_bwd(double slope, double attn_drop, const Tensor &row_pt
                             const Tensor &edge_max, const Tensor &edge_sum, const c10::optional<Tensor> &edge_mask,
                             const Tensor &in_feat, const Tensor &attn_row, const Tensor &attn_col, const Tensor &grad,
                             int64_t plan, int64_t meta) {
-  const GatDims d = gat_checks(attn_row, attn_col, row_ptr, col_ind, rows ? &*rows : nullptr, in_feat);
-  TORCH_CHECK(attn_drop >= 0.0 && attn_drop < 1.0, "attn_drop must be in [0, 1), got ", attn_drop);
+  const Dims d = gat_checks(attn_row, attn_col, row_ptr, col_ind, opt(rows), in_feat);
   check_i32(col_ptr, "col_ptr");
   check_i32(row_ind, "row_ind");
   check_i32(permute, "permute");
@@ -428,23 +389,15 @@ std::vector<Tensor> gat_bwd(double slope, double attn_drop, const Tensor &row_pt
   TORCH_CHECK(col_ptr.size(0) == d.m + 1 && row_ind.size(0) == d.nnz && permute.size(0) == d.nnz,
               "col_ptr / row_ind / permute do not match the CSR structure");
   check_same_device(in_feat, {&col_ptr, &row_ind, &permute, &edge_max, &edge_sum, &grad});
-  if (edge_mask) {
-    check_f32(*edge_mask, "edge_mask");
-    TORCH_CHECK(edge_mask->dim() == 2 && edge_mask->size(0) == d.nnz && edge_mask->size(1) == d.h, "edge_mask must have shape (",
-                d.nnz, ", ", d.h, "), got ", edge_mask->sizes());
-    check_same_device(in_feat, {&*edge_mask});
-  }
+  drop_checks(d, in_feat, attn_drop, edge_mask);
   c10::hip::HIPGuardMasqueradingAsCUDA guard(in_feat.device());
   Tensor grad_feat = torch::empty_like(in_feat);
   Tensor grad_row = torch::empty({d.m, d.h}, in_feat.options()), grad_col = torch::empty({d.m, d.h}, in_feat.options());
   Tensor grad_edge = torch::empty({d.h, d.nnz}, in_feat.options());
-  check_rc(dfgnn_gat_bwd(d.m, d.nnz, d.h, d.f, row_ptr.data_ptr<int>(), col_ind.data_ptr<int>(),
-                         rows ? rows->data_ptr<int>() : nullptr, col_ptr.data_ptr<int>(), row_ind.data_ptr<int>(),
-                         permute.data_ptr<int>(), attn_row.data_ptr<float>(), attn_col.data_ptr<float>(), (float)slope,
-                         in_feat.data_ptr<float>(), edge_max.data_ptr<float>(), edge_sum.data_ptr<float>(),
-                         edge_mask ? edge_mask->data_ptr<float>() : nullptr, (float)attn_drop, grad.data_ptr<float>(),
-                         grad_edge.data_ptr<float>(), grad_feat.data_ptr<float>(), grad_row.data_ptr<float>(),
-                         grad_col.data_ptr<float>(), plan_ptr(plan), plan_ptr(meta), cur_stream()),
+  check_rc(dfgnn_gat_bwd(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), i32(rows), i32(col_ptr), i32(row_ind), i32(permute),
+                         f32(attn_row), f32(attn_col), (float)slope, f32(in_feat), f32(edge_max), f32(edge_sum), f32(edge_mask),
+                         (float)attn_drop, f32(grad), f32(grad_edge), f32(grad_feat), f32(grad_row), f32(grad_col),
+                         plan_ptr(plan), plan_ptr(meta), cur_stream()),
            "gat_backward");
   return {grad_feat, grad_row, grad_col};
 }
@@ -453,40 +406,25 @@ std::vector<Tensor> gat_bwd(double slope, double attn_drop, const Tensor &row_pt
 // take CSR (+ the COO rows for the two-kernel forms).  which: 0 tiling, 1 csr, 2 csr_gm, 3 softmax, 4 softmax_gm
 Tensor gt_variant_fwd(int64_t which, const Tensor &indptr, const Tensor &indices, const c10::optional<Tensor> &rows, const Tensor &val,
                       const Tensor &Q, const Tensor &K, const Tensor &V, bool unit_val) {
-  check_i32(indptr, "indptr");
-  check_i32(indices, "indices");
-  check_f32(val, "val");
-  check_feat3(Q, Q, "Q");
-  check_feat3(K, Q, "K");
-  check_feat3(V, Q, "V");
-  TORCH_CHECK(indptr.dim() == 1 && indices.dim() == 1, "indptr / indices must be 1-D");
-  TORCH_CHECK(indptr.size(0) - 1 == Q.size(0), "indptr describes ", indptr.size(0) - 1, " rows but features have ", Q.size(0), " nodes");
-  const int m = (int)Q.size(0), nnz = (int)indices.size(0), h = (int)Q.size(1), f = (int)Q.size(2);
-  check_edges(val, nnz, "val");
-  check_same_device(Q, {&indptr, &indices, &val, &K, &V});
-  const bool needs_rows = which >= 3;
   TORCH_CHECK(which >= 0 && which <= 4, "unknown GT variant ", which);
-  if (needs_rows) {
-    TORCH_CHECK(rows.has_value(), "rows is required by the softmax variants");
-    check_i32(*rows, "rows");
-    check_edges(*rows, nnz, "rows");
-    check_same_device(Q, {&*rows});
-  }
+  TORCH_CHECK(which < 3 || rows.has_value(), "rows is required by the softmax variants");
+  const Dims d = gt_checks(indptr, indices, which >= 3 ? &*rows : nullptr, &val, Q, K, V);
+  const int m = d.m, nnz = d.nnz, h = d.h, f = d.f;
   c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
   Tensor out = torch::empty_like(Q), logits;
   if (which != 0) logits = torch::empty({h, nnz}, Q.options());
-  const int *ip = indptr.data_ptr<int>(), *ci = indices.data_ptr<int>();
-  const float *q = Q.data_ptr<float>(), *k = K.data_ptr<float>(), *v = V.data_ptr<float>();
-  float *lg = logits.defined() ? logits.data_ptr<float>() : nullptr, *o = out.data_ptr<float>();
+  const int *ip = i32(indptr), *ci = i32(indices);
+  const float *q = f32(Q), *k = f32(K), *v = f32(V);
+  float *lg = f32(logits), *o = f32(out);
   // (the two-kernel 'softmax' forms multiply the values in as they are; the others take NULL for all ones)
-  const float *vl = (which >= 3 || !unit_val) ? val.data_ptr<float>() : nullptr;
+  const float *vl = (which >= 3 || !unit_val) ? f32(val) : nullptr;
   int rc = 0;
   switch (which) {
-    case 0: rc = dfgnn_gt_tiling_fwd(m, nnz, h, f, ip, ci, val.data_ptr<float>(), q, k, v, o, cur_stream()); break;
+    case 0: rc = dfgnn_gt_tiling_fwd(m, nnz, h, f, ip, ci, f32(val), q, k, v, o, cur_stream()); break;
     case 1: rc = dfgnn_gt_csr_fwd(m, nnz, h, f, ip, ci, vl, q, k, v, lg, o, cur_stream()); break;
     case 2: rc = dfgnn_gt_csr_gm_fwd(m, nnz, h, f, ip, ci, vl, q, k, v, lg, o, cur_stream()); break;
-    case 3: rc = dfgnn_gt_softmax_fwd(m, nnz, h, f, ip, ci, rows->data_ptr<int>(), vl, q, k, v, lg, o, cur_stream()); break;
-    default: rc = dfgnn_gt_softmax_gm_fwd(m, nnz, h, f, ip, ci, rows->data_ptr<int>(), vl, q, k, v, lg, o, cur_stream()); break;
+    case 3: rc = dfgnn_gt_softmax_fwd(m, nnz, h, f, ip, ci, i32(rows), vl, q, k, v, lg, o, cur_stream()); break;
+    default: rc = dfgnn_gt_softmax_gm_fwd(m, nnz, h, f, ip, ci, i32(rows), vl, q, k, v, lg, o, cur_stream()); break;
   }
   static const char *names[] = {"gt_tiling_inference", "gt_csr_inference", "gt_csr_gm_inference", "gt_softmax_inference",
                                 "gt_softmax_gm_inference"};
@@ -504,9 +442,7 @@ std::pair<Tensor, std::vector<int64_t>> plan_build(const Tensor &indptr, const T
   c10::hip::HIPGuardMasqueradingAsCUDA guard(indptr.device());
   Tensor buf = torch::empty({(int64_t)dfgnn_plan_ints(m, nnz)}, indptr.options());
   int meta[12];
-  check_rc(dfgnn_plan_build(m, nnz, (int)f, indptr.data_ptr<int>(), indices.data_ptr<int>(), buf.data_ptr<int>(), meta,
-                            cur_stream()),
-           "dfgnn_plan_build");
+  check_rc(dfgnn_plan_build(m, nnz, (int)f, i32(indptr), i32(indices), i32(buf), meta, cur_stream()), "dfgnn_plan_build");
   return {buf, std::vector<int64_t>(meta, meta + 12)};
 }
 
@@ -524,19 +460,15 @@ std::vector<Tensor> preprocess_hyper(const Tensor &src, const Tensor &dst, int64
               "graphs with 2^31 or more nodes / edges are not supported (int32 index arrays)");
   const int m = (int)num_nodes;
   c10::hip::HIPGuardMasqueradingAsCUDA guard(s.device());
-  const auto i32 = s.options().dtype(torch::kInt32);
-  std::vector<Tensor> outs = {torch::empty({m + 1}, i32), torch::empty({nnz}, i32), torch::empty({nnz}, i32), torch::empty({nnz}, i32)};
-  if (csc) {
-    outs.push_back(torch::empty({m + 1}, i32));
-    outs.push_back(torch::empty({nnz}, i32));
-    outs.push_back(torch::empty({nnz}, i32));
-  }
+  const auto i32o = s.options().dtype(torch::kInt32);
+  std::vector<Tensor> outs = {torch::empty({m + 1}, i32o), torch::empty({nnz}, i32o), torch::empty({nnz}, i32o), torch::empty({nnz}, i32o)};
+  if (csc) outs.insert(outs.end(), {torch::empty({m + 1}, i32o), torch::empty({nnz}, i32o), torch::empty({nnz}, i32o)});
   const size_t ws_bytes = dfgnn_preprocess_ws_bytes(m, (int)nnz);
   Tensor ws = torch::empty({(int64_t)ws_bytes}, s.options().dtype(torch::kUInt8));
-  check_rc(dfgnn_preprocess_hyper(m, (int)nnz, s.data_ptr(), t.data_ptr(), s.scalar_type() == torch::kInt64 ? 1 : 0,
-                                  outs[0].data_ptr<int>(), outs[1].data_ptr<int>(), outs[2].data_ptr<int>(), outs[3].data_ptr<int>(),
-                                  csc ? outs[4].data_ptr<int>() : nullptr, csc ? outs[5].data_ptr<int>() : nullptr,
-                                  csc ? outs[6].data_ptr<int>() : nullptr, ws.data_ptr(), ws_bytes, cur_stream()),
+  const Tensor none;
+  check_rc(dfgnn_preprocess_hyper(m, (int)nnz, s.data_ptr(), t.data_ptr(), s.scalar_type() == torch::kInt64 ? 1 : 0, i32(outs[0]),
+                                  i32(outs[1]), i32(outs[2]), i32(outs[3]), i32(csc ? outs[4] : none), i32(csc ? outs[5] : none),
+                                  i32(csc ? outs[6] : none), ws.data_ptr(), ws_bytes, cur_stream()),
            "dfgnn_preprocess_hyper");
   return outs;
 }

@@ -15,36 +15,30 @@ import torch
 import dfgnn_native as _n
 import os
 
-from _binding_util import (as_int32, check_contiguous, check_device, check_dtype, check_feat3, get_plan, get_plan_obj,
-                           plan_dense_weights, ptr,
-                           stream_ptr, val_ptr)
+from _binding_util import (as_int32, call, check_2d, check_csc, check_csr, check_edges, check_family, check_feats,
+                           get_plan_obj, plan_dense_weights, plan_ptrs, val_ptr)
 
 # Set to False to force the general (plan-less) kernels; results are identical either way.
 USE_BLOCK_PLAN = True
 
-
-def _dims(indptr, indices, Q):
-    return indptr.size(0) - 1, indices.size(0), Q.size(1), Q.size(2)
-
-
-def _check_graph(indptr, indices, m_feat):
-    if indptr.dim() != 1 or indices.dim() != 1:
-        raise RuntimeError("indptr / indices must be 1-D")
-    if indptr.size(0) - 1 != m_feat:
-        raise RuntimeError(f"indptr describes {indptr.size(0) - 1} rows but features have {m_feat} nodes")
+# Every operator below: the block plan / val_ptr look-ups (shared by both transports), the torch C++ binding when there is
+# one (csrc/torch_ext.cpp: same checks, same C ABI call), else the ctypes transport: checks by family, allocations, call().
 
 
-def _check_qkv(Q, K, V):
-    check_device(Q=Q, K=K, V=V)
-    check_contiguous(Q=Q, K=K, V=V)
-    check_dtype(torch.float32, Q=Q, K=K, V=V)
-    check_feat3(Q=Q, K=K, V=V)
+def _checks(indptr, indices, Q, K, V, rows=None, val=None, **like_Q):
+    """What every GT operator checks: Q / K / V (and `like_Q`: grad, out) fp32 [nodes, heads, feat] of one shape, the CSR
+    arrays of those nodes, and -- where the operator takes them -- the COO rows and the edge values -> (m, nnz, h, f)."""
+    m, h, f = check_feats(Q=Q, K=K, V=V, **like_Q)
+    nnz = check_csr(Q, m, indptr, indices)
+    if rows is not None:
+        check_edges(Q, nnz, torch.int32, rows=rows)
+    if val is not None:
+        check_edges(Q, nnz, torch.float32, val=val)
+    return m, nnz, h, f
 
 
-def _check_edges(nnz, **arrs):
-    for name, t in arrs.items():
-        if t.dim() != 1 or t.size(0) != nnz:
-            raise RuntimeError(f"{name} must have shape ({nnz},), got {tuple(t.shape)}")
+def _empty(like, *shape):
+    return torch.empty(shape, dtype=torch.float32, device=like.device)
 
 
 def gt_hyper_inference(indptr, indices, rows, val, smem_consume, Q, K, V):
@@ -55,26 +49,15 @@ def gt_hyper_inference(indptr, indices, rows, val, smem_consume, Q, K, V):
         plan = gt_stats_pair_applies(indptr, indices, val, Q)
         if plan is not None:
             return gt_hyper_forward_stats(indptr, indices, Q, K, V, plan=plan, val=val, save_stats=False)
+    plan = get_plan_obj(indptr, indices, Q, USE_BLOCK_PLAN)
     ext = _n.ext()
-    if ext is not None:  # torch C++ binding (csrc/torch_ext.cpp): same checks, same C ABI call
-        plan, meta, _ = get_plan(indptr, indices, Q.size(-1) if Q.dim() == 3 else 0, USE_BLOCK_PLAN)
-        return ext.gt_hyper_fwd(indptr, indices, rows, val, Q, K, V, False, val_ptr(val) is None, plan or 0, meta or 0)
-    check_device(indptr=indptr, indices=indices, rows=rows, val=val)
-    check_contiguous(indptr=indptr, indices=indices, rows=rows, val=val)
-    check_dtype(torch.int32, indptr=indptr, indices=indices, rows=rows)
-    check_dtype(torch.float32, val=val)
-    _check_qkv(Q, K, V)
-    m, nnz, h, f = _dims(indptr, indices, Q)
-    _check_graph(indptr, indices, Q.size(0))
-    _check_edges(nnz, rows=rows, val=val)
-    with torch.cuda.device(Q.device):
-        out = torch.empty_like(Q)
-        plan, meta, need_ws = get_plan(indptr, indices, f, USE_BLOCK_PLAN)
-        # scratch for per-edge values: required when the plan has edge-global ranges
-        ws = torch.empty((h, nnz), dtype=torch.float32, device=Q.device) if plan is not None else None
-        _n.check(_n.lib().dfgnn_gt_hyper_fwd(m, nnz, h, f, ptr(indptr), ptr(indices), ptr(rows), val_ptr(val),
-                                             ptr(Q), ptr(K), ptr(V), None, ptr(ws), ptr(out), plan, meta,
-                                             stream_ptr(Q.device)), "gt_hyper_inference")
+    if ext is not None:
+        return ext.gt_hyper_fwd(indptr, indices, rows, val, Q, K, V, False, val_ptr(val) is None, *plan_ptrs(plan))
+    m, nnz, h, f = _checks(indptr, indices, Q, K, V, rows, val)
+    out = torch.empty_like(Q)
+    ws = _empty(Q, h, nnz) if plan is not None else None   # scratch for per-edge values (the plan's edge-global ranges)
+    call("dfgnn_gt_hyper_fwd", "gt_hyper_inference", Q.device, m, nnz, h, f, indptr, indices, rows, val_ptr(val), Q, K, V,
+         None, ws, out, *plan_ptrs(plan))
     return [out]
 
 
@@ -86,25 +69,14 @@ def gt_hyper_inference_ablation(indptr, indices, rows, val, smem_consume, Q, K, 
 
 def gt_hyper_forward(row_ptr, col_ind, rows, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V):
     """fused_gtconv.cpp:79-116 -> [out, attn_edge[h, nnz]] (training forward)."""
+    pp, mp = plan_ptrs(get_plan_obj(row_ptr, col_ind, Q, USE_BLOCK_PLAN))
     ext = _n.ext()
     if ext is not None:
-        plan, meta, _ = get_plan(row_ptr, col_ind, Q.size(-1) if Q.dim() == 3 else 0, USE_BLOCK_PLAN)
-        return ext.gt_hyper_fwd(row_ptr, col_ind, rows, val, Q, K, V, True, val_ptr(val) is None, plan or 0, meta or 0)
-    check_device(row_ptr=row_ptr, col_ind=col_ind, val=val, rows=rows)
-    check_contiguous(row_ptr=row_ptr, col_ind=col_ind, val=val, rows=rows)
-    check_dtype(torch.int32, row_ptr=row_ptr, col_ind=col_ind, rows=rows)
-    check_dtype(torch.float32, val=val)
-    _check_qkv(Q, K, V)
-    m, nnz, h, f = _dims(row_ptr, col_ind, Q)
-    _check_graph(row_ptr, col_ind, Q.size(0))
-    _check_edges(nnz, rows=rows, val=val)
-    with torch.cuda.device(Q.device):
-        out = torch.empty_like(Q)
-        attn_edge = torch.empty((h, nnz), dtype=torch.float32, device=Q.device)
-        plan, meta, _ = get_plan(row_ptr, col_ind, f, USE_BLOCK_PLAN)
-        _n.check(_n.lib().dfgnn_gt_hyper_fwd(m, nnz, h, f, ptr(row_ptr), ptr(col_ind), ptr(rows), val_ptr(val),
-                                             ptr(Q), ptr(K), ptr(V), ptr(attn_edge), None, ptr(out), plan, meta,
-                                             stream_ptr(Q.device)), "gt_hyper_forward")
+        return ext.gt_hyper_fwd(row_ptr, col_ind, rows, val, Q, K, V, True, val_ptr(val) is None, pp, mp)
+    m, nnz, h, f = _checks(row_ptr, col_ind, Q, K, V, rows, val)
+    out, attn_edge = torch.empty_like(Q), _empty(Q, h, nnz)
+    call("dfgnn_gt_hyper_fwd", "gt_hyper_forward", Q.device, m, nnz, h, f, row_ptr, col_ind, rows, val_ptr(val), Q, K, V,
+         attn_edge, None, out, pp, mp)
     return [out, attn_edge]
 
 
@@ -112,34 +84,20 @@ def gt_backward(row_ptr, col_ind, rows, val, col_ptr, row_ind, val_idx, smem_con
                 grad):
     """fused_gtconv.cpp:125-172 -> [dQ, dK, dV]."""
     val_idx = as_int32(val_idx)
+    pp, mp = plan_ptrs(get_plan_obj(row_ptr, col_ind, Q, USE_BLOCK_PLAN))
     ext = _n.ext()
     if ext is not None:
-        plan, meta, _ = get_plan(row_ptr, col_ind, Q.size(-1) if Q.dim() == 3 else 0, USE_BLOCK_PLAN)
         return ext.gt_bwd(row_ptr, col_ind, rows, val, col_ptr, row_ind, val_idx, Q, K, V, attn_edge, grad,
-                          val_ptr(val) is None, plan or 0, meta or 0)
-    check_device(row_ptr=row_ptr, col_ind=col_ind, rows=rows, val=val, col_ptr=col_ptr, row_ind=row_ind,
-                 val_idx=val_idx, attn_edge=attn_edge, grad=grad)
-    check_contiguous(row_ptr=row_ptr, col_ind=col_ind, rows=rows, val=val, col_ptr=col_ptr, row_ind=row_ind,
-                     val_idx=val_idx, attn_edge=attn_edge, grad=grad)
-    check_dtype(torch.int32, row_ptr=row_ptr, col_ind=col_ind, rows=rows, col_ptr=col_ptr, row_ind=row_ind)
-    check_dtype(torch.float32, val=val, attn_edge=attn_edge, grad=grad)
-    _check_qkv(Q, K, V)
-    check_feat3(Q=Q, grad=grad)
-    m, nnz, h, f = _dims(row_ptr, col_ind, Q)
-    _check_graph(row_ptr, col_ind, Q.size(0))
-    _check_edges(nnz, rows=rows, val=val, row_ind=row_ind, val_idx=val_idx)
-    if col_ptr.dim() != 1 or col_ptr.size(0) != m + 1:
-        raise RuntimeError(f"col_ptr must have shape ({m + 1},): the adjacency must be square")
+                          val_ptr(val) is None, pp, mp)
+    m, nnz, h, f = _checks(row_ptr, col_ind, Q, K, V, rows, val, grad=grad)
+    check_csc(Q, m, nnz, col_ptr, row_ind=row_ind, val_idx=val_idx)
+    check_family(Q, torch.float32, attn_edge=attn_edge)
     if attn_edge.numel() != h * nnz:
         raise RuntimeError(f"attn_edge must have {h}*{nnz} elements, got {attn_edge.numel()}")
-    with torch.cuda.device(Q.device):
-        grad_edge = torch.empty((h, nnz), dtype=torch.float32, device=Q.device)
-        dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
-        plan, meta, _ = get_plan(row_ptr, col_ind, f, USE_BLOCK_PLAN)
-        _n.check(_n.lib().dfgnn_gt_bwd(m, nnz, h, f, ptr(row_ptr), ptr(col_ind), ptr(rows), val_ptr(val),
-                                       ptr(col_ptr), ptr(row_ind), ptr(val_idx), ptr(Q), ptr(K), ptr(V),
-                                       ptr(attn_edge), ptr(grad), ptr(grad_edge), ptr(dQ), ptr(dK), ptr(dV),
-                                       plan, meta, stream_ptr(Q.device)), "gt_backward")
+    grad_edge = _empty(Q, h, nnz)
+    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
+    call("dfgnn_gt_bwd", "gt_backward", Q.device, m, nnz, h, f, row_ptr, col_ind, rows, val_ptr(val), col_ptr, row_ind,
+         val_idx, Q, K, V, attn_edge, grad, grad_edge, dQ, dK, dV, pp, mp)
     return [dQ, dK, dV]
 
 
@@ -159,6 +117,7 @@ USE_RANKED_PAIR = os.environ.get("DFGNN_RANKED", "1") != "0"
 RANKED_HEADS = tuple(int(x) for x in os.environ.get("DFGNN_RANKED_HEADS", "1").split(",") if x)
 
 
+
 def gt_stats_pair_applies(row_ptr, col_ind, val, Q):
     """The block plan (a true value) when gt_hyper_forward_stats / gt_backward_stats can serve this call -- a plan whose
     ranges are all dense (dfgnn_gt_stats_applies) -- else None.  The plan may be handed to the two calls (`plan=`), which
@@ -166,7 +125,7 @@ def gt_stats_pair_applies(row_ptr, col_ind, val, Q):
     dense weights, _binding_util.plan_dense_weights)."""
     if not (USE_STATS_PAIR and USE_BLOCK_PLAN) or Q.dim() != 3 or not Q.is_cuda:
         return None
-    plan = get_plan_obj(row_ptr, col_ind, Q.size(-1), True)
+    plan = get_plan_obj(row_ptr, col_ind, Q)
     if plan is not None and plan.stats_applies(Q.size(1)):
         return plan
     return None
@@ -184,8 +143,8 @@ def gt_stats_pair_chosen(row_ptr, col_ind, val, Q):
 
 
 def _stats_weights(plan, row_ptr, val):
-    """None for unit edge values (or no `val`), else the plan's dense weights of `val`."""
-    if val is None or val_ptr(val) is None:
+    """None without a plan and for unit edge values (or no `val`), else the plan's dense weights of `val`."""
+    if plan is None or val is None or val_ptr(val) is None:
         return None
     return plan_dense_weights(plan, row_ptr, val)
 
@@ -200,7 +159,7 @@ def gt_ranked_pair_applies(row_ptr, col_ind, val, Q):
     """The block plan when gt_hyper_forward_ranked / gt_backward_ranked can serve this call, else None."""
     if not (USE_RANKED_PAIR and USE_BLOCK_PLAN) or Q.dim() != 3 or not Q.is_cuda or val_ptr(val) is not None:
         return None
-    plan = get_plan_obj(row_ptr, col_ind, Q.size(-1), True)
+    plan = get_plan_obj(row_ptr, col_ind, Q)
     if plan is not None and plan.stats_applies(Q.size(1)):
         return plan
     return None
@@ -216,63 +175,58 @@ def gt_ranked_pair_chosen(row_ptr, col_ind, val, Q):
     return gt_ranked_pair_applies(row_ptr, col_ind, val, Q)
 
 
+def gt_training_pair(row_ptr, col_ind, val, Q):
+    """Which training pair FusedGTFunction_hyper takes for this call -> (pair, plan): ("stats", plan) where the policy
+    chooses the statistics pair, else ("ranked", plan) where it chooses the rank-ordered attn_edge pair, else
+    ("attn_edge", None): the reference's form, gt_hyper_forward / gt_backward."""
+    plan = gt_stats_pair_chosen(row_ptr, col_ind, val, Q)
+    if plan is not None:
+        return "stats", plan
+    plan = gt_ranked_pair_chosen(row_ptr, col_ind, val, Q)
+    return ("ranked", plan) if plan is not None else ("attn_edge", None)
+
+
 def gt_hyper_forward_ranked(row_ptr, col_ind, Q, K, V, plan=None):
     """-> [out, attn_ranked[1, nnz]] (row i's k-th edge by increasing column at row_ptr[i] + k)."""
     if plan is None:
-        plan = get_plan_obj(row_ptr, col_ind, Q.size(-1) if Q.dim() == 3 else 0, USE_BLOCK_PLAN)
-    pp, mp = plan.ptrs() if plan is not None else (None, None)
+        plan = get_plan_obj(row_ptr, col_ind, Q, USE_BLOCK_PLAN)
+    pp, mp = plan_ptrs(plan)
     ext = _n.ext()
-    if ext is not None and hasattr(ext, "gt_hyper_fwd_ranked"):
-        return ext.gt_hyper_fwd_ranked(row_ptr, col_ind, Q, K, V, pp or 0, mp or 0)
-    check_device(row_ptr=row_ptr, col_ind=col_ind)
-    check_contiguous(row_ptr=row_ptr, col_ind=col_ind)
-    check_dtype(torch.int32, row_ptr=row_ptr, col_ind=col_ind)
-    _check_qkv(Q, K, V)
-    m, nnz, h, f = _dims(row_ptr, col_ind, Q)
-    _check_graph(row_ptr, col_ind, Q.size(0))
-    with torch.cuda.device(Q.device):
-        out = torch.empty_like(Q)
-        attn = torch.empty((h, nnz), dtype=torch.float32, device=Q.device)
-        _n.check(_n.lib().dfgnn_gt_hyper_fwd_ranked(m, nnz, h, f, ptr(row_ptr), ptr(col_ind), ptr(Q), ptr(K), ptr(V), ptr(attn),
-                                                    ptr(out), pp, mp, stream_ptr(Q.device)), "gt_hyper_forward_ranked")
+    if ext is not None:
+        return ext.gt_hyper_fwd_ranked(row_ptr, col_ind, Q, K, V, pp, mp)
+    m, nnz, h, f = _checks(row_ptr, col_ind, Q, K, V)
+    out, attn = torch.empty_like(Q), _empty(Q, h, nnz)
+    call("dfgnn_gt_hyper_fwd_ranked", "gt_hyper_forward_ranked", Q.device, m, nnz, h, f, row_ptr, col_ind, Q, K, V, attn,
+         out, pp, mp)
     return [out, attn]
 
 
 def gt_backward_ranked(row_ptr, col_ind, Q, K, V, attn_ranked, grad, plan=None):
     """-> [dQ, dK, dV] from the rank-ordered attention values of gt_hyper_forward_ranked."""
     if plan is None:
-        plan = get_plan_obj(row_ptr, col_ind, Q.size(-1) if Q.dim() == 3 else 0, USE_BLOCK_PLAN)
-    pp, mp = plan.ptrs() if plan is not None else (None, None)
+        plan = get_plan_obj(row_ptr, col_ind, Q, USE_BLOCK_PLAN)
+    pp, mp = plan_ptrs(plan)
     ext = _n.ext()
-    if ext is not None and hasattr(ext, "gt_bwd_ranked"):
-        return ext.gt_bwd_ranked(row_ptr, col_ind, Q, K, V, attn_ranked, grad, pp or 0, mp or 0)
-    check_device(row_ptr=row_ptr, col_ind=col_ind, attn_ranked=attn_ranked, grad=grad)
-    check_contiguous(row_ptr=row_ptr, col_ind=col_ind, attn_ranked=attn_ranked, grad=grad)
-    check_dtype(torch.int32, row_ptr=row_ptr, col_ind=col_ind)
-    check_dtype(torch.float32, attn_ranked=attn_ranked, grad=grad)
-    _check_qkv(Q, K, V)
-    check_feat3(Q=Q, grad=grad)
-    m, nnz, h, f = _dims(row_ptr, col_ind, Q)
-    _check_graph(row_ptr, col_ind, Q.size(0))
+    if ext is not None:
+        return ext.gt_bwd_ranked(row_ptr, col_ind, Q, K, V, attn_ranked, grad, pp, mp)
+    m, nnz, h, f = _checks(row_ptr, col_ind, Q, K, V, grad=grad)
+    check_family(Q, torch.float32, attn_ranked=attn_ranked)
     if attn_ranked.numel() != h * nnz:
         raise RuntimeError(f"attn_ranked must have {h}*{nnz} elements, got {attn_ranked.numel()}")
-    with torch.cuda.device(Q.device):
-        dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
-        _n.check(_n.lib().dfgnn_gt_bwd_ranked(m, nnz, h, f, ptr(row_ptr), ptr(col_ind), ptr(Q), ptr(K), ptr(V), ptr(attn_ranked),
-                                              ptr(grad), ptr(dQ), ptr(dK), ptr(dV), pp, mp, stream_ptr(Q.device)),
-                 "gt_backward_ranked")
+    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
+    call("dfgnn_gt_bwd_ranked", "gt_backward_ranked", Q.device, m, nnz, h, f, row_ptr, col_ind, Q, K, V, attn_ranked, grad,
+         dQ, dK, dV, pp, mp)
     return [dQ, dK, dV]
 
 
 def gt_hyper_step_raw(row_ptr, col_ind, rows, val, col_ptr, row_ind, val_idx, smem, Q, K, V, grad):
     """-> [out, dQ, dK, dV]: the launches of one FusedGTFunction_hyper forward + backward as explicit operator calls (no
     autograd graph), choosing the pair the way the autograd function does -- what the HIP-graph replays capture."""
-    plan = gt_stats_pair_chosen(row_ptr, col_ind, val, Q)
-    if plan is not None:
+    pair, plan = gt_training_pair(row_ptr, col_ind, val, Q)
+    if pair == "stats":
         out, rmax, rsum = gt_hyper_forward_stats(row_ptr, col_ind, Q, K, V, plan=plan, val=val)
         return [out] + list(gt_backward_stats(row_ptr, col_ind, Q, K, V, rmax, rsum, grad, plan=plan, val=val))
-    plan = gt_ranked_pair_chosen(row_ptr, col_ind, val, Q)
-    if plan is not None:
+    if pair == "ranked":
         out, attn = gt_hyper_forward_ranked(row_ptr, col_ind, Q, K, V, plan=plan)
         return [out] + list(gt_backward_ranked(row_ptr, col_ind, Q, K, V, attn, grad, plan=plan))
     out, attn = gt_hyper_forward(row_ptr, col_ind, rows, val, col_ptr, row_ind, val_idx, smem, Q, K, V)
@@ -282,54 +236,35 @@ def gt_hyper_step_raw(row_ptr, col_ind, rows, val, col_ptr, row_ind, val_idx, sm
 def gt_hyper_forward_stats(row_ptr, col_ind, Q, K, V, plan=None, val=None, save_stats=True):
     """-> [out, row_max[m, h], row_sum[m, h]]: the training forward without attn_edge (call gt_stats_pair_applies first).
     val: edge values (None or all ones: unit values).  save_stats=False -> [out] (inference)."""
-    ext = _n.ext()
     if plan is None:
-        plan = get_plan_obj(row_ptr, col_ind, Q.size(-1) if Q.dim() == 3 else 0, USE_BLOCK_PLAN)
-    weights = _stats_weights(plan, row_ptr, val) if plan is not None else None
-    plan, meta = plan.ptrs() if plan is not None else (None, None)
-    if ext is not None and hasattr(ext, "gt_hyper_fwd_stats"):
-        return ext.gt_hyper_fwd_stats(row_ptr, col_ind, Q, K, V, plan or 0, meta or 0, weights, save_stats)
-    check_device(row_ptr=row_ptr, col_ind=col_ind)
-    check_contiguous(row_ptr=row_ptr, col_ind=col_ind)
-    check_dtype(torch.int32, row_ptr=row_ptr, col_ind=col_ind)
-    _check_qkv(Q, K, V)
-    m, nnz, h, f = _dims(row_ptr, col_ind, Q)
-    _check_graph(row_ptr, col_ind, Q.size(0))
-    with torch.cuda.device(Q.device):
-        out = torch.empty_like(Q)
-        row_max = torch.empty((m, h), dtype=torch.float32, device=Q.device) if save_stats else None
-        row_sum = torch.empty((m, h), dtype=torch.float32, device=Q.device) if save_stats else None
-        _n.check(_n.lib().dfgnn_gt_hyper_fwd_stats(m, nnz, h, f, ptr(row_ptr), ptr(col_ind), ptr(weights), ptr(Q), ptr(K),
-                                                   ptr(V), ptr(row_max), ptr(row_sum), ptr(out), plan, meta,
-                                                   stream_ptr(Q.device)), "gt_hyper_forward_stats")
+        plan = get_plan_obj(row_ptr, col_ind, Q, USE_BLOCK_PLAN)
+    weights = _stats_weights(plan, row_ptr, val)
+    pp, mp = plan_ptrs(plan)
+    ext = _n.ext()
+    if ext is not None:
+        return ext.gt_hyper_fwd_stats(row_ptr, col_ind, Q, K, V, pp, mp, weights, save_stats)
+    m, nnz, h, f = _checks(row_ptr, col_ind, Q, K, V)
+    out = torch.empty_like(Q)
+    row_max, row_sum = (_empty(Q, m, h), _empty(Q, m, h)) if save_stats else (None, None)
+    call("dfgnn_gt_hyper_fwd_stats", "gt_hyper_forward_stats", Q.device, m, nnz, h, f, row_ptr, col_ind, weights, Q, K, V,
+         row_max, row_sum, out, pp, mp)
     return [out, row_max, row_sum] if save_stats else [out]
 
 
 def gt_backward_stats(row_ptr, col_ind, Q, K, V, row_max, row_sum, grad, plan=None, val=None):
     """-> [dQ, dK, dV] from the row statistics of gt_hyper_forward_stats (P is recomputed on the matrix cores)."""
-    ext = _n.ext()
     if plan is None:
-        plan = get_plan_obj(row_ptr, col_ind, Q.size(-1) if Q.dim() == 3 else 0, USE_BLOCK_PLAN)
-    weights = _stats_weights(plan, row_ptr, val) if plan is not None else None
-    plan, meta = plan.ptrs() if plan is not None else (None, None)
-    if ext is not None and hasattr(ext, "gt_bwd_stats"):
-        return ext.gt_bwd_stats(row_ptr, col_ind, Q, K, V, row_max, row_sum, grad, plan or 0, meta or 0, weights)
-    check_device(row_ptr=row_ptr, col_ind=col_ind, row_max=row_max, row_sum=row_sum, grad=grad)
-    check_contiguous(row_ptr=row_ptr, col_ind=col_ind, row_max=row_max, row_sum=row_sum, grad=grad)
-    check_dtype(torch.int32, row_ptr=row_ptr, col_ind=col_ind)
-    check_dtype(torch.float32, row_max=row_max, row_sum=row_sum, grad=grad)
-    _check_qkv(Q, K, V)
-    check_feat3(Q=Q, grad=grad)
-    m, nnz, h, f = _dims(row_ptr, col_ind, Q)
-    _check_graph(row_ptr, col_ind, Q.size(0))
-    for name, t in (("row_max", row_max), ("row_sum", row_sum)):
-        if tuple(t.shape) != (m, h):
-            raise RuntimeError(f"{name} must have shape ({m}, {h}), got {tuple(t.shape)}")
-    with torch.cuda.device(Q.device):
-        dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
-        _n.check(_n.lib().dfgnn_gt_bwd_stats(m, nnz, h, f, ptr(row_ptr), ptr(col_ind), ptr(weights), ptr(Q), ptr(K), ptr(V),
-                                             ptr(row_max), ptr(row_sum), ptr(grad), ptr(dQ), ptr(dK), ptr(dV), plan, meta,
-                                             stream_ptr(Q.device)), "gt_backward_stats")
+        plan = get_plan_obj(row_ptr, col_ind, Q, USE_BLOCK_PLAN)
+    weights = _stats_weights(plan, row_ptr, val)
+    pp, mp = plan_ptrs(plan)
+    ext = _n.ext()
+    if ext is not None:
+        return ext.gt_bwd_stats(row_ptr, col_ind, Q, K, V, row_max, row_sum, grad, pp, mp, weights)
+    m, nnz, h, f = _checks(row_ptr, col_ind, Q, K, V, grad=grad)
+    check_2d(Q, m, h, row_max=row_max, row_sum=row_sum)
+    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
+    call("dfgnn_gt_bwd_stats", "gt_backward_stats", Q.device, m, nnz, h, f, row_ptr, col_ind, weights, Q, K, V, row_max,
+         row_sum, grad, dQ, dK, dV, pp, mp)
     return [dQ, dK, dV]
 
 
@@ -339,33 +274,16 @@ def gt_backward_stats(row_ptr, col_ind, Q, K, V, row_max, row_sum, grad, plan=No
 # takes it; FusedGTFunction_hyper does not.
 
 
-def _check_rowstats_graph(row_ptr, col_ind, val, Q, K, V):
-    edge_val = {} if val is None else {"val": val}
-    check_device(row_ptr=row_ptr, col_ind=col_ind, **edge_val)
-    check_contiguous(row_ptr=row_ptr, col_ind=col_ind, **edge_val)
-    check_dtype(torch.int32, row_ptr=row_ptr, col_ind=col_ind)
-    check_dtype(torch.float32, **edge_val)
-    _check_qkv(Q, K, V)
-    m, nnz, h, f = _dims(row_ptr, col_ind, Q)
-    _check_graph(row_ptr, col_ind, Q.size(0))
-    _check_edges(nnz, **edge_val)
-    return m, nnz, h, f
-
-
 def gt_forward_rowstats(row_ptr, col_ind, val, Q, K, V):
     """-> [out, row_max[m, h], row_sum[m, h]]: the training forward of any graph without attn_edge.
     val: edge values fp32[nnz] in CSR order; None or all ones: unit values."""
     ext = _n.ext()
-    if ext is not None and hasattr(ext, "gt_fwd_rowstats"):
+    if ext is not None:
         return ext.gt_fwd_rowstats(row_ptr, col_ind, val, Q, K, V, val_ptr(val) is None)
-    m, nnz, h, f = _check_rowstats_graph(row_ptr, col_ind, val, Q, K, V)
-    with torch.cuda.device(Q.device):
-        out = torch.empty_like(Q)
-        row_max = torch.empty((m, h), dtype=torch.float32, device=Q.device)
-        row_sum = torch.empty((m, h), dtype=torch.float32, device=Q.device)
-        _n.check(_n.lib().dfgnn_gt_fwd_rowstats(m, nnz, h, f, ptr(row_ptr), ptr(col_ind), val_ptr(val), ptr(Q), ptr(K),
-                                                ptr(V), ptr(row_max), ptr(row_sum), ptr(out), stream_ptr(Q.device)),
-                 "gt_forward_rowstats")
+    m, nnz, h, f = _checks(row_ptr, col_ind, Q, K, V, val=val)
+    out, row_max, row_sum = torch.empty_like(Q), _empty(Q, m, h), _empty(Q, m, h)
+    call("dfgnn_gt_fwd_rowstats", "gt_forward_rowstats", Q.device, m, nnz, h, f, row_ptr, col_ind, val_ptr(val), Q, K, V,
+         row_max, row_sum, out)
     return [out, row_max, row_sum]
 
 
@@ -374,117 +292,62 @@ def gt_backward_rowstats(row_ptr, col_ind, val, col_ptr, row_ind, val_idx, Q, K,
     val as in gt_forward_rowstats."""
     val_idx = as_int32(val_idx)
     ext = _n.ext()
-    if ext is not None and hasattr(ext, "gt_bwd_rowstats"):
+    if ext is not None:
         return ext.gt_bwd_rowstats(row_ptr, col_ind, val, col_ptr, row_ind, val_idx, Q, K, V, out, row_max, row_sum, grad,
                                    val_ptr(val) is None)
-    m, nnz, h, f = _check_rowstats_graph(row_ptr, col_ind, val, Q, K, V)
-    check_device(col_ptr=col_ptr, row_ind=row_ind, val_idx=val_idx, out=out, row_max=row_max, row_sum=row_sum, grad=grad)
-    check_contiguous(col_ptr=col_ptr, row_ind=row_ind, val_idx=val_idx, out=out, row_max=row_max, row_sum=row_sum,
-                     grad=grad)
-    check_dtype(torch.int32, col_ptr=col_ptr, row_ind=row_ind)
-    check_dtype(torch.float32, out=out, row_max=row_max, row_sum=row_sum, grad=grad)
-    check_feat3(Q=Q, out=out, grad=grad)
-    _check_edges(nnz, row_ind=row_ind, val_idx=val_idx)
-    if col_ptr.dim() != 1 or col_ptr.size(0) != m + 1:
-        raise RuntimeError(f"col_ptr must have shape ({m + 1},): the adjacency must be square")
-    for name, t in (("row_max", row_max), ("row_sum", row_sum)):
-        if tuple(t.shape) != (m, h):
-            raise RuntimeError(f"{name} must have shape ({m}, {h}), got {tuple(t.shape)}")
-    with torch.cuda.device(Q.device):
-        delta = torch.empty((m, h), dtype=torch.float32, device=Q.device)
-        dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
-        _n.check(_n.lib().dfgnn_gt_bwd_rowstats(m, nnz, h, f, ptr(row_ptr), ptr(col_ind), val_ptr(val), ptr(col_ptr),
-                                                ptr(row_ind), ptr(val_idx), ptr(Q), ptr(K), ptr(V), ptr(out),
-                                                ptr(row_max), ptr(row_sum), ptr(grad), ptr(delta), ptr(dQ), ptr(dK),
-                                                ptr(dV), stream_ptr(Q.device)), "gt_backward_rowstats")
+    m, nnz, h, f = _checks(row_ptr, col_ind, Q, K, V, val=val, out=out, grad=grad)
+    check_csc(Q, m, nnz, col_ptr, row_ind=row_ind, val_idx=val_idx)
+    check_2d(Q, m, h, row_max=row_max, row_sum=row_sum)
+    delta = _empty(Q, m, h)
+    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
+    call("dfgnn_gt_bwd_rowstats", "gt_backward_rowstats", Q.device, m, nnz, h, f, row_ptr, col_ind, val_ptr(val), col_ptr,
+         row_ind, val_idx, Q, K, V, out, row_max, row_sum, grad, delta, dQ, dK, dV)
     return [dQ, dK, dV]
 
 
-def _ext_variant(which, indptr, indices, rows, val, Q, K, V):
-    """The CSR-taking inference variants through the torch C++ binding (csrc/torch_ext.cpp: gt_variant_fwd), or None."""
+# ---- the CSR-taking inference variants ----------------------------------------------------------------------------------
+_VARIANTS = ("gt_tiling", "gt_csr", "gt_csr_gm", "gt_softmax", "gt_softmax_gm")   # by `which` of torch_ext.cpp: gt_variant_fwd
+
+
+def _variant(which, indptr, indices, rows, val, Q, K, V):
+    """-> out of inference variant `which`: dfgnn_<name>_fwd, reported as <name>_inference."""
     ext = _n.ext()
-    if ext is None or not hasattr(ext, "gt_variant_fwd"):
-        return None
-    return ext.gt_variant_fwd(which, indptr, indices, rows, val, Q, K, V, val_ptr(val) is None)
+    if ext is not None:
+        return ext.gt_variant_fwd(which, indptr, indices, rows, val, Q, K, V, val_ptr(val) is None)
+    name = _VARIANTS[which]
+    m, nnz, h, f = _checks(indptr, indices, Q, K, V, rows, val)
+    out = torch.empty_like(Q)
+    # 'tiling' and the two-kernel 'softmax' forms multiply the values in as they are (the latter after the COO rows, and
+    # like the 'csr' forms with the logits [h, nnz] as scratch); the 'csr' forms take NULL for all ones
+    graph = (indptr, indices) if which < 3 else (indptr, indices, rows)
+    outs = (out,) if which == 0 else (_empty(Q, h, nnz), out)
+    call(f"dfgnn_{name}_fwd", f"{name}_inference", Q.device, m, nnz, h, f, *graph, val_ptr(val) if which in (1, 2) else val,
+         Q, K, V, *outs)
+    return out
 
 
 def gt_tiling_inference(indptr, indices, val, smem_consume, Q, K, V):
     """fused_gtconv.cpp:244-276 -> [out]"""
-    out = _ext_variant(0, indptr, indices, None, val, Q, K, V)
-    if out is not None:
-        return [out]
-    check_device(indptr=indptr, indices=indices, val=val)
-    check_contiguous(indptr=indptr, indices=indices, val=val)
-    check_dtype(torch.int32, indptr=indptr, indices=indices)
-    check_dtype(torch.float32, val=val)
-    _check_qkv(Q, K, V)
-    m, nnz, h, f = _dims(indptr, indices, Q)
-    _check_graph(indptr, indices, Q.size(0))
-    _check_edges(nnz, val=val)
-    with torch.cuda.device(Q.device):
-        out = torch.empty_like(Q)
-        _n.check(_n.lib().dfgnn_gt_tiling_fwd(m, nnz, h, f, ptr(indptr), ptr(indices), ptr(val), ptr(Q), ptr(K),
-                                              ptr(V), ptr(out), stream_ptr(Q.device)), "gt_tiling_inference")
-    return [out]
-
-
-def _gt_csr(fn_name, what, indptr, indices, val, Q, K, V):
-    out = _ext_variant(1 if fn_name == "dfgnn_gt_csr_fwd" else 2, indptr, indices, None, val, Q, K, V)
-    if out is not None:
-        return [out]
-    check_device(indptr=indptr, indices=indices, val=val)
-    check_contiguous(indptr=indptr, indices=indices, val=val)
-    check_dtype(torch.int32, indptr=indptr, indices=indices)
-    check_dtype(torch.float32, val=val)
-    _check_qkv(Q, K, V)
-    m, nnz, h, f = _dims(indptr, indices, Q)
-    _check_graph(indptr, indices, Q.size(0))
-    _check_edges(nnz, val=val)
-    with torch.cuda.device(Q.device):
-        out = torch.empty_like(Q)
-        logits = torch.empty((h, nnz), dtype=torch.float32, device=Q.device)
-        _n.check(getattr(_n.lib(), fn_name)(m, nnz, h, f, ptr(indptr), ptr(indices), val_ptr(val), ptr(Q), ptr(K), ptr(V),
-                                            ptr(logits), ptr(out), stream_ptr(Q.device)), what)
-    return [out]
+    return [_variant(0, indptr, indices, None, val, Q, K, V)]
 
 
 def gt_csr_inference(indptr, indices, val, smem_consume, Q, K, V):
     """fused_gtconv.cpp:174-207 -> [out].  The node-parallel CSR baseline of the reference's sweeps (fused_gt_csr): a wave
     per row, the row's logits materialised in LDS (csrc/csr_fwd.hip), then max / sum / weighted-sum sweeps."""
-    return _gt_csr("dfgnn_gt_csr_fwd", "gt_csr_inference", indptr, indices, val, Q, K, V)
+    return [_variant(1, indptr, indices, None, val, Q, K, V)]
 
 
 def gt_csr_gm_inference(indptr, indices, val, Q, K, V):
     """fused_gtconv.cpp:209-242 -> [out].  As gt_csr_inference with the logits in global memory
     (fused_gt_csr_global_memory)."""
-    return _gt_csr("dfgnn_gt_csr_gm_fwd", "gt_csr_gm_inference", indptr, indices, val, Q, K, V)
-
-
-def _gt_softmax(fn_name, what, indptr, indices, rows, val, Q, K, V):
-    out = _ext_variant(3 if fn_name == "dfgnn_gt_softmax_fwd" else 4, indptr, indices, rows, val, Q, K, V)
-    if out is not None:
-        return out
-    check_device(indptr=indptr, indices=indices, rows=rows, val=val)
-    check_contiguous(indptr=indptr, indices=indices, rows=rows, val=val)
-    check_dtype(torch.int32, indptr=indptr, indices=indices, rows=rows)
-    check_dtype(torch.float32, val=val)
-    _check_qkv(Q, K, V)
-    m, nnz, h, f = _dims(indptr, indices, Q)
-    _check_graph(indptr, indices, Q.size(0))
-    _check_edges(nnz, rows=rows, val=val)
-    with torch.cuda.device(Q.device):
-        out = torch.empty_like(Q)
-        logits = torch.empty((h, nnz), dtype=torch.float32, device=Q.device)
-        _n.check(getattr(_n.lib(), fn_name)(m, nnz, h, f, ptr(indptr), ptr(indices), ptr(rows), ptr(val), ptr(Q),
-                                            ptr(K), ptr(V), ptr(logits), ptr(out), stream_ptr(Q.device)), what)
-    return out
+    return [_variant(2, indptr, indices, None, val, Q, K, V)]
 
 
 def gt_softmax_inference(indptr, indices, rows, val, smem_consume, Q, K, V):
     """fused_gtconv.cpp:316-352 -> [out] (two kernels: COO SDDMM, then LDS softmax+SpMM)."""
-    return [_gt_softmax("dfgnn_gt_softmax_fwd", "gt_softmax_inference", indptr, indices, rows, val, Q, K, V)]
+    return [_variant(3, indptr, indices, rows, val, Q, K, V)]
 
 
 def gt_softmax_gm_inference(indptr, indices, rows, val, Q, K, V):
     """fused_gtconv.cpp:354-389 -> bare Tensor (two kernels, logits re-read from global memory)."""
-    return _gt_softmax("dfgnn_gt_softmax_gm_fwd", "gt_softmax_gm_inference", indptr, indices, rows, val, Q, K, V)
+    return _variant(4, indptr, indices, rows, val, Q, K, V)

@@ -1071,15 +1071,29 @@ def test_hipgraph_capture_of_a_training_step(shape):
     assert not torch.equal(again[0], eager[0])
 
 
+def _plan_parts(plan, m, nnz):
+    """What dfgnn_plan_build defines of a plan buffer (csrc/plan.hip; the rest is scratch of the build): the header, the fit
+    and spill lists, and behind hdr[11] the packed edge coordinates, the edge bitmaps and the rank-ordered coordinates."""
+    buf, (nfit, nspill), coords = plan.buf, plan.meta[:2], plan.meta[11]
+    mask = (coords + (nnz + 1) // 2 + 4 + 3) & ~3
+    return [buf[:12], torch.tensor(plan.meta, dtype=torch.int32, device=buf.device), buf[12:12 + 2 * nfit],
+            buf[12 + 2 * m:12 + 2 * m + 2 * nspill], buf[coords:].view(torch.int16)[:nnz], buf[mask:mask + 16 * m],
+            buf[mask + 16 * m:].view(torch.int16)[:nnz]]
+
+
 def test_torch_extension_and_ctypes_bindings_agree():
     """The torch C++ extension (csrc/torch_ext.cpp) and the ctypes binding end in the same C ABI calls: bit-identical
     results for every entry point the extension serves, the same RuntimeError for a bad argument, and the extension is
-    the one the operator modules use."""
+    the one the operator modules use.  The plan-bound pairs run on a batch of dense ranges only (asserted first), so that
+    every leg reaches the kernels it names."""
+    import _binding_util
     import dfgnn_native
+    import dfgnn_preprocess
     import fused_gatconv as gat
     import fused_gtconv as gt
     from DFGNN.layers import preprocess_Hyper_fw_bw
     from DFGNN.utils import synthetic as S
+    from test_gpu_stats_pair import _geometry_batch
     assert dfgnn_native.ext() is not None
     g = S.pattern_like(batch_size=12, seed=8).to(DEV)
     A, rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem = preprocess_Hyper_fw_bw(g)
@@ -1087,6 +1101,18 @@ def test_torch_extension_and_ctypes_bindings_agree():
     Q, K, V = S.gt_features(m, 2, 64, seed=1, device=DEV)
     dO = torch.randn_like(Q)
     ar, ac, X = S.gat_features(m, 2, 64, seed=2, device=DEV)
+    src, dst = (t.to(DEV) for t in g.edges())
+    # a batch whose ranges are all dense: the statistics pair (two heads; unit and other edge values) and the rank-ordered pair
+    gb = _geometry_batch(1)
+    _, _, rp_b, ci_b, val_b, _, _, _, _ = preprocess_Hyper_fw_bw(gb)
+    mb, nnz_b = gb.num_nodes(), gb.num_edges()
+    wval = torch.rand_like(val_b) + 0.5
+    Q2, K2, V2 = S.gt_features(mb, 2, 32, seed=3, device=DEV)
+    Q1, K1, V1 = S.gt_features(mb, 1, 64, seed=4, device=DEV)
+    dO2, dO1 = torch.randn_like(Q2), torch.randn_like(Q1)
+    assert gt.gt_stats_pair_applies(rp_b, ci_b, val_b, Q2) is not None
+    assert gt.gt_stats_pair_applies(rp_b, ci_b, wval, Q2) is not None
+    assert gt.gt_ranked_pair_applies(rp_b, ci_b, val_b, Q1) is not None
 
     def run():
         out, attn = gt.gt_hyper_forward(row_ptr, col_ind, rows, val, col_ptr, row_ind, val_idx, smem, Q, K, V)
@@ -1096,24 +1122,70 @@ def test_torch_extension_and_ctypes_bindings_agree():
                 gat.gat_inference_softmax(smem, ar, ac, row_ptr, col_ind, rows, 0.2, X),
                 gat.gat_inference_softmax_gm(ar, ac, row_ptr, col_ind, rows, 0.2, X),
                 gat.gat_inference_tiling(ar, ac, row_ptr, col_ind, 0.2, X)]
+        n_first = len(res)
+        _binding_util._weights_cache.d.clear()       # (else the second transport only reads the first one's dense weights)
+        for v in (val_b, wval):
+            out, mx, sm = gt.gt_hyper_forward_stats(rp_b, ci_b, Q2, K2, V2, val=v)
+            res += [out, mx, sm] + list(gt.gt_backward_stats(rp_b, ci_b, Q2, K2, V2, mx, sm, dO2, val=v))
+        out, attn = gt.gt_hyper_forward_ranked(rp_b, ci_b, Q1, K1, V1)
+        res += [out, attn] + list(gt.gt_backward_ranked(rp_b, ci_b, Q1, K1, V1, attn, dO1))
+        for drop in (0.0, 0.3):
+            torch.manual_seed(11)                    # both transports draw the same dropout randoms
+            o, emax, esum, emask = gat.gat_forward(ar, ac, row_ptr, col_ind, 0.2, X, drop)
+            res += [o, emax, esum, emask] + list(gat.gat_backward(0.2, drop, row_ptr, col_ind, col_ptr, row_ind, val_idx, emax,
+                                                                  esum, emask, X, ar, ac, dO))
+        res += gt.gt_tiling_inference(row_ptr, col_ind, val, smem, Q, K, V)
+        res += gt.gt_csr_inference(row_ptr, col_ind, val, smem, Q, K, V)
+        res += gt.gt_csr_gm_inference(row_ptr, col_ind, val, Q, K, V)
+        res += gt.gt_softmax_inference(row_ptr, col_ind, rows, val, smem, Q, K, V)
+        res.append(gt.gt_softmax_gm_inference(row_ptr, col_ind, rows, val, Q, K, V))
+        res += list(dfgnn_preprocess.coo_to_hyper(src, dst, m, csc=True)) + list(dfgnn_preprocess.coo_to_hyper(src, dst, m, csc=False))
+        plan = _binding_util.build_plan(rp_b, ci_b, 32)
+        assert plan.num_dense == plan.num_fit > 0 and plan.num_spill == 0
+        res += _plan_parts(plan, mb, nnz_b)
+        _binding_util._weights_cache.d.clear()
+        res.append(_binding_util.plan_dense_weights(plan, rp_b, wval))
         try:
             gt.gt_hyper_inference(row_ptr, col_ind, rows.long(), val, smem, Q, K, V)
             err = None
         except RuntimeError as e:
             err = str(e)
-        return res, err
+        return res, err, n_first
 
-    via_ext, err_ext = run()
+    via_ext, err_ext, n_first = run()
     saved = dfgnn_native._ext
     dfgnn_native._ext = None                      # force the ctypes path
     try:
-        via_ctypes, err_ctypes = run()
+        via_ctypes, err_ctypes, _ = run()
     finally:
         dfgnn_native._ext = saved
-    assert len(via_ext) == len(via_ctypes) == 10
-    for a, b in zip(via_ext, via_ctypes):
-        assert torch.equal(a, b)
+    assert n_first == 10 and len(via_ext) == len(via_ctypes) == 10 + 12 + 5 + 14 + 5 + 11 + 7 + 1
+    for i, (a, b) in enumerate(zip(via_ext, via_ctypes)):
+        assert a.shape == b.shape and torch.equal(a, b), i
     assert err_ext and err_ctypes and "int32" in err_ext and "int32" in err_ctypes
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs")
+def test_tensors_of_two_devices_are_refused_by_both_transports():
+    """A tensor of another GPU than the call's would hand a kernel of this GPU a pointer of that one: RuntimeError through
+    the torch C++ extension and through the ctypes binding."""
+    import dfgnn_native
+    import fused_gtconv as gt
+    from DFGNN.layers import preprocess_Hyper
+    from DFGNN.utils import synthetic as S
+    g = S.pattern_like(batch_size=4, seed=2).to(DEV)
+    row_ptr, col_ind, rows, val, smem = preprocess_Hyper(g)
+    Q, K, V = S.gt_features(g.num_nodes(), 1, 32, seed=1, device=DEV)
+    assert dfgnn_native.ext() is not None
+    with pytest.raises(RuntimeError):
+        gt.gt_hyper_inference(row_ptr, col_ind, rows, val, smem, Q, K.to("cuda:1"), V)
+    saved = dfgnn_native._ext
+    dfgnn_native._ext = None                      # force the ctypes path
+    try:
+        with pytest.raises(RuntimeError):
+            gt.gt_hyper_inference(row_ptr, col_ind, rows, val, smem, Q, K.to("cuda:1"), V)
+    finally:
+        dfgnn_native._ext = saved
 
 
 def test_hipgraph_refuses_autograd_callables():

@@ -3,7 +3,7 @@
 usage: python tools/kernel_resources.py [pattern] [lib]"""
 import re, subprocess, sys
 pat = sys.argv[1] if len(sys.argv) > 1 else "dense"
-lib = sys.argv[2] if len(sys.argv) > 2 else "df-gnn_amd/libdfgnn.so"
+lib = sys.argv[2] if len(sys.argv) > 2 else "df-gnn_amd/libdfgnn_hip.so"
 import tempfile, os
 tmp = tempfile.mkdtemp()
 fb = os.path.join(tmp, "fb")
