@@ -1,0 +1,87 @@
+"""GATv2 layers (Brody et al., "How Attentive are Graph Attention Networks?") on the fused GATv2 operators
+(DFGNN/operators/fused_gatconv.py: GATv2ConvFuse_inference / GATv2ConvFuse).  This build's addition: the reference has no
+GATv2.  Parameters as dgl.nn.GATv2Conv publishes them -- two projections (`fc_src` / `fc_dst` there; one module when
+`share_weights`) and an attention vector per head -- with the logit of edge (i, j)
+
+    s_e = sum_d attn[h, d] LeakyReLU(fc_row(x_i)[h, d] + fc_col(x_j)[h, d])
+
+normalised over row i's out-edges (rows = sources of g.edges(), as every fused operator here; DFGNN/layers/util.py) and
+out_i = sum_e softmax(s)_e fc_col(x_j).  The non-fused branch restates that with torch index ops on A.row / A.col, the way
+DotGatConv (DFGNN/layers/GAT_DOT) restates its module; it materialises z[nnz, heads, out], which is what the fused
+operators avoid.  Both branches lay the projections out as view(-1, heads, out), so they agree for any head count."""
+import torch
+from torch import nn
+from torch.nn import functional as F
+
+from DFGNN.operators.fused_gatconv import GATv2ConvFuse, GATv2ConvFuse_inference
+
+
+class GATv2ConvDGL(nn.Module):
+    def __init__(self, in_size, out_size, num_heads, negative_slope=0.2, share_weights=False):
+        super().__init__()
+        self.in_size, self.out_size, self.num_heads = in_size, out_size, num_heads
+        self.negative_slope, self.share_weights = negative_slope, share_weights
+        self.fc_row = nn.Linear(in_size, out_size * num_heads)
+        self.fc_col = self.fc_row if share_weights else nn.Linear(in_size, out_size * num_heads)
+        self.attn = nn.Parameter(torch.zeros(num_heads, out_size))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        gain = nn.init.calculate_gain("relu")
+        nn.init.xavier_normal_(self.fc_row.weight, gain=gain)
+        if not self.share_weights:
+            nn.init.xavier_normal_(self.fc_col.weight, gain=gain)
+        nn.init.xavier_normal_(self.attn, gain=gain)
+
+    def project(self, feat):
+        """-> X_row, X_col [N, heads, out]; the same tensor when the weights are shared."""
+        x_row = self.fc_row(feat).view(-1, self.num_heads, self.out_size)
+        return x_row, (x_row if self.share_weights else self.fc_col(feat).view(-1, self.num_heads, self.out_size))
+
+    def forward_nofuse(self, A, feat):
+        return self.conv_nofuse(A, *self.project(feat))
+
+    def conv_nofuse(self, A, x_row, x_col):
+        """-> [N, heads, out] with torch index ops over the edges (A.row[e], A.col[e])."""
+        row, col = A.row.long(), A.col.long()
+        n = x_row.size(0)
+        s = (F.leaky_relu(x_row[row] + x_col[col], self.negative_slope) * self.attn).sum(-1)      # [E, heads]
+        smax = torch.full((n, self.num_heads), float("-inf"), device=s.device, dtype=s.dtype)
+        smax = smax.scatter_reduce(0, row[:, None].expand_as(s), s, reduce="amax", include_self=True)
+        p = torch.exp(s - smax[row])
+        den = torch.zeros((n, self.num_heads), device=s.device, dtype=s.dtype).index_add_(0, row, p)
+        return torch.zeros_like(x_row).index_add_(0, row, x_col[col] * (p / den[row])[:, :, None])   # empty row: 0
+
+
+class GATv2Conv_tiling(GATv2ConvDGL):
+    """Inference: forward(params, feat, fuse) -> (out[N, heads * out], elapsed_ms), timed like the other inference layers
+    (3 dry + 10 runs).  fuse: params = preprocess_CSR's (row_ptr, col_ind, val, smem); else params = A."""
+
+    def forward(self, params, feat, fuse=False):
+        from DFGNN.utils import benchmark
+        N = len(feat)
+        with torch.no_grad():   # (both branches time the convolution on the projected features)
+            if fuse:
+                row_ptr, col_ind, _, _ = params
+                x_row, x_col = (x.contiguous() for x in self.project(feat))
+                out, elapsed = benchmark(GATv2ConvFuse_inference, self.attn.detach(), row_ptr, col_ind, self.negative_slope,
+                                         x_row, x_col)
+            else:
+                out, elapsed = benchmark(self.conv_nofuse, params, *self.project(feat))
+        return out.reshape(N, -1), elapsed * 1000
+
+
+class GATv2Conv_forward(GATv2ConvDGL):
+    """Training: forward(params, feat, fuse) -> out[N, heads * out], differentiable in both branches.
+    params = preprocess_Hyper_fw_bw's (A, rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem)."""
+
+    def forward(self, params, feat, fuse=False):
+        A, _, row_ptr, col_ind, _, col_ptr, row_ind, _, _ = params
+        if fuse:
+            x_row, x_col = self.project(feat)
+            x_row = x_row.contiguous()
+            out = GATv2ConvFuse(self.attn, row_ptr, col_ind, col_ptr, row_ind, self.negative_slope, x_row,
+                                x_row if self.share_weights else x_col.contiguous())
+        else:
+            out = self.forward_nofuse(A, feat)
+        return out.reshape(len(feat), -1)

@@ -80,3 +80,33 @@ def GATConvFuse(attn_row, attn_col, row_ptr, col_ind, col_ptr, row_ind, permute,
     """reference :5-28"""
     return FusedGATFunction.apply(attn_row, attn_col, row_ptr, col_ind, col_ptr, row_ind, permute,
                                   negative_slope, in_feat, attn_drop)
+
+
+# ---- GATv2 (this build's addition; fused_gatconv.gatv2_*): logits a^T LeakyReLU(X_row[i] + X_col[j]) ---------------------
+def GATv2ConvFuse_inference(attn, row_ptr, col_ind, negative_slope, X_row, X_col):
+    """-> out[m, h, f]; attn fp32 [heads, feat], X_row / X_col fp32 [nodes, heads, feat] (the same tensor: shared weights)."""
+    return fused_gat.gatv2_inference(attn, row_ptr, col_ind, negative_slope, X_row, X_col)
+
+
+class FusedGATv2Function(torch.autograd.Function):
+    """Training pair: the forward saves its output and two floats per (row, head); the backward recomputes each edge from
+    the rows it gathers.  No floating-point tensor of nnz elements is created or kept."""
+
+    @staticmethod
+    def forward(ctx, attn, row_ptr, col_ind, col_ptr, row_ind, negative_slope, X_row, X_col):
+        out, row_max, row_sum = fused_gat.gatv2_forward(attn, row_ptr, col_ind, negative_slope, X_row, X_col)
+        ctx.save_for_backward(row_ptr, col_ind, col_ptr, row_ind, attn, X_row, X_col, out, row_max, row_sum)
+        ctx.negative_slope = negative_slope
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        row_ptr, col_ind, col_ptr, row_ind, attn, X_row, X_col, out, row_max, row_sum = ctx.saved_tensors
+        dX_row, dX_col, dattn = fused_gat.gatv2_backward(ctx.negative_slope, row_ptr, col_ind, col_ptr, row_ind, attn, X_row,
+                                                         X_col, out, row_max, row_sum, grad_out.contiguous())
+        # (one tensor passed as both X_row and X_col: autograd adds the two gradients)
+        return dattn, None, None, None, None, None, dX_row, dX_col
+
+
+def GATv2ConvFuse(attn, row_ptr, col_ind, col_ptr, row_ind, negative_slope, X_row, X_col):
+    return FusedGATv2Function.apply(attn, row_ptr, col_ind, col_ptr, row_ind, negative_slope, X_row, X_col)

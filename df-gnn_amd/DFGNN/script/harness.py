@@ -17,9 +17,11 @@ SWEEPS = {  # --format all: the variants this build serves out of the reference'
     ("batch", "gt"): ["csr", "softmax", "hyper"],
     ("batch", "gat"): ["csr", "softmax", "hyper_v2"],
     ("batch", "agnn"): ["csr", "softmax", "hyper"],
+    ("batch", "gatv2"): ["tiling"],
     ("full", "gt"): ["csr", "softmax", "hyper", "tiling"],
     ("full", "gat"): ["csr", "softmax", "hyper_v2", "tiling", "hyper_recompute"],
     ("full", "agnn"): ["csr", "softmax", "hyper", "tiling"],
+    ("full", "gatv2"): ["tiling"],
 }
 
 

@@ -253,6 +253,39 @@ int dfgnn_gt_bwd_rowstats(int m, int nnz, int h, int f, const int *row_ptr, cons
                                   as_stream(stream));
 }
 
+// ---- GATv2 (gatv2_train.hip): fused inference and training pair, any graph ------------------------------------------------
+int dfgnn_gatv2_bwd_ws_floats(int h, int f) {
+  if (h < 0 || f < 0) return kErrBadArg;
+  if (h > 65535) return kErrUnsupported;
+  const long long n = (long long)kGatv2Parts * (h > 0 ? h : 1) * (f > 0 ? f : 1);
+  return n > 0x7fffffffLL ? kErrUnsupported : (int)n;
+}
+
+int dfgnn_gatv2_fwd(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *attn,
+                    float negative_slope, const float *X_row, const float *X_col, float *row_max, float *row_sum,
+                    float *out, dfgnn_stream_t stream) {
+  if (int c = check_common(m, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (!attn || !X_row || !X_col || !out || (!row_max != !row_sum)) return kErrBadArg;  // (both statistics or neither)
+  const Csr g{m, nnz, h, f, row_ptr, col_ind, nullptr, nullptr};
+  return launch_gatv2_fwd(g, Gatv2Graph{nullptr, nullptr, attn, negative_slope}, X_row, X_col, row_max, row_sum, out,
+                          as_stream(stream));
+}
+
+int dfgnn_gatv2_bwd(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const int *col_ptr,
+                    const int *row_ind, const float *attn, float negative_slope, const float *X_row, const float *X_col,
+                    const float *out, const float *row_max, const float *row_sum, const float *grad_out, float *delta,
+                    float *ws, float *dX_row, float *dX_col, float *dattn, dfgnn_stream_t stream) {
+  if (int c = check_common(m, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (!attn || !X_row || !X_col || !out || !row_max || !row_sum || !grad_out || !delta || !ws || !dX_row || !dX_col ||
+      !dattn || !col_ptr || (nnz > 0 && !row_ind))
+    return kErrBadArg;
+  if (dX_row == dX_col) return kErrBadArg;  // (the two passes each write their buffer in full)
+  if (dfgnn_gatv2_bwd_ws_floats(h, f) < 0) return kErrUnsupported;
+  const Csr g{m, nnz, h, f, row_ptr, col_ind, nullptr, nullptr};
+  return launch_gatv2_bwd(g, Gatv2Graph{col_ptr, row_ind, attn, negative_slope}, X_row, X_col, out, row_max, row_sum,
+                          grad_out, delta, ws, dX_row, dX_col, dattn, as_stream(stream));
+}
+
 int dfgnn_gt_tiling_fwd(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
                         const float *Q, const float *K, const float *V, float *out, dfgnn_stream_t stream) {
   if (int c = check_common(m, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;

@@ -205,6 +205,20 @@ int launch_gt_train_bwd_rows(const Csr &g, const float *Q, const float *K, const
 int launch_gt_train_bwd_cols(const Csr &g, const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q,
                              const float *K, const float *V, const float *row_max, const float *row_sum,
                              const float *delta, const float *grad_out, float *dK, float *dV, hipStream_t s);
+// GATv2 pair (gatv2_train.hip): any graph, no plan.  The forward saves row_max / row_sum [m, h] (both nullable: inference);
+// the backward is the CSR pass (delta, dX_row and at most kGatv2Parts partial sums [h, f] of dattn -> ws), the CSC pass
+// (dX_col) and the reduction of the partials into dattn, on one stream.
+constexpr int kGatv2Parts = 2048;  // persistent workgroups of the CSR pass per head = partial sums of dattn
+struct Gatv2Graph {
+  const int *col_ptr, *row_ind;  // CSC (backward only)
+  const float *attn;             // [h, f]
+  float slope;
+};
+int launch_gatv2_fwd(const Csr &g, const Gatv2Graph &v, const float *X_row, const float *X_col, float *row_max,
+                     float *row_sum, float *out, hipStream_t s);
+int launch_gatv2_bwd(const Csr &g, const Gatv2Graph &v, const float *X_row, const float *X_col, const float *out,
+                     const float *row_max, const float *row_sum, const float *grad_out, float *delta, float *ws,
+                     float *dX_row, float *dX_col, float *dattn, hipStream_t s);
 // graphs with fewer than kBlockMinAvgDegree edges per row on average take the row-per-lane-group kernels
 inline bool low_degree(int m, int nnz) { return (long)nnz < (long)kBlockMinAvgDegree * m; }
 int launch_gat_hyper_fwd(const Csr &g, const float *attn_row, const float *attn_col, float slope,

@@ -402,6 +402,68 @@ std::vector<Tensor> gat_bwd(double slope, double attn_drop, const Tensor &row_pt
   return {grad_feat, grad_row, grad_col};
 }
 
+// ---- GATv2 (include/dfgnn.h: dfgnn_gatv2_fwd / dfgnn_gatv2_bwd): any graph, no plan ----------------------------------------
+// What both entry points check: X_row / X_col fp32 [nodes, heads, feat] of one shape, attn fp32 [heads, feat], the CSR arrays
+Dims gatv2_checks(const Tensor &attn, const Tensor &row_ptr, const Tensor &col_ind, const Tensor &X_row, const Tensor &X_col) {
+  check_i32(row_ptr, "row_ptr");
+  check_i32(col_ind, "col_ind");
+  check_feat3(X_row, X_row, "X_row");
+  check_feat3(X_col, X_row, "X_col");
+  check_f32(attn, "attn");
+  TORCH_CHECK(attn.dim() == 2 && attn.size(0) == X_row.size(1) && attn.size(1) == X_row.size(2), "attn must have shape (",
+              X_row.size(1), ", ", X_row.size(2), "), got ", attn.sizes());
+  TORCH_CHECK(row_ptr.dim() == 1 && col_ind.dim() == 1, "indptr / indices must be 1-D");
+  TORCH_CHECK(row_ptr.size(0) - 1 == X_row.size(0), "indptr describes ", row_ptr.size(0) - 1, " rows but features have ",
+              X_row.size(0), " nodes");
+  check_same_device(X_row, {&attn, &row_ptr, &col_ind, &X_col});
+  return Dims{(int)X_row.size(0), (int)col_ind.size(0), (int)X_row.size(1), (int)X_row.size(2)};
+}
+
+// save_stats = false: inference -> {out}; else the training forward -> {out, row_max, row_sum}
+std::vector<Tensor> gatv2_fwd(const Tensor &attn, const Tensor &row_ptr, const Tensor &col_ind, double slope, const Tensor &X_row,
+                              const Tensor &X_col, bool save_stats) {
+  const Dims d = gatv2_checks(attn, row_ptr, col_ind, X_row, X_col);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(X_row.device());
+  Tensor out = torch::empty_like(X_row);
+  Tensor row_max, row_sum;
+  if (save_stats) {
+    row_max = torch::empty({d.m, d.h}, X_row.options());
+    row_sum = torch::empty({d.m, d.h}, X_row.options());
+  }
+  check_rc(dfgnn_gatv2_fwd(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), f32(attn), (float)slope, f32(X_row), f32(X_col),
+                           f32(row_max), f32(row_sum), f32(out), cur_stream()),
+           save_stats ? "gatv2_forward" : "gatv2_inference");
+  if (!save_stats) return {out};
+  return {out, row_max, row_sum};
+}
+
+std::vector<Tensor> gatv2_bwd(double slope, const Tensor &row_ptr, const Tensor &col_ind, const Tensor &col_ptr, const Tensor &row_ind,
+                              const Tensor &attn, const Tensor &X_row, const Tensor &X_col, const Tensor &out, const Tensor &row_max,
+                              const Tensor &row_sum, const Tensor &grad) {
+  const Dims d = gatv2_checks(attn, row_ptr, col_ind, X_row, X_col);
+  check_i32(col_ptr, "col_ptr");
+  check_i32(row_ind, "row_ind");
+  check_edges(row_ind, d.nnz, "row_ind");
+  TORCH_CHECK(col_ptr.dim() == 1 && col_ptr.size(0) == d.m + 1, "col_ptr must have shape (", d.m + 1,
+              ",): the adjacency must be square");
+  check_feat3(out, X_row, "out");
+  check_feat3(grad, X_row, "grad");
+  row_stats_checks(d, X_row, row_max, row_sum);
+  check_same_device(X_row, {&col_ptr, &row_ind, &out, &grad});
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(X_row.device());
+  Tensor dX_row = torch::empty_like(X_row), dX_col = torch::empty_like(X_col);
+  if (d.m == 0) return {dX_row, dX_col, torch::zeros_like(attn)};  // (nothing to launch: no edge adds to dattn)
+  const int ws_floats = dfgnn_gatv2_bwd_ws_floats(d.h, d.f);
+  check_rc(ws_floats < 0 ? ws_floats : 0, "gatv2_backward");
+  Tensor delta = torch::empty({d.m, d.h}, X_row.options()), ws = torch::empty({(int64_t)ws_floats}, X_row.options());
+  Tensor dattn = torch::empty_like(attn);
+  check_rc(dfgnn_gatv2_bwd(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), i32(col_ptr), i32(row_ind), f32(attn), (float)slope,
+                           f32(X_row), f32(X_col), f32(out), f32(row_max), f32(row_sum), f32(grad), f32(delta), f32(ws),
+                           f32(dX_row), f32(dX_col), f32(dattn), cur_stream()),
+           "gatv2_backward");
+  return {dX_row, dX_col, dattn};
+}
+
 // fused_gtconv.cpp:244-276 (tiling), :174-242 (csr, csr_gm), :316-389 (softmax, softmax_gm): the GT inference variants that
 // take CSR (+ the COO rows for the two-kernel forms).  which: 0 tiling, 1 csr, 2 csr_gm, 3 softmax, 4 softmax_gm
 Tensor gt_variant_fwd(int64_t which, const Tensor &indptr, const Tensor &indices, const c10::optional<Tensor> &rows, const Tensor &val,
@@ -495,6 +557,8 @@ PYBIND11_MODULE(_dfgnn_ext, m) {
   m.def("gat_tiling_fwd", &gat_tiling_fwd, "fused GAT conv 'tiling' inference");
   m.def("gat_fwd_train", &gat_fwd_train, "fused GAT conv training forward (row statistics, attention dropout)");
   m.def("gat_bwd", &gat_bwd, "fused GAT conv backward");
+  m.def("gatv2_fwd", &gatv2_fwd, "fused GATv2 conv forward of any graph (inference, or training with row statistics)");
+  m.def("gatv2_bwd", &gatv2_bwd, "fused GATv2 conv backward of any graph from the forward's output and row statistics");
   m.def("gt_variant_fwd", &gt_variant_fwd, "fused GT conv inference: tiling / csr / csr_gm / softmax / softmax_gm");
   m.def("plan_build", &plan_build, "block plan of a CSR structure (dfgnn_plan_build)");
   m.def("preprocess_hyper", &preprocess_hyper, "COO -> CSR / COO rows / CSC on the GPU (dfgnn_preprocess_hyper)");

@@ -270,3 +270,61 @@ def gat_forward_tb(attn_row, attn_col, row_ptr, col_ind, negative_slope, in_feat
     check_family(in_feat, torch.int32, tile_scheduler=tile_scheduler)
     out, edge_max, edge_sum, _ = gat_forward(attn_row, attn_col, row_ptr, col_ind, negative_slope, in_feat, 0.0)
     return [out, edge_max, edge_sum]
+
+
+# ---- GATv2 (include/dfgnn.h: dfgnn_gatv2_fwd / dfgnn_gatv2_bwd; csrc/gatv2_train.hip) -----------------------------------
+# Not part of the reference's module.  The logit of edge (i, j) is sum_d attn[h, d] LeakyReLU(X_row[i, h, d] + X_col[j, h, d]):
+# not rank-one, so no per-node scores exist to hand over -- the operators take the attention vector and the two projected
+# feature tensors themselves.  Any graph, no plan, any f; nothing of size nnz is allocated.
+
+
+def _check_v2(attn, row_ptr, col_ind, X_row, X_col, **like_X):
+    """What every GATv2 operator checks: X_row / X_col (and `like_X`: out, grad) fp32 [nodes, heads, feat] of one shape,
+    attn fp32 [heads, feat], the CSR arrays of those nodes -> (m, nnz, h, f)."""
+    m, h, f = check_feats(X_row=X_row, X_col=X_col, **like_X)
+    check_2d(X_row, h, f, attn=attn)
+    return m, check_csr(X_row, m, row_ptr, col_ind), h, f
+
+
+def _gatv2_fwd(what, save_stats, attn, row_ptr, col_ind, negative_slope, X_row, X_col):
+    ext = _n.ext()
+    if ext is not None:
+        return ext.gatv2_fwd(attn, row_ptr, col_ind, float(negative_slope), X_row, X_col, save_stats)
+    m, nnz, h, f = _check_v2(attn, row_ptr, col_ind, X_row, X_col)
+    out = torch.empty_like(X_row)
+    row_max, row_sum = (_empty(X_row, m, h), _empty(X_row, m, h)) if save_stats else (None, None)
+    call("dfgnn_gatv2_fwd", what, X_row.device, m, nnz, h, f, row_ptr, col_ind, attn, float(negative_slope), X_row, X_col,
+         row_max, row_sum, out)
+    return [out, row_max, row_sum] if save_stats else [out]
+
+
+def gatv2_inference(attn, row_ptr, col_ind, negative_slope, X_row, X_col):
+    """-> out[m, h, f].  X_row and X_col may be the same tensor (shared weights)."""
+    return _gatv2_fwd("gatv2_inference", False, attn, row_ptr, col_ind, negative_slope, X_row, X_col)[0]
+
+
+def gatv2_forward(attn, row_ptr, col_ind, negative_slope, X_row, X_col):
+    """-> [out, row_max[m, h], row_sum[m, h]]: the training forward; the same `out` as gatv2_inference."""
+    return _gatv2_fwd("gatv2_forward", True, attn, row_ptr, col_ind, negative_slope, X_row, X_col)
+
+
+def gatv2_backward(negative_slope, row_ptr, col_ind, col_ptr, row_ind, attn, X_row, X_col, out, row_max, row_sum, grad):
+    """-> [dX_row, dX_col, dattn[h, f]] from the forward's output and row statistics (each edge is recomputed).  With
+    X_row is X_col the gradient of the shared tensor is dX_row + dX_col."""
+    ext = _n.ext()
+    if ext is not None:
+        return ext.gatv2_bwd(float(negative_slope), row_ptr, col_ind, col_ptr, row_ind, attn, X_row, X_col, out, row_max,
+                             row_sum, grad)
+    m, nnz, h, f = _check_v2(attn, row_ptr, col_ind, X_row, X_col, out=out, grad=grad)
+    check_csc(X_row, m, nnz, col_ptr, row_ind=row_ind)
+    check_2d(X_row, m, h, row_max=row_max, row_sum=row_sum)
+    dX_row, dX_col = torch.empty_like(X_row), torch.empty_like(X_col)
+    if m == 0:
+        return [dX_row, dX_col, torch.zeros_like(attn)]    # (nothing to launch: no edge adds to dattn)
+    ws_floats = int(_n.lib().dfgnn_gatv2_bwd_ws_floats(h, f))
+    if ws_floats < 0:
+        _n.check(ws_floats, "gatv2_backward")
+    delta, ws, dattn = _empty(X_row, m, h), _empty(X_row, ws_floats), torch.empty_like(attn)
+    call("dfgnn_gatv2_bwd", "gatv2_backward", X_row.device, m, nnz, h, f, row_ptr, col_ind, col_ptr, row_ind, attn,
+         float(negative_slope), X_row, X_col, out, row_max, row_sum, grad, delta, ws, dX_row, dX_col, dattn)
+    return [dX_row, dX_col, dattn]

@@ -182,6 +182,38 @@ int dfgnn_gt_bwd_rowstats(int m, int nnz, int h, int f, const int *row_ptr, cons
                           const float *V, const float *out, const float *row_max, const float *row_sum,
                           const float *grad_out, float *delta, float *dQ, float *dK, float *dV, dfgnn_stream_t stream);
 
+/* GATv2 convolution (csrc/gatv2_train.hip): fused inference and training pair for ANY graph, no plan, no degree limit,
+ * any f.  The logit of edge (i, j) is neither rank-one (dfgnn_gat_*) nor a dot product (dfgnn_gt_*):
+ *   z_e = X_row[i,h,:] + X_col[j,h,:],  s_e = sum_d attn[h,d] lrelu(z_e[d]),  lrelu(x) = x > 0 ? x : negative_slope x
+ *   P_e = exp(s_e - row_max_i) / row_sum_i,  out[i,h,:] = sum_e P_e X_col[j,h,:]
+ * so a formulation with index ops materialises z[nnz, h, f]; here nothing of size nnz exists.  The neighbour row
+ * X_col[j] is both the logit operand and the message: the lane-group form of the forward gathers it once per edge.
+ * Saved between forward and backward: row_max, row_sum fp32[m, h] (empty row: out = 0, row_max = -1e38, row_sum = 0), as
+ * for dfgnn_gt_fwd_rowstats.  The backward, given the forward's `out`, rebuilds each edge in a CSR pass and a CSC pass:
+ *   delta_i = <grad_out_i, out_i>,  dS_e = P_e (<grad_out_i, X_col_j> - delta_i),
+ *   g_e[d] = dS_e attn[h,d] (z_e[d] > 0 ? 1 : negative_slope)     (at z == 0 the derivative is negative_slope, as in torch)
+ *   dX_row[i] = sum_{e of row i} g_e            dX_col[j] = sum_{e into j} (P_e grad_out_i + g_e)
+ *   dattn[h,d] = sum_{all e} dS_e lrelu(z_e[d])
+ * dattn is a sum over every edge: the CSR pass runs a bounded number of persistent workgroups, each keeps its share in
+ * registers over all the rows it walks and stores ONE partial [h, f] into `ws`; a small kernel in the same call sums the
+ * partials in a fixed order.  No atomics: every output is written in full by plain stores and is deterministic.
+ *   attn     fp32[h, f]
+ *   X_row, X_col  fp32[m, h, f]; may be the same pointer (shared weights).  dX_row and dX_col are distinct buffers
+ *   row_max = row_sum = NULL in the forward: nothing is saved (inference); otherwise both are set
+ *   delta    caller scratch fp32[m, h], written by the CSR pass and read by the CSC pass
+ *   ws       caller scratch of dfgnn_gatv2_bwd_ws_floats(h, f) floats (independent of m and nnz), 16-byte aligned for
+ *            the float4 path
+ * dfgnn_gatv2_bwd_ws_floats: > 0 = the number of floats; < 0 = a DFGNN_E_* code (negative size: BADARG; h > 65535 or a
+ * size that does not fit an int: UNSUPPORTED, as dfgnn_gatv2_bwd then answers too). */
+int dfgnn_gatv2_bwd_ws_floats(int h, int f);
+int dfgnn_gatv2_fwd(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *attn,
+                    float negative_slope, const float *X_row, const float *X_col, float *row_max, float *row_sum,
+                    float *out, dfgnn_stream_t stream);
+int dfgnn_gatv2_bwd(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const int *col_ptr,
+                    const int *row_ind, const float *attn, float negative_slope, const float *X_row, const float *X_col,
+                    const float *out, const float *row_max, const float *row_sum, const float *grad_out, float *delta,
+                    float *ws, float *dX_row, float *dX_col, float *dattn, dfgnn_stream_t stream);
+
 /* weights[256 i + c] = val[e] for the edge e from node i to the c-th node of i's range of the plan, 0 elsewhere:
  * dfgnn_plan_dense_weights_floats(m) = 256 m floats (device, 16-byte aligned), written by one memset + one kernel on
  * `stream`.  val: fp32[nnz] in CSR order.  Only the dense ranges of the plan are filled (dfgnn_gt_stats_applies == 1:
