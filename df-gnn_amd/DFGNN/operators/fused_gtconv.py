@@ -102,6 +102,43 @@ def GTConvFuse_rowstats(rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, 
         rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V)
 
 
+class FusedGTFunction_bias(torch.autograd.Function):
+    """FusedGTFunction_rowstats with a per-edge, per-head additive attention bias (include/dfgnn.h: dfgnn_gt_fwd_bias /
+    dfgnn_gt_bwd_bias, csrc/gt_bias_train.hip): s_e = val_e <Q_i, K_j> + bias[h, e], bias fp32[h, nnz] in CSR edge order,
+    -inf masks an edge.  Saved between forward and backward: Q, K, V, bias, out, the row statistics and the graph arrays
+    (`val` only when it is not all ones).  dbias[h, nnz] is computed only when the bias requires a gradient; otherwise the
+    backward allocates and writes nothing of size h nnz."""
+
+    @staticmethod
+    def forward(ctx, rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V, bias):
+        out_feat, row_max, row_sum = fused_gt.gt_forward_bias(row_ptr, col_ind, val, bias, Q, K, V)
+        keep_val = () if fused_gt.val_ptr(val) is None else (val,)
+        ctx.save_for_backward(row_ptr, col_ind, col_ptr, row_ind, val_idx, Q, K, V, bias, out_feat, row_max, row_sum,
+                              *keep_val)
+        return out_feat
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        row_ptr, col_ind, col_ptr, row_ind, val_idx, Q, K, V, bias, out_feat, row_max, row_sum, *val = ctx.saved_tensors
+        val = val[0] if val else None
+        grad_Q, grad_K, grad_V, grad_bias = fused_gt.gt_backward_bias(
+            row_ptr, col_ind, val, bias, col_ptr, row_ind, val_idx, Q, K, V, out_feat, row_max, row_sum,
+            grad_out.contiguous(), need_dbias=ctx.needs_input_grad[11])
+        return (None,) * 8 + (grad_Q, grad_K, grad_V, grad_bias)
+
+
+def GTConvFuse_bias(rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V, bias):
+    """Differentiable conv of any graph with the additive attention bias fp32[h, nnz] (CSR edge order); the argument list
+    of GTConvFuse_rowstats plus `bias` (`rows` and `smem_consume` are accepted and not used)."""
+    return FusedGTFunction_bias.apply(
+        rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V, bias)
+
+
+def GTConvFuse_inference_bias(row_ptr, col_ind, val, Q, K, V, bias):
+    """Inference of any graph with the additive attention bias fp32[h, nnz] (CSR edge order)."""
+    return fused_gt.gt_inference_bias(row_ptr, col_ind, val, bias, Q, K, V)
+
+
 def GTConvFuse_inference_softmax(indptr, indices, rows, val, smem_consume, Q, K, V):
     """softmax: two kernels (COO SDDMM, then softmax + SpMM).  reference :238-259"""
     return fused_gt.gt_softmax_inference(indptr, indices, rows, val, smem_consume, Q, K, V)[0]

@@ -253,6 +253,34 @@ int dfgnn_gt_bwd_rowstats(int m, int nnz, int h, int f, const int *row_ptr, cons
                                   as_stream(stream));
 }
 
+// ---- the general statistics pair with a per-edge additive attention bias (gt_bias_train.hip) ------------------------------
+int dfgnn_gt_fwd_bias(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                      const float *bias, const float *Q, const float *K, const float *V, float *row_max, float *row_sum,
+                      float *out, dfgnn_stream_t stream) {
+  if (int c = check_common(m, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (!Q || !K || !V || !out || (!row_max != !row_sum)) return kErrBadArg;  // (both statistics or neither: inference)
+  if (nnz > 0 && !bias) return kErrBadArg;
+  const Csr g{m, nnz, h, f, row_ptr, col_ind, nullptr, val};
+  return launch_gt_bias_fwd(g, bias, Q, K, V, row_max, row_sum, out, as_stream(stream));
+}
+
+int dfgnn_gt_bwd_bias(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                      const float *bias, const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q,
+                      const float *K, const float *V, const float *out, const float *row_max, const float *row_sum,
+                      const float *grad_out, float *delta, float *dQ, float *dK, float *dV, float *dbias,
+                      dfgnn_stream_t stream) {
+  if (int c = check_common(m, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (!Q || !K || !V || !out || !row_max || !row_sum || !grad_out || !delta || !dQ || !dK || !dV || !col_ptr)
+    return kErrBadArg;
+  if (nnz > 0 && (!bias || !row_ind || !val_idx)) return kErrBadArg;  // (the CSC pass finds an entry's bias through val_idx)
+  const Csr g{m, nnz, h, f, row_ptr, col_ind, nullptr, val};
+  if (int rc = launch_gt_bias_bwd_rows(g, bias, Q, K, V, out, row_max, row_sum, grad_out, delta, dQ, dbias,
+                                       as_stream(stream)))
+    return rc;
+  return launch_gt_bias_bwd_cols(g, bias, col_ptr, row_ind, val_idx, Q, K, V, row_max, row_sum, delta, grad_out, dK, dV,
+                                 as_stream(stream));
+}
+
 // ---- GATv2 (gatv2_train.hip): fused inference and training pair, any graph ------------------------------------------------
 int dfgnn_gatv2_bwd_ws_floats(int h, int f) {
   if (h < 0 || f < 0) return kErrBadArg;

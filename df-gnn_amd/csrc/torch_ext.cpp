@@ -241,6 +241,59 @@ std::vector<Tensor> gt_bwd_rowstats(const Tensor &row_ptr, const Tensor &col_ind
   return {dQ, dK, dV};
 }
 
+// ---- the general pair with a per-edge additive attention bias (include/dfgnn.h: dfgnn_gt_fwd_bias / dfgnn_gt_bwd_bias) ----
+// bias: fp32 [h, nnz] in CSR edge order
+void bias_checks(const Dims &d, const Tensor &ref, const Tensor &bias) {
+  check_f32(bias, "bias");
+  TORCH_CHECK(bias.dim() == 2 && bias.size(0) == d.h && bias.size(1) == d.nnz, "bias must have shape (", d.h, ", ", d.nnz,
+              "), got ", bias.sizes());
+  check_same_device(ref, {&bias});
+}
+
+// save_stats = false: inference (-> {out})
+std::vector<Tensor> gt_fwd_bias(const Tensor &row_ptr, const Tensor &col_ind, const c10::optional<Tensor> &val, const Tensor &bias,
+                                const Tensor &Q, const Tensor &K, const Tensor &V, bool unit_val, bool save_stats) {
+  const Dims d = gt_checks(row_ptr, col_ind, nullptr, opt(val), Q, K, V);
+  bias_checks(d, Q, bias);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
+  Tensor out = torch::empty_like(Q);
+  Tensor row_max, row_sum;
+  if (save_stats) {
+    row_max = torch::empty({d.m, d.h}, Q.options());
+    row_sum = torch::empty({d.m, d.h}, Q.options());
+  }
+  check_rc(dfgnn_gt_fwd_bias(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), edge_val_ptr(val, unit_val), f32(bias), f32(Q),
+                             f32(K), f32(V), f32(row_max), f32(row_sum), f32(out), cur_stream()),
+           save_stats ? "gt_forward_bias" : "gt_inference_bias");
+  if (!save_stats) return {out};
+  return {out, row_max, row_sum};
+}
+
+// -> {dQ, dK, dV, dbias}, or {dQ, dK, dV} without need_dbias
+std::vector<Tensor> gt_bwd_bias(const Tensor &row_ptr, const Tensor &col_ind, const c10::optional<Tensor> &val, const Tensor &bias,
+                                const Tensor &col_ptr, const Tensor &row_ind, const Tensor &val_idx, const Tensor &Q,
+                                const Tensor &K, const Tensor &V, const Tensor &out, const Tensor &row_max,
+                                const Tensor &row_sum, const Tensor &grad, bool unit_val, bool need_dbias) {
+  const Dims d = gt_checks(row_ptr, col_ind, nullptr, opt(val), Q, K, V);
+  bias_checks(d, Q, bias);
+  csc_checks(d, Q, col_ptr, row_ind, val_idx);
+  check_feat3(out, Q, "out");
+  check_feat3(grad, Q, "grad");
+  row_stats_checks(d, Q, row_max, row_sum);
+  check_same_device(Q, {&out, &grad});
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
+  Tensor delta = torch::empty({d.m, d.h}, Q.options());
+  Tensor dQ = torch::empty_like(Q), dK = torch::empty_like(K), dV = torch::empty_like(V);
+  Tensor dbias;
+  if (need_dbias) dbias = torch::empty({d.h, d.nnz}, Q.options());
+  check_rc(dfgnn_gt_bwd_bias(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), edge_val_ptr(val, unit_val), f32(bias),
+                             i32(col_ptr), i32(row_ind), i32(val_idx), f32(Q), f32(K), f32(V), f32(out), f32(row_max),
+                             f32(row_sum), f32(grad), f32(delta), f32(dQ), f32(dK), f32(dV), f32(dbias), cur_stream()),
+           "gt_backward_bias");
+  if (!need_dbias) return {dQ, dK, dV};
+  return {dQ, dK, dV, dbias};
+}
+
 // ---- the attn_edge pair in rank order (include/dfgnn.h: dfgnn_gt_hyper_fwd_ranked / dfgnn_gt_bwd_ranked) ----------------
 std::vector<Tensor> gt_hyper_fwd_ranked(const Tensor &row_ptr, const Tensor &col_ind, const Tensor &Q, const Tensor &K,
                                         const Tensor &V, int64_t plan, int64_t meta) {
@@ -549,6 +602,8 @@ PYBIND11_MODULE(_dfgnn_ext, m) {
   m.def("gt_bwd_stats", &gt_bwd_stats, "fused GT conv backward from the row statistics");
   m.def("gt_fwd_rowstats", &gt_fwd_rowstats, "fused GT conv training forward of any graph, row statistics instead of attn_edge");
   m.def("gt_bwd_rowstats", &gt_bwd_rowstats, "fused GT conv backward of any graph from the forward's output and row statistics");
+  m.def("gt_fwd_bias", &gt_fwd_bias, "fused GT conv forward of any graph with a per-edge additive attention bias");
+  m.def("gt_bwd_bias", &gt_bwd_bias, "fused GT conv backward of any graph with a per-edge additive attention bias");
   m.def("gt_hyper_fwd_ranked", &gt_hyper_fwd_ranked, "fused GT conv 'hyper' training forward, attention values in rank order");
   m.def("gt_bwd_ranked", &gt_bwd_ranked, "fused GT conv backward from rank-ordered attention values");
   m.def("plan_dense_weights", &plan_dense_weights, "edge values of a plan's dense ranges in dense form (dfgnn_plan_dense_weights)");

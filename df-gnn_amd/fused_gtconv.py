@@ -305,6 +305,62 @@ def gt_backward_rowstats(row_ptr, col_ind, val, col_ptr, row_ind, val_idx, Q, K,
     return [dQ, dK, dV]
 
 
+# ---- the general pair with a per-edge additive attention bias (include/dfgnn.h: dfgnn_gt_fwd_bias / dfgnn_gt_bwd_bias) ---
+# Not part of the reference's module.  The pair above with s_e = val_e <Q_i, K_j> + bias[h, e] (csrc/gt_bias_train.hip):
+# bias is fp32[h, nnz] in CSR edge order, -inf masks an edge.  DFGNN.operators.fused_gtconv.GTConvFuse_bias takes it.
+
+
+def _check_bias(Q, h, nnz, bias):
+    check_2d(Q, h, nnz, bias=bias)
+
+
+def _forward_bias(what, save_stats, row_ptr, col_ind, val, bias, Q, K, V):
+    ext = _n.ext()
+    if ext is not None:
+        return ext.gt_fwd_bias(row_ptr, col_ind, val, bias, Q, K, V, val_ptr(val) is None, save_stats)
+    m, nnz, h, f = _checks(row_ptr, col_ind, Q, K, V, val=val)
+    _check_bias(Q, h, nnz, bias)
+    out = torch.empty_like(Q)
+    row_max, row_sum = (_empty(Q, m, h), _empty(Q, m, h)) if save_stats else (None, None)
+    call("dfgnn_gt_fwd_bias", what, Q.device, m, nnz, h, f, row_ptr, col_ind, val_ptr(val), bias, Q, K, V, row_max, row_sum,
+         out)
+    return [out, row_max, row_sum] if save_stats else [out]
+
+
+def gt_inference_bias(row_ptr, col_ind, val, bias, Q, K, V):
+    """-> out: inference of any graph with the additive bias fp32[h, nnz] (CSR order; -inf masks an edge).
+    val: edge values fp32[nnz] in CSR order; None or all ones: unit values."""
+    return _forward_bias("gt_inference_bias", False, row_ptr, col_ind, val, bias, Q, K, V)[0]
+
+
+def gt_forward_bias(row_ptr, col_ind, val, bias, Q, K, V):
+    """-> [out, row_max[m, h], row_sum[m, h]]: the training forward; a (row, head) without an unmasked edge has out = 0,
+    row_max = -1e38, row_sum = 0."""
+    return _forward_bias("gt_forward_bias", True, row_ptr, col_ind, val, bias, Q, K, V)
+
+
+def gt_backward_bias(row_ptr, col_ind, val, bias, col_ptr, row_ind, val_idx, Q, K, V, out, row_max, row_sum, grad,
+                     need_dbias=True):
+    """-> [dQ, dK, dV, dbias[h, nnz]] from the forward's output and row statistics; dbias is None without need_dbias (then
+    nothing of size h nnz is allocated or written)."""
+    val_idx = as_int32(val_idx)
+    ext = _n.ext()
+    if ext is not None:
+        res = ext.gt_bwd_bias(row_ptr, col_ind, val, bias, col_ptr, row_ind, val_idx, Q, K, V, out, row_max, row_sum, grad,
+                              val_ptr(val) is None, need_dbias)
+        return res if need_dbias else res + [None]
+    m, nnz, h, f = _checks(row_ptr, col_ind, Q, K, V, val=val, out=out, grad=grad)
+    _check_bias(Q, h, nnz, bias)
+    check_csc(Q, m, nnz, col_ptr, row_ind=row_ind, val_idx=val_idx)
+    check_2d(Q, m, h, row_max=row_max, row_sum=row_sum)
+    delta = _empty(Q, m, h)
+    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
+    dbias = _empty(Q, h, nnz) if need_dbias else None
+    call("dfgnn_gt_bwd_bias", "gt_backward_bias", Q.device, m, nnz, h, f, row_ptr, col_ind, val_ptr(val), bias, col_ptr,
+         row_ind, val_idx, Q, K, V, out, row_max, row_sum, grad, delta, dQ, dK, dV, dbias)
+    return [dQ, dK, dV, dbias]
+
+
 # ---- the CSR-taking inference variants ----------------------------------------------------------------------------------
 _VARIANTS = ("gt_tiling", "gt_csr", "gt_csr_gm", "gt_softmax", "gt_softmax_gm")   # by `which` of torch_ext.cpp: gt_variant_fwd
 

@@ -182,6 +182,31 @@ int dfgnn_gt_bwd_rowstats(int m, int nnz, int h, int f, const int *row_ptr, cons
                           const float *V, const float *out, const float *row_max, const float *row_sum,
                           const float *grad_out, float *delta, float *dQ, float *dK, float *dV, dfgnn_stream_t stream);
 
+/* The pair above with a per-edge, per-head ADDITIVE attention bias (csrc/gt_bias_train.hip): any graph, no plan, any f.
+ *   s_e = val_e <Q_i, K_j> + bias[h, e],  P_e = exp(s_e - row_max_i) / row_sum_i,  out_i = sum_e P_e V_j
+ *   delta_i = <grad_out_i, out_i>,  dS_e = P_e (<grad_out_i, V_j> - delta_i)
+ *   dQ_i = sum dS_e val_e K_j,  dK_j = sum dS_e val_e Q_i,  dV_j = sum P_e grad_out_i,  dbias[h, e] = dS_e
+ * (Graphormer's spatial / edge encodings, GraphGPS / GRIT-style attention, relative positional and edge-type biases.)
+ *   bias     fp32[h, nnz] in CSR edge order (the layout of attn_edge); required when nnz > 0.  -inf masks an edge: P_e = 0,
+ *            dbias_e = 0, nothing added to any sum; a (row, head) whose edges are all masked is an empty row (out = 0,
+ *            row_max = -1e38, row_sum = 0, dQ = 0).  No output holds a NaN or an inf.  +inf and NaN in bias are the
+ *            caller's error
+ *   dbias    fp32[h, nnz], every slot written by plain stores (no pre-zeroing), or NULL: the bias needs no gradient and
+ *            nothing of size h nnz is written
+ *   val      fp32[nnz], CSR order, NULL = unit values
+ *   val_idx  required when nnz > 0 (also for unit values): the CSC pass finds an entry's bias through it
+ *   row_max = row_sum = NULL in the forward: nothing is saved (inference)
+ * Everything else as dfgnn_gt_fwd_rowstats / dfgnn_gt_bwd_rowstats: delta is caller scratch fp32[m, h]; dQ, dK, dV are
+ * written in full; no atomics, the sums are deterministic; the same two forms by average degree. */
+int dfgnn_gt_fwd_bias(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                      const float *bias, const float *Q, const float *K, const float *V, float *row_max, float *row_sum,
+                      float *out, dfgnn_stream_t stream);
+int dfgnn_gt_bwd_bias(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                      const float *bias, const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q,
+                      const float *K, const float *V, const float *out, const float *row_max, const float *row_sum,
+                      const float *grad_out, float *delta, float *dQ, float *dK, float *dV, float *dbias,
+                      dfgnn_stream_t stream);
+
 /* GATv2 convolution (csrc/gatv2_train.hip): fused inference and training pair for ANY graph, no plan, no degree limit,
  * any f.  The logit of edge (i, j) is neither rank-one (dfgnn_gat_*) nor a dot product (dfgnn_gt_*):
  *   z_e = X_row[i,h,:] + X_col[j,h,:],  s_e = sum_d attn[h,d] lrelu(z_e[d]),  lrelu(x) = x > 0 ? x : negative_slope x
