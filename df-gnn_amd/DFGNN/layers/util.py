@@ -21,8 +21,8 @@ from .GAT_DOT import DOTGATConv_csr, DOTGATConv_hyper, DOTGATConv_softmax
 from .GAT import (GATConv_dgNN, GATConv_hyper, GATConv_hyper_ablation, GATConv_hyper_recompute, GATConv_hyper_v2,
                   GATConv_softmax, GATConv_softmax_gm, GATConv_tiling)
 from .GATv2 import GATv2Conv_forward, GATv2Conv_tiling
-from .GT import (SparseMHA_bias_timing, SparseMHA_CSR, SparseMHA_CSR_GM, SparseMHA_forward_timing, SparseMHA_hyper,
-                 SparseMHA_rowstats_timing, SparseMHA_softmax, SparseMHA_softmax_gm, SparseMHA_tiling)
+from .GT import (SparseMHA_bias_timing, SparseMHA_CSR, SparseMHA_CSR_GM, SparseMHA_edge_timing, SparseMHA_forward_timing,
+                 SparseMHA_hyper, SparseMHA_rowstats_timing, SparseMHA_softmax, SparseMHA_softmax_gm, SparseMHA_tiling)
 
 WARP_SIZE = 32  # only used by the smem_consume formula kept from the reference
 
@@ -106,6 +106,7 @@ _GT_LAYERS = {
     "forward": SparseMHA_forward_timing,
     "forward_rowstats": SparseMHA_rowstats_timing,  # this build's addition: row statistics instead of attn_edge, any graph
     "forward_bias": SparseMHA_bias_timing,  # this build's addition: a per-edge additive attention bias (seeded random here)
+    "forward_edge": SparseMHA_edge_timing,  # this build's addition: per-edge feature vectors in keys and values (seeded random here)
     "hyper_ablation": SparseMHA_hyper,  # reference :385-386 (ablation entry; served by the production kernel)
 }
 _GAT_LAYERS = {
@@ -179,6 +180,6 @@ def load_prepfunc(args):
         return preprocess_Hyper
     if args.format in ("softmax", "softmax_gm"):
         return preprocess_softmax
-    if args.format in ("forward", "forward_rowstats", "forward_bias"):
+    if args.format in ("forward", "forward_rowstats", "forward_bias", "forward_edge"):
         return preprocess_Hyper_fw_bw
     raise ValueError(f"Unsupported format {args.format}")

@@ -139,6 +139,43 @@ def GTConvFuse_inference_bias(row_ptr, col_ind, val, Q, K, V, bias):
     return fused_gt.gt_inference_bias(row_ptr, col_ind, val, bias, Q, K, V)
 
 
+class FusedGTFunction_edge(torch.autograd.Function):
+    """FusedGTFunction_rowstats with a per-edge feature vector added to keys and values (include/dfgnn.h: dfgnn_gt_fwd_edge /
+    dfgnn_gt_bwd_edge, csrc/gt_edge_train.hip): k~_e = K_j + E_e, v~_e = V_j + E_e, E fp32[nnz, h, f] in CSR edge order.
+    Saved between forward and backward: Q, K, V, E, out, the row statistics and the graph arrays (`val` only when it is not
+    all ones) -- nothing of size nnz h f beyond E itself.  dE[nnz, h, f] is computed only when E requires a gradient;
+    otherwise the backward allocates and writes nothing of that size."""
+
+    @staticmethod
+    def forward(ctx, rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V, E):
+        out_feat, row_max, row_sum = fused_gt.gt_forward_edge(row_ptr, col_ind, val, E, Q, K, V)
+        keep_val = () if fused_gt.val_ptr(val) is None else (val,)
+        ctx.save_for_backward(row_ptr, col_ind, col_ptr, row_ind, val_idx, Q, K, V, E, out_feat, row_max, row_sum,
+                              *keep_val)
+        return out_feat
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        row_ptr, col_ind, col_ptr, row_ind, val_idx, Q, K, V, E, out_feat, row_max, row_sum, *val = ctx.saved_tensors
+        val = val[0] if val else None
+        grad_Q, grad_K, grad_V, grad_E = fused_gt.gt_backward_edge(
+            row_ptr, col_ind, val, E, col_ptr, row_ind, val_idx, Q, K, V, out_feat, row_max, row_sum,
+            grad_out.contiguous(), need_dE=ctx.needs_input_grad[11])
+        return (None,) * 8 + (grad_Q, grad_K, grad_V, grad_E)
+
+
+def GTConvFuse_edge(rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V, E):
+    """Differentiable conv of any graph with the edge features fp32[nnz, h, f] (CSR edge order) added to keys and values;
+    the argument list of GTConvFuse_rowstats plus `E` (`rows` and `smem_consume` are accepted and not used)."""
+    return FusedGTFunction_edge.apply(
+        rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V, E)
+
+
+def GTConvFuse_inference_edge(row_ptr, col_ind, val, Q, K, V, E):
+    """Inference of any graph with the edge features fp32[nnz, h, f] (CSR edge order) added to keys and values."""
+    return fused_gt.gt_inference_edge(row_ptr, col_ind, val, E, Q, K, V)
+
+
 def GTConvFuse_inference_softmax(indptr, indices, rows, val, smem_consume, Q, K, V):
     """softmax: two kernels (COO SDDMM, then softmax + SpMM).  reference :238-259"""
     return fused_gt.gt_softmax_inference(indptr, indices, rows, val, smem_consume, Q, K, V)[0]

@@ -81,6 +81,11 @@ def check_2d(ref, n, h, **tensors):
     _family(ref, torch.float32, (n, h), tensors)
 
 
+def check_3d(ref, n, h, f, **tensors):
+    """fp32 arrays [n, h, f]: per-edge feature vectors (n = nnz)."""
+    _family(ref, torch.float32, (n, h, f), tensors)
+
+
 def stream_ptr(device):
     return torch.cuda.current_stream(device).cuda_stream
 

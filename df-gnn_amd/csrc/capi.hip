@@ -281,6 +281,33 @@ int dfgnn_gt_bwd_bias(int m, int nnz, int h, int f, const int *row_ptr, const in
                                  as_stream(stream));
 }
 
+// ---- the general statistics pair with a per-edge feature vector in keys and values (gt_edge_train.hip) --------------------
+int dfgnn_gt_fwd_edge(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                      const float *E, const float *Q, const float *K, const float *V, float *row_max, float *row_sum,
+                      float *out, dfgnn_stream_t stream) {
+  if (int c = check_common(m, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (!Q || !K || !V || !out || (!row_max != !row_sum)) return kErrBadArg;  // (both statistics or neither: inference)
+  if (nnz > 0 && !E) return kErrBadArg;
+  const Csr g{m, nnz, h, f, row_ptr, col_ind, nullptr, val};
+  return launch_gt_edge_fwd(g, E, Q, K, V, row_max, row_sum, out, as_stream(stream));
+}
+
+int dfgnn_gt_bwd_edge(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                      const float *E, const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q,
+                      const float *K, const float *V, const float *out, const float *row_max, const float *row_sum,
+                      const float *grad_out, float *delta, float *dQ, float *dK, float *dV, float *dE,
+                      dfgnn_stream_t stream) {
+  if (int c = check_common(m, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (!Q || !K || !V || !out || !row_max || !row_sum || !grad_out || !delta || !dQ || !dK || !dV || !col_ptr)
+    return kErrBadArg;
+  if (nnz > 0 && (!E || !row_ind || !val_idx)) return kErrBadArg;  // (the CSC pass finds an entry's E row through val_idx)
+  const Csr g{m, nnz, h, f, row_ptr, col_ind, nullptr, val};
+  if (int rc = launch_gt_edge_bwd_rows(g, E, Q, K, V, out, row_max, row_sum, grad_out, delta, dQ, dE, as_stream(stream)))
+    return rc;
+  return launch_gt_edge_bwd_cols(g, E, col_ptr, row_ind, val_idx, Q, K, V, row_max, row_sum, delta, grad_out, dK, dV,
+                                 as_stream(stream));
+}
+
 // ---- GATv2 (gatv2_train.hip): fused inference and training pair, any graph ------------------------------------------------
 int dfgnn_gatv2_bwd_ws_floats(int h, int f) {
   if (h < 0 || f < 0) return kErrBadArg;

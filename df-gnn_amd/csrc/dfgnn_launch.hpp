@@ -216,6 +216,17 @@ int launch_gt_bias_bwd_rows(const Csr &g, const float *bias, const float *Q, con
 int launch_gt_bias_bwd_cols(const Csr &g, const float *bias, const int *col_ptr, const int *row_ind, const int *val_idx,
                             const float *Q, const float *K, const float *V, const float *row_max, const float *row_sum,
                             const float *delta, const float *grad_out, float *dK, float *dV, hipStream_t s);
+// GT pair with a per-edge feature vector added to keys and values (gt_edge_train.hip): launch_gt_train_* with E [nnz, h, f]
+// (CSR order), k~_e = K_j + E_e, v~_e = V_j + E_e.  The CSR pass also writes dE [nnz, h, f] in full when it is not null; the
+// CSC pass gathers E rows through val_idx, which it therefore always reads.
+int launch_gt_edge_fwd(const Csr &g, const float *E, const float *Q, const float *K, const float *V, float *row_max,
+                       float *row_sum, float *out, hipStream_t s);
+int launch_gt_edge_bwd_rows(const Csr &g, const float *E, const float *Q, const float *K, const float *V,
+                            const float *out, const float *row_max, const float *row_sum, const float *grad_out,
+                            float *delta, float *dQ, float *dE, hipStream_t s);
+int launch_gt_edge_bwd_cols(const Csr &g, const float *E, const int *col_ptr, const int *row_ind, const int *val_idx,
+                            const float *Q, const float *K, const float *V, const float *row_max, const float *row_sum,
+                            const float *delta, const float *grad_out, float *dK, float *dV, hipStream_t s);
 // GATv2 pair (gatv2_train.hip): any graph, no plan.  The forward saves row_max / row_sum [m, h] (both nullable: inference);
 // the backward is the CSR pass (delta, dX_row and at most kGatv2Parts partial sums [h, f] of dattn -> ws), the CSC pass
 // (dX_col) and the reduction of the partials into dattn, on one stream.

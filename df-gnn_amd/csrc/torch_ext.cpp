@@ -294,6 +294,59 @@ std::vector<Tensor> gt_bwd_bias(const Tensor &row_ptr, const Tensor &col_ind, co
   return {dQ, dK, dV, dbias};
 }
 
+// ---- the general pair with a per-edge feature vector in keys and values (include/dfgnn.h: dfgnn_gt_fwd_edge / dfgnn_gt_bwd_edge) ----
+// E: fp32 [nnz, h, f] in CSR edge order
+void edge_feat_checks(const Dims &d, const Tensor &ref, const Tensor &E) {
+  check_f32(E, "E");
+  TORCH_CHECK(E.dim() == 3 && E.size(0) == d.nnz && E.size(1) == d.h && E.size(2) == d.f, "E must have shape (", d.nnz, ", ",
+              d.h, ", ", d.f, "), got ", E.sizes());
+  check_same_device(ref, {&E});
+}
+
+// save_stats = false: inference (-> {out})
+std::vector<Tensor> gt_fwd_edge(const Tensor &row_ptr, const Tensor &col_ind, const c10::optional<Tensor> &val, const Tensor &E,
+                                const Tensor &Q, const Tensor &K, const Tensor &V, bool unit_val, bool save_stats) {
+  const Dims d = gt_checks(row_ptr, col_ind, nullptr, opt(val), Q, K, V);
+  edge_feat_checks(d, Q, E);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
+  Tensor out = torch::empty_like(Q);
+  Tensor row_max, row_sum;
+  if (save_stats) {
+    row_max = torch::empty({d.m, d.h}, Q.options());
+    row_sum = torch::empty({d.m, d.h}, Q.options());
+  }
+  check_rc(dfgnn_gt_fwd_edge(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), edge_val_ptr(val, unit_val), f32(E), f32(Q),
+                             f32(K), f32(V), f32(row_max), f32(row_sum), f32(out), cur_stream()),
+           save_stats ? "gt_forward_edge" : "gt_inference_edge");
+  if (!save_stats) return {out};
+  return {out, row_max, row_sum};
+}
+
+// -> {dQ, dK, dV, dE}, or {dQ, dK, dV} without need_dE
+std::vector<Tensor> gt_bwd_edge(const Tensor &row_ptr, const Tensor &col_ind, const c10::optional<Tensor> &val, const Tensor &E,
+                                const Tensor &col_ptr, const Tensor &row_ind, const Tensor &val_idx, const Tensor &Q,
+                                const Tensor &K, const Tensor &V, const Tensor &out, const Tensor &row_max,
+                                const Tensor &row_sum, const Tensor &grad, bool unit_val, bool need_dE) {
+  const Dims d = gt_checks(row_ptr, col_ind, nullptr, opt(val), Q, K, V);
+  edge_feat_checks(d, Q, E);
+  csc_checks(d, Q, col_ptr, row_ind, val_idx);
+  check_feat3(out, Q, "out");
+  check_feat3(grad, Q, "grad");
+  row_stats_checks(d, Q, row_max, row_sum);
+  check_same_device(Q, {&out, &grad});
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
+  Tensor delta = torch::empty({d.m, d.h}, Q.options());
+  Tensor dQ = torch::empty_like(Q), dK = torch::empty_like(K), dV = torch::empty_like(V);
+  Tensor dE;
+  if (need_dE) dE = torch::empty_like(E);
+  check_rc(dfgnn_gt_bwd_edge(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), edge_val_ptr(val, unit_val), f32(E),
+                             i32(col_ptr), i32(row_ind), i32(val_idx), f32(Q), f32(K), f32(V), f32(out), f32(row_max),
+                             f32(row_sum), f32(grad), f32(delta), f32(dQ), f32(dK), f32(dV), f32(dE), cur_stream()),
+           "gt_backward_edge");
+  if (!need_dE) return {dQ, dK, dV};
+  return {dQ, dK, dV, dE};
+}
+
 // ---- the attn_edge pair in rank order (include/dfgnn.h: dfgnn_gt_hyper_fwd_ranked / dfgnn_gt_bwd_ranked) ----------------
 std::vector<Tensor> gt_hyper_fwd_ranked(const Tensor &row_ptr, const Tensor &col_ind, const Tensor &Q, const Tensor &K,
                                         const Tensor &V, int64_t plan, int64_t meta) {
@@ -604,6 +657,8 @@ PYBIND11_MODULE(_dfgnn_ext, m) {
   m.def("gt_bwd_rowstats", &gt_bwd_rowstats, "fused GT conv backward of any graph from the forward's output and row statistics");
   m.def("gt_fwd_bias", &gt_fwd_bias, "fused GT conv forward of any graph with a per-edge additive attention bias");
   m.def("gt_bwd_bias", &gt_bwd_bias, "fused GT conv backward of any graph with a per-edge additive attention bias");
+  m.def("gt_fwd_edge", &gt_fwd_edge, "fused GT conv forward of any graph with a per-edge feature vector in keys and values");
+  m.def("gt_bwd_edge", &gt_bwd_edge, "fused GT conv backward of any graph with a per-edge feature vector in keys and values");
   m.def("gt_hyper_fwd_ranked", &gt_hyper_fwd_ranked, "fused GT conv 'hyper' training forward, attention values in rank order");
   m.def("gt_bwd_ranked", &gt_bwd_ranked, "fused GT conv backward from rank-ordered attention values");
   m.def("plan_dense_weights", &plan_dense_weights, "edge values of a plan's dense ranges in dense form (dfgnn_plan_dense_weights)");

@@ -32,6 +32,8 @@ SIGNATURES = {
     "dfgnn_gt_bwd_rowstats": [_i, _i, _i, _i] + [_vp] * 18,
     "dfgnn_gt_fwd_bias": [_i, _i, _i, _i] + [_vp] * 11,
     "dfgnn_gt_bwd_bias": [_i, _i, _i, _i] + [_vp] * 20,
+    "dfgnn_gt_fwd_edge": [_i, _i, _i, _i] + [_vp] * 11,
+    "dfgnn_gt_bwd_edge": [_i, _i, _i, _i] + [_vp] * 20,
     "dfgnn_gatv2_bwd_ws_floats": [_i, _i],
     "dfgnn_gatv2_fwd": [_i, _i, _i, _i] + [_vp] * 3 + [_f] + [_vp] * 6,
     "dfgnn_gatv2_bwd": [_i, _i, _i, _i] + [_vp] * 5 + [_f] + [_vp] * 12,

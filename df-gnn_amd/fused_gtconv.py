@@ -15,7 +15,7 @@ import torch
 import dfgnn_native as _n
 import os
 
-from _binding_util import (as_int32, call, check_2d, check_csc, check_csr, check_edges, check_family, check_feats,
+from _binding_util import (as_int32, call, check_2d, check_3d, check_csc, check_csr, check_edges, check_family, check_feats,
                            get_plan_obj, plan_dense_weights, plan_ptrs, val_ptr)
 
 # Set to False to force the general (plan-less) kernels; results are identical either way.
@@ -359,6 +359,61 @@ def gt_backward_bias(row_ptr, col_ind, val, bias, col_ptr, row_ind, val_idx, Q, 
     call("dfgnn_gt_bwd_bias", "gt_backward_bias", Q.device, m, nnz, h, f, row_ptr, col_ind, val_ptr(val), bias, col_ptr,
          row_ind, val_idx, Q, K, V, out, row_max, row_sum, grad, delta, dQ, dK, dV, dbias)
     return [dQ, dK, dV, dbias]
+
+
+# ---- the general pair with a per-edge feature vector in keys and values (include/dfgnn.h: dfgnn_gt_fwd_edge / _bwd_edge) ---
+# Not part of the reference's module.  The row-statistics pair with k~_e = K_j + E_e, v~_e = V_j + E_e (csrc/gt_edge_train.hip):
+# E is fp32[nnz, h, f] in CSR edge order.  DFGNN.operators.fused_gtconv.GTConvFuse_edge takes it.
+
+
+def _check_edge_feat(Q, nnz, h, f, E):
+    check_3d(Q, nnz, h, f, E=E)
+
+
+def _forward_edge(what, save_stats, row_ptr, col_ind, val, E, Q, K, V):
+    ext = _n.ext()
+    if ext is not None:
+        return ext.gt_fwd_edge(row_ptr, col_ind, val, E, Q, K, V, val_ptr(val) is None, save_stats)
+    m, nnz, h, f = _checks(row_ptr, col_ind, Q, K, V, val=val)
+    _check_edge_feat(Q, nnz, h, f, E)
+    out = torch.empty_like(Q)
+    row_max, row_sum = (_empty(Q, m, h), _empty(Q, m, h)) if save_stats else (None, None)
+    call("dfgnn_gt_fwd_edge", what, Q.device, m, nnz, h, f, row_ptr, col_ind, val_ptr(val), E, Q, K, V, row_max, row_sum, out)
+    return [out, row_max, row_sum] if save_stats else [out]
+
+
+def gt_inference_edge(row_ptr, col_ind, val, E, Q, K, V):
+    """-> out: inference of any graph with the edge features fp32[nnz, h, f] (CSR order) added to keys and values.
+    val: edge values fp32[nnz] in CSR order; None or all ones: unit values."""
+    return _forward_edge("gt_inference_edge", False, row_ptr, col_ind, val, E, Q, K, V)[0]
+
+
+def gt_forward_edge(row_ptr, col_ind, val, E, Q, K, V):
+    """-> [out, row_max[m, h], row_sum[m, h]]: the training forward; an empty row has out = 0, row_max = -1e38,
+    row_sum = 0."""
+    return _forward_edge("gt_forward_edge", True, row_ptr, col_ind, val, E, Q, K, V)
+
+
+def gt_backward_edge(row_ptr, col_ind, val, E, col_ptr, row_ind, val_idx, Q, K, V, out, row_max, row_sum, grad,
+                     need_dE=True):
+    """-> [dQ, dK, dV, dE[nnz, h, f]] from the forward's output and row statistics; dE is None without need_dE (then
+    nothing of size nnz h f is allocated or written)."""
+    val_idx = as_int32(val_idx)
+    ext = _n.ext()
+    if ext is not None:
+        res = ext.gt_bwd_edge(row_ptr, col_ind, val, E, col_ptr, row_ind, val_idx, Q, K, V, out, row_max, row_sum, grad,
+                              val_ptr(val) is None, need_dE)
+        return res if need_dE else res + [None]
+    m, nnz, h, f = _checks(row_ptr, col_ind, Q, K, V, val=val, out=out, grad=grad)
+    _check_edge_feat(Q, nnz, h, f, E)
+    check_csc(Q, m, nnz, col_ptr, row_ind=row_ind, val_idx=val_idx)
+    check_2d(Q, m, h, row_max=row_max, row_sum=row_sum)
+    delta = _empty(Q, m, h)
+    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
+    dE = torch.empty_like(E) if need_dE else None
+    call("dfgnn_gt_bwd_edge", "gt_backward_edge", Q.device, m, nnz, h, f, row_ptr, col_ind, val_ptr(val), E, col_ptr,
+         row_ind, val_idx, Q, K, V, out, row_max, row_sum, grad, delta, dQ, dK, dV, dE)
+    return [dQ, dK, dV, dE]
 
 
 # ---- the CSR-taking inference variants ----------------------------------------------------------------------------------

@@ -207,6 +207,33 @@ int dfgnn_gt_bwd_bias(int m, int nnz, int h, int f, const int *row_ptr, const in
                       const float *grad_out, float *delta, float *dQ, float *dK, float *dV, float *dbias,
                       dfgnn_stream_t stream);
 
+/* The general statistics pair with a per-edge FEATURE VECTOR added to keys and values (csrc/gt_edge_train.hip): any graph,
+ * no plan, any f.  Edge e = (i, j) carries E_e in R^f per head; one E serves key and value (PyG's TransformerConv(edge_dim),
+ * Shaw-style relative position vectors, the edge channel of GPS / GRIT-type models):
+ *   k~_e = K_j + E_e,  v~_e = V_j + E_e
+ *   s_e = val_e <Q_i, k~_e>,  P_e = exp(s_e - row_max_i) / row_sum_i,  out_i = sum_e P_e v~_e
+ *   delta_i = <grad_out_i, out_i>,  dS_e = P_e (<grad_out_i, v~_e> - delta_i)
+ *   dQ_i = sum dS_e val_e k~_e,  dK_j = sum dS_e val_e Q_i,  dV_j = sum P_e grad_out_i
+ *   dE_e = dS_e val_e Q_i + P_e grad_out_i
+ *   E        fp32[nnz, h, f] in CSR edge order (the feature layout with the edge in place of the node: the row of
+ *            (edge e, head) starts at (e h + head) f); required when nnz > 0.  Duplicate edges each have their own row
+ *   dE       fp32[nnz, h, f], every slot written by plain stores (no pre-zeroing), or NULL: E needs no gradient and nothing
+ *            of size nnz h f is written
+ *   val      fp32[nnz], CSR order, NULL = unit values
+ *   val_idx  required when nnz > 0 (also for unit values): the CSC pass finds an entry's E row through it
+ *   row_max = row_sum = NULL in the forward: nothing is saved (inference)
+ * An empty row has out = 0, row_max = -1e38, row_sum = 0, dQ = 0.  Everything else as dfgnn_gt_fwd_rowstats /
+ * dfgnn_gt_bwd_rowstats: delta is caller scratch fp32[m, h]; dQ, dK, dV are written in full; no atomics, the sums are
+ * deterministic; the same two forms by average degree; nothing allocates or synchronises (capturable in a HIP graph). */
+int dfgnn_gt_fwd_edge(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                      const float *E, const float *Q, const float *K, const float *V, float *row_max, float *row_sum,
+                      float *out, dfgnn_stream_t stream);
+int dfgnn_gt_bwd_edge(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                      const float *E, const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q,
+                      const float *K, const float *V, const float *out, const float *row_max, const float *row_sum,
+                      const float *grad_out, float *delta, float *dQ, float *dK, float *dV, float *dE,
+                      dfgnn_stream_t stream);
+
 /* GATv2 convolution (csrc/gatv2_train.hip): fused inference and training pair for ANY graph, no plan, no degree limit,
  * any f.  The logit of edge (i, j) is neither rank-one (dfgnn_gat_*) nor a dot product (dfgnn_gt_*):
  *   z_e = X_row[i,h,:] + X_col[j,h,:],  s_e = sum_d attn[h,d] lrelu(z_e[d]),  lrelu(x) = x > 0 ? x : negative_slope x
