@@ -34,7 +34,13 @@ class GATv2ConvDGL(nn.Module):
         nn.init.xavier_normal_(self.attn, gain=gain)
 
     def project(self, feat):
-        """-> X_row, X_col [N, heads, out]; the same tensor when the weights are shared."""
+        """-> X_row, X_col [N, heads, out]; the same tensor when the weights are shared.  feat may be a pair (feat_cols,
+        feat_rows) -- the two node sets of a rectangular graph: X_col [n_cols, heads, out] is projected from the first member,
+        X_row [m, heads, out] from the second."""
+        if isinstance(feat, (tuple, list)):
+            feat_cols, feat_rows = feat
+            return (self.fc_row(feat_rows).view(-1, self.num_heads, self.out_size),
+                    self.fc_col(feat_cols).view(-1, self.num_heads, self.out_size))
         x_row = self.fc_row(feat).view(-1, self.num_heads, self.out_size)
         return x_row, (x_row if self.share_weights else self.fc_col(feat).view(-1, self.num_heads, self.out_size))
 
@@ -73,15 +79,17 @@ class GATv2Conv_tiling(GATv2ConvDGL):
 
 class GATv2Conv_forward(GATv2ConvDGL):
     """Training: forward(params, feat, fuse) -> out[N, heads * out], differentiable in both branches.
-    params = preprocess_Hyper_fw_bw's (A, rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem)."""
+    params = preprocess_Hyper_fw_bw's (A, rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem); on a rectangular
+    graph preprocess_block's, with feat = (feat_cols, feat_rows) -> out[m, heads * out]."""
 
     def forward(self, params, feat, fuse=False):
         A, _, row_ptr, col_ind, _, col_ptr, row_ind, _, _ = params
         if fuse:
             x_row, x_col = self.project(feat)
+            shared = x_col is x_row
             x_row = x_row.contiguous()
             out = GATv2ConvFuse(self.attn, row_ptr, col_ind, col_ptr, row_ind, self.negative_slope, x_row,
-                                x_row if self.share_weights else x_col.contiguous())
+                                x_row if shared else x_col.contiguous())
         else:
             out = self.forward_nofuse(A, feat)
-        return out.reshape(len(feat), -1)
+        return out.reshape(out.size(0), -1)

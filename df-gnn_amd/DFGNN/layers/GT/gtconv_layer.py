@@ -6,6 +6,15 @@ import torch.nn as nn
 from DFGNN.utils import sparse as dglsp
 
 
+def split_pair(h):
+    """Node features as a layer takes them -> (h_cols, h_rows, is_pair): one tensor serves both sides of a square graph; a
+    pair (h_cols, h_rows) -- PyG's (x_src, x_dst), the input and the output nodes of a sampled block -- feeds keys / values
+    from its first member and queries from its second."""
+    if isinstance(h, (tuple, list)):
+        return h[0], h[1], True
+    return h, h, False
+
+
 class SparseMHA(nn.Module):
     """Sparse multi-head attention: out = softmax_rows((Q K^T) * A) V."""
 
@@ -20,11 +29,11 @@ class SparseMHA(nn.Module):
         self.v_proj = nn.Linear(in_size, out_size)
 
     def prep_qkv(self, h):
-        """[N, head_dim, heads] layout (inference path), q pre-scaled.  reference :19-27"""
-        N = len(h)
-        q = self.q_proj(h).reshape(N, self.head_dim, self.num_heads) * self.scaling
-        k = self.k_proj(h).reshape(N, self.head_dim, self.num_heads)
-        v = self.v_proj(h).reshape(N, self.head_dim, self.num_heads)
+        """[N, head_dim, heads] layout (inference path), q pre-scaled.  reference :19-27.  h may be a pair (split_pair)."""
+        h_cols, h_rows, _ = split_pair(h)
+        q = self.q_proj(h_rows).reshape(len(h_rows), self.head_dim, self.num_heads) * self.scaling
+        k = self.k_proj(h_cols).reshape(len(h_cols), self.head_dim, self.num_heads)
+        v = self.v_proj(h_cols).reshape(len(h_cols), self.head_dim, self.num_heads)
         return q, k, v
 
     def forward_dglsp(self, A, q, k, v):

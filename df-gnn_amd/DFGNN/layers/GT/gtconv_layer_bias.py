@@ -11,12 +11,14 @@ import torch
 from DFGNN.operators.fused_gtconv import GTConvFuse_bias, GTConvFuse_inference_bias
 from DFGNN.utils import benchmark
 
+from .gtconv_layer import split_pair
 from .gtconv_layer_forward import _TrainingQKV
 
 
 def index_ops_mha_bias(rows, col_ind, val, q, k, v, edge_bias):
-    """softmax_rows(val_e <q_i, k_j> + edge_bias[e]) v_j with torch index ops.  q, k, v: [N, heads, d]; edge_bias:
-    [nnz, heads]; rows / col_ind: the edge list in CSR order.  Materialises [nnz, heads] logits and probabilities."""
+    """softmax_rows(val_e <q_i, k_j> + edge_bias[e]) v_j with torch index ops.  q: [N, heads, d]; k, v: [N, heads, d] (on a
+    rectangular graph [n_cols, heads, d]); edge_bias: [nnz, heads]; rows / col_ind: the edge list in CSR order.
+    Materialises [nnz, heads] logits and probabilities."""
     rows, cols = rows.long(), col_ind.long()
     s = (q[rows] * k[cols]).sum(-1) * val.to(q.dtype)[:, None] + edge_bias                    # [nnz, heads]
     mx = torch.full((q.size(0), s.size(1)), float("-inf"), dtype=s.dtype, device=s.device)
@@ -25,13 +27,15 @@ def index_ops_mha_bias(rows, col_ind, val, q, k, v, edge_bias):
     p = torch.exp(s - mx[rows])
     den = torch.zeros_like(mx).index_add_(0, rows, p)
     attn = p / torch.where(den > 0, den, torch.ones_like(den))[rows]
-    return torch.zeros_like(v).index_add_(0, rows, v[cols] * attn[:, :, None])
+    return v.new_zeros((q.size(0),) + tuple(v.shape[1:])).index_add_(0, rows, v[cols] * attn[:, :, None])
 
 
 class SparseMHA_bias(_TrainingQKV):
     def forward(self, params, h, edge_bias, fuse=False):
-        """edge_bias: [nnz, heads] in CSR edge order -- what Linear(edge_dim, heads)(edge_attr) yields."""
+        """edge_bias: [nnz, heads] in CSR edge order -- what Linear(edge_dim, heads)(edge_attr) yields.  h: [N, in] or, on a
+        rectangular graph (preprocess_block), the pair (h_cols, h_rows) -> [len(h_rows), out]."""
         A, rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume = params
+        h_rows = split_pair(h)[1]
         q, k, v = self._qkv_fused(h)
         if fuse:
             bias = edge_bias.t().contiguous()            # [heads, nnz]: a 64-edge tile of one head is one coalesced load
@@ -42,7 +46,7 @@ class SparseMHA_bias(_TrainingQKV):
                 out = GTConvFuse_inference_bias(row_ptr, col_ind, val, q, k, v, bias)
         else:
             out = index_ops_mha_bias(rows, col_ind, val, q, k, v, edge_bias)
-        return out.reshape(len(h), -1)
+        return out.reshape(len(h_rows), -1)
 
 
 class SparseMHA_bias_timing(_TrainingQKV):

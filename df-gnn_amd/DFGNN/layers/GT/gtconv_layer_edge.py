@@ -12,6 +12,7 @@ from torch import nn
 from DFGNN.operators.fused_gtconv import GTConvFuse_edge, GTConvFuse_inference_edge
 from DFGNN.utils import benchmark
 
+from .gtconv_layer import split_pair
 from .gtconv_layer_forward import _TrainingQKV
 
 
@@ -27,7 +28,7 @@ def index_ops_mha_edge(rows, col_ind, val, q, k, v, e):
     p = torch.exp(s - mx[rows])
     den = torch.zeros_like(mx).index_add_(0, rows, p)
     attn = p / den[rows]
-    return torch.zeros_like(v).index_add_(0, rows, ve * attn[:, :, None])
+    return v.new_zeros((q.size(0),) + tuple(v.shape[1:])).index_add_(0, rows, ve * attn[:, :, None])   # (k, v may have n_cols rows)
 
 
 class SparseMHA_edge(_TrainingQKV):
@@ -39,8 +40,10 @@ class SparseMHA_edge(_TrainingQKV):
         self.lin_edge = nn.Linear(in_size if edge_dim is None else edge_dim, out_size, bias=False)
 
     def forward(self, params, h, edge_attr, fuse=False):
-        """edge_attr: [nnz, edge_dim] in CSR edge order."""
+        """edge_attr: [nnz, edge_dim] in CSR edge order.  h: [N, in] or, on a rectangular graph (preprocess_block), the pair
+        (h_cols, h_rows) -> [len(h_rows), out]."""
         A, rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume = params
+        h_rows = split_pair(h)[1]
         q, k, v = self._qkv_fused(h)
         e = self.lin_edge(edge_attr).view(-1, self.num_heads, self.head_dim)
         if fuse:
@@ -51,7 +54,7 @@ class SparseMHA_edge(_TrainingQKV):
                 out = GTConvFuse_inference_edge(row_ptr, col_ind, val, q, k, v, e)
         else:
             out = index_ops_mha_edge(rows, col_ind, val, q, k, v, e)
-        return out.reshape(len(h), -1)
+        return out.reshape(len(h_rows), -1)
 
 
 class SparseMHA_edge_timing(_TrainingQKV):

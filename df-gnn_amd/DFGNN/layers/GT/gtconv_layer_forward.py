@@ -7,15 +7,17 @@ params = (A, rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consum
 from DFGNN.operators.fused_gtconv import GTConvFuse_hyper, GTConvFuse_inference_hyper
 from DFGNN.utils import benchmark
 
-from .gtconv_layer import SparseMHA
+from .gtconv_layer import SparseMHA, split_pair
 
 
 class _TrainingQKV(SparseMHA):
     def _qkv_fused(self, h):
-        N = len(h)
-        q = self.q_proj(h).reshape(N, self.num_heads, self.head_dim) * self.scaling
-        k = self.k_proj(h).reshape(N, self.num_heads, self.head_dim)
-        v = self.v_proj(h).reshape(N, self.num_heads, self.head_dim)
+        """[N, heads, head_dim] layout, q pre-scaled.  h may be a pair (h_cols, h_rows): K and V are projected from the
+        first member, Q from the second (the layers on the pairs that take a rectangular graph)."""
+        h_cols, h_rows, _ = split_pair(h)
+        q = self.q_proj(h_rows).reshape(len(h_rows), self.num_heads, self.head_dim) * self.scaling
+        k = self.k_proj(h_cols).reshape(len(h_cols), self.num_heads, self.head_dim)
+        v = self.v_proj(h_cols).reshape(len(h_cols), self.num_heads, self.head_dim)
         return q, k, v
 
 

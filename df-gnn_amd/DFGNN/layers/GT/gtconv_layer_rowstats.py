@@ -6,15 +6,18 @@ params = (A, rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consum
 from DFGNN.operators.fused_gtconv import GTConvFuse_inference_hyper, GTConvFuse_rowstats
 from DFGNN.utils import benchmark
 
+from .gtconv_layer import split_pair
 from .gtconv_layer_forward import _TrainingQKV
 
 
 class SparseMHA_rowstats(_TrainingQKV):
     def forward(self, params, h, fuse=False):
+        """h: [N, in] or, on a rectangular graph (preprocess_block), the pair (h_cols, h_rows) -> [len(h_rows), out]."""
         A, rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume = params
+        _, h_rows, pair = split_pair(h)
         if fuse:
             q, k, v = self._qkv_fused(h)
-            if self.training:
+            if self.training or pair:   # (the 'hyper' inference operator below is square-only)
                 out = GTConvFuse_rowstats(rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume,
                                           q.contiguous(), k.contiguous(), v.contiguous())
             else:
@@ -22,7 +25,7 @@ class SparseMHA_rowstats(_TrainingQKV):
                                                  k.contiguous(), v.contiguous())
         else:
             out = self.forward_dglsp(A, *self.prep_qkv(h))
-        return out.reshape(len(h), -1)
+        return out.reshape(len(h_rows), -1)
 
 
 class SparseMHA_rowstats_timing(_TrainingQKV):

@@ -100,6 +100,28 @@ def preprocess_Hyper_fw_bw(g, fused=True):
             _round_up(max_neigh * 8, WARP_SIZE))
 
 
+def preprocess_block(block, fused=True):
+    """preprocess_Hyper_fw_bw for a rectangular graph (DFGNN.utils.graph.Block: num_rows x num_cols, edges() = (row, column)
+    ids): the same 9-tuple, with A of shape (rows, cols), row_ptr of rows + 1 and col_ptr of cols + 1 entries -- what the
+    layers on the pairs that take a rectangular graph (SparseMHA_rowstats / _bias / _edge, GATv2Conv_forward) expect next to
+    a pair of node features (h_cols, h_rows)."""
+    shape = (block.num_rows(), block.num_cols())
+    A, max_neigh = dglsp.spmatrix(torch.stack(block.edges()), shape=shape), 128
+    if not fused:
+        return A, None, None, None, None, None, None, None, None
+    if A.row.is_cuda:
+        import dfgnn_preprocess
+        row_ptr, col_ind, rows, _, col_ptr, row_ind, val_idx = dfgnn_preprocess.coo_to_hyper(A.row, A.col, shape, csc=True)
+        return (A, rows, row_ptr, col_ind, _unit_val(A.nnz, A.device), col_ptr, row_ind, val_idx,
+                _round_up(max_neigh * 8, WARP_SIZE))
+    rows = torch.sort(A.row.int()).values
+    row_ptr, col_ind, val = _csr_parts(A)
+    A_csr = dglsp.from_csr(indptr=row_ptr, indices=col_ind, val=val, shape=A.shape)
+    col_ptr, row_ind, val_idx = A_csr.csc()
+    return (A, rows, row_ptr, col_ind, val, col_ptr.int(), row_ind.int(), val_idx.int(),
+            _round_up(max_neigh * 8, WARP_SIZE))
+
+
 _GT_LAYERS = {
     "csr": SparseMHA_CSR, "csr_gm": SparseMHA_CSR_GM, "tiling": SparseMHA_tiling, "hyper": SparseMHA_hyper,
     "nofuse": SparseMHA_hyper, "softmax": SparseMHA_softmax, "softmax_gm": SparseMHA_softmax_gm,

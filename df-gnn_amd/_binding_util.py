@@ -53,6 +53,21 @@ def check_feats(**tensors):
     return tuple(ref.shape)
 
 
+def check_cols(rows_name, rows, **tensors):
+    """The column side of a pair that takes an m x n_cols graph (K / V, GATv2's X_col): fp32 [n_cols, heads, feat] tensors
+    of one shape with the heads and features of the row side `rows` (Q, X_row) -> n_cols."""
+    name, first = next(iter(tensors.items()))
+    _family(rows, torch.float32, None, {name: first})
+    if first.dim() != 3 or first.shape[1:] != rows.shape[1:]:
+        raise RuntimeError(f"{name} must have shape (n_cols, {rows.shape[1]}, {rows.shape[2]}): the heads and features of "
+                           f"{rows_name}, got {tuple(first.shape)}")
+    for other, t in list(tensors.items())[1:]:
+        _family(rows, torch.float32, None, {other: t})
+        if t.shape != first.shape:
+            raise RuntimeError(f"{other} must have shape {tuple(first.shape)} like {name}, got {tuple(t.shape)}")
+    return first.shape[0]
+
+
 def check_csr(ref, m, indptr, indices):
     """The int32 CSR arrays of a graph whose `m` rows are the nodes of the feature tensors -> nnz."""
     _family(ref, torch.int32, None, {"indptr": indptr, "indices": indices})
@@ -69,6 +84,15 @@ def check_csc(ref, m, nnz, col_ptr, **per_edge):
     if col_ptr.shape != (m + 1,):
         raise RuntimeError(f"col_ptr must have shape ({m + 1},): the adjacency must be square")
     _family(ref, torch.int32, (nnz,), per_edge)
+
+
+def check_csc_rect(ref, n_cols, nnz, col_ptr, cols_name, **per_edge):
+    """check_csc for an m x n_cols graph: col_ptr has one entry per column -- per row of K / V (X_col) -- and one more."""
+    _family(ref, torch.int32, None, {"col_ptr": col_ptr})
+    _family(ref, torch.int32, (nnz,), per_edge)
+    if col_ptr.shape != (n_cols + 1,):
+        raise RuntimeError(f"col_ptr must have shape ({n_cols + 1},): one entry for each of the {n_cols} rows of {cols_name} "
+                           "and one more")
 
 
 def check_edges(ref, nnz, dtype, **tensors):

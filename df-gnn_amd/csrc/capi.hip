@@ -64,6 +64,22 @@ inline int check_common(int m, int nnz, int h, int f, const void *row_ptr, const
   if (h > 65535) return kErrUnsupported;
   return 0;
 }
+
+// check_common for an m x n_cols graph.  Nothing to do at all: no heads, no features, or neither rows nor columns.
+inline int check_rect(int m, int n_cols, int nnz, int h, int f, const void *row_ptr, const void *col_ind) {
+  if (m < 0 || n_cols < 0 || nnz < 0 || h < 0 || f < 0) return kErrBadArg;
+  if ((m == 0 && n_cols == 0) || h == 0 || f == 0) return 1;
+  if (nnz > 0 && (m == 0 || n_cols == 0)) return kErrBadArg;  // (an edge needs a row and a column)
+  if (m > 0 && !row_ptr) return kErrBadArg;
+  if (nnz > 0 && !col_ind) return kErrBadArg;
+  if (h > 65535) return kErrUnsupported;
+  return 0;
+}
+inline Csr rect_csr(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val) {
+  Csr g{m, nnz, h, f, row_ptr, col_ind, nullptr, val};
+  g.n_cols = n_cols;
+  return g;
+}
 }  // namespace
 
 extern "C" {
@@ -228,52 +244,80 @@ int dfgnn_gt_bwd_ranked(int m, int nnz, int h, int f, const int *row_ptr, const 
   return launch_gt_dense_bwd(g, p, Q, K, V, attn_ranked, grad_out, dQ, dK, dV, as_stream(stream), true);
 }
 
+// ---- the four pairs that take an m x n_cols graph (rows: queries / outputs, columns: keys / values) -----------------------
+// Each has a *_rect entry with both extents; the entry of the square adjacency is that one with n_cols = m.  A pass whose
+// extent is 0 launches nothing (dfgnn_launch.hpp), so: without rows the backward still zeroes dK / dV in full (every column
+// is empty), without columns the forward writes out = 0 and the sentinels and the backward dQ = 0.  An array of an empty
+// side may be NULL.
+
 // ---- the general statistics pair (gt_train.hip): any graph, no plan, nothing of size nnz saved or parked ----------------
-int dfgnn_gt_fwd_rowstats(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
-                          const float *Q, const float *K, const float *V, float *row_max, float *row_sum, float *out,
-                          dfgnn_stream_t stream) {
-  if (int c = check_common(m, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
-  if (!Q || !K || !V || !out || (!row_max != !row_sum)) return kErrBadArg;  // (both statistics or neither: inference)
-  const Csr g{m, nnz, h, f, row_ptr, col_ind, nullptr, val};
+int dfgnn_gt_fwd_rowstats_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind,
+                               const float *val, const float *Q, const float *K, const float *V, float *row_max,
+                               float *row_sum, float *out, dfgnn_stream_t stream) {
+  if (int c = check_rect(m, n_cols, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (m == 0) return 0;  // (no row: nothing to write)
+  if (!Q || !out || (n_cols > 0 && (!K || !V)) || (!row_max != !row_sum)) return kErrBadArg;  // (both statistics or neither: inference)
+  const Csr g = rect_csr(m, n_cols, nnz, h, f, row_ptr, col_ind, val);
   return launch_gt_train_fwd(g, Q, K, V, row_max, row_sum, out, as_stream(stream));
 }
 
-int dfgnn_gt_bwd_rowstats(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
-                          const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q, const float *K,
-                          const float *V, const float *out, const float *row_max, const float *row_sum,
-                          const float *grad_out, float *delta, float *dQ, float *dK, float *dV, dfgnn_stream_t stream) {
-  if (int c = check_common(m, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
-  if (!Q || !K || !V || !out || !row_max || !row_sum || !grad_out || !delta || !dQ || !dK || !dV || !col_ptr)
-    return kErrBadArg;
+int dfgnn_gt_fwd_rowstats(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                          const float *Q, const float *K, const float *V, float *row_max, float *row_sum, float *out,
+                          dfgnn_stream_t stream) {
+  return dfgnn_gt_fwd_rowstats_rect(m, m, nnz, h, f, row_ptr, col_ind, val, Q, K, V, row_max, row_sum, out, stream);
+}
+
+int dfgnn_gt_bwd_rowstats_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind,
+                               const float *val, const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q,
+                               const float *K, const float *V, const float *out, const float *row_max, const float *row_sum,
+                               const float *grad_out, float *delta, float *dQ, float *dK, float *dV, dfgnn_stream_t stream) {
+  if (int c = check_rect(m, n_cols, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (m > 0 && (!Q || !out || !row_max || !row_sum || !grad_out || !delta || !dQ)) return kErrBadArg;
+  if (n_cols > 0 && (!K || !V || !dK || !dV || !col_ptr)) return kErrBadArg;
   if (nnz > 0 && (!row_ind || (val && !val_idx))) return kErrBadArg;  // (unit values never read val_idx)
-  const Csr g{m, nnz, h, f, row_ptr, col_ind, nullptr, val};
+  const Csr g = rect_csr(m, n_cols, nnz, h, f, row_ptr, col_ind, val);
   if (int rc = launch_gt_train_bwd_rows(g, Q, K, V, out, row_max, row_sum, grad_out, delta, dQ, as_stream(stream)))
     return rc;
   return launch_gt_train_bwd_cols(g, col_ptr, row_ind, val_idx, Q, K, V, row_max, row_sum, delta, grad_out, dK, dV,
                                   as_stream(stream));
 }
 
+int dfgnn_gt_bwd_rowstats(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                          const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q, const float *K,
+                          const float *V, const float *out, const float *row_max, const float *row_sum,
+                          const float *grad_out, float *delta, float *dQ, float *dK, float *dV, dfgnn_stream_t stream) {
+  return dfgnn_gt_bwd_rowstats_rect(m, m, nnz, h, f, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, Q, K, V, out, row_max,
+                                    row_sum, grad_out, delta, dQ, dK, dV, stream);
+}
+
 // ---- the general statistics pair with a per-edge additive attention bias (gt_bias_train.hip) ------------------------------
-int dfgnn_gt_fwd_bias(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
-                      const float *bias, const float *Q, const float *K, const float *V, float *row_max, float *row_sum,
-                      float *out, dfgnn_stream_t stream) {
-  if (int c = check_common(m, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
-  if (!Q || !K || !V || !out || (!row_max != !row_sum)) return kErrBadArg;  // (both statistics or neither: inference)
+int dfgnn_gt_fwd_bias_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                           const float *bias, const float *Q, const float *K, const float *V, float *row_max,
+                           float *row_sum, float *out, dfgnn_stream_t stream) {
+  if (int c = check_rect(m, n_cols, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (m == 0) return 0;  // (no row: nothing to write)
+  if (!Q || !out || (n_cols > 0 && (!K || !V)) || (!row_max != !row_sum)) return kErrBadArg;  // (both statistics or neither: inference)
   if (nnz > 0 && !bias) return kErrBadArg;
-  const Csr g{m, nnz, h, f, row_ptr, col_ind, nullptr, val};
+  const Csr g = rect_csr(m, n_cols, nnz, h, f, row_ptr, col_ind, val);
   return launch_gt_bias_fwd(g, bias, Q, K, V, row_max, row_sum, out, as_stream(stream));
 }
 
-int dfgnn_gt_bwd_bias(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
-                      const float *bias, const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q,
-                      const float *K, const float *V, const float *out, const float *row_max, const float *row_sum,
-                      const float *grad_out, float *delta, float *dQ, float *dK, float *dV, float *dbias,
-                      dfgnn_stream_t stream) {
-  if (int c = check_common(m, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
-  if (!Q || !K || !V || !out || !row_max || !row_sum || !grad_out || !delta || !dQ || !dK || !dV || !col_ptr)
-    return kErrBadArg;
+int dfgnn_gt_fwd_bias(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                      const float *bias, const float *Q, const float *K, const float *V, float *row_max, float *row_sum,
+                      float *out, dfgnn_stream_t stream) {
+  return dfgnn_gt_fwd_bias_rect(m, m, nnz, h, f, row_ptr, col_ind, val, bias, Q, K, V, row_max, row_sum, out, stream);
+}
+
+int dfgnn_gt_bwd_bias_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                           const float *bias, const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q,
+                           const float *K, const float *V, const float *out, const float *row_max, const float *row_sum,
+                           const float *grad_out, float *delta, float *dQ, float *dK, float *dV, float *dbias,
+                           dfgnn_stream_t stream) {
+  if (int c = check_rect(m, n_cols, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (m > 0 && (!Q || !out || !row_max || !row_sum || !grad_out || !delta || !dQ)) return kErrBadArg;
+  if (n_cols > 0 && (!K || !V || !dK || !dV || !col_ptr)) return kErrBadArg;
   if (nnz > 0 && (!bias || !row_ind || !val_idx)) return kErrBadArg;  // (the CSC pass finds an entry's bias through val_idx)
-  const Csr g{m, nnz, h, f, row_ptr, col_ind, nullptr, val};
+  const Csr g = rect_csr(m, n_cols, nnz, h, f, row_ptr, col_ind, val);
   if (int rc = launch_gt_bias_bwd_rows(g, bias, Q, K, V, out, row_max, row_sum, grad_out, delta, dQ, dbias,
                                        as_stream(stream)))
     return rc;
@@ -281,15 +325,47 @@ int dfgnn_gt_bwd_bias(int m, int nnz, int h, int f, const int *row_ptr, const in
                                  as_stream(stream));
 }
 
+int dfgnn_gt_bwd_bias(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                      const float *bias, const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q,
+                      const float *K, const float *V, const float *out, const float *row_max, const float *row_sum,
+                      const float *grad_out, float *delta, float *dQ, float *dK, float *dV, float *dbias,
+                      dfgnn_stream_t stream) {
+  return dfgnn_gt_bwd_bias_rect(m, m, nnz, h, f, row_ptr, col_ind, val, bias, col_ptr, row_ind, val_idx, Q, K, V, out, row_max,
+                                row_sum, grad_out, delta, dQ, dK, dV, dbias, stream);
+}
+
 // ---- the general statistics pair with a per-edge feature vector in keys and values (gt_edge_train.hip) --------------------
+int dfgnn_gt_fwd_edge_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                           const float *E, const float *Q, const float *K, const float *V, float *row_max, float *row_sum,
+                           float *out, dfgnn_stream_t stream) {
+  if (int c = check_rect(m, n_cols, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (m == 0) return 0;  // (no row: nothing to write)
+  if (!Q || !out || (n_cols > 0 && (!K || !V)) || (!row_max != !row_sum)) return kErrBadArg;  // (both statistics or neither: inference)
+  if (nnz > 0 && !E) return kErrBadArg;
+  const Csr g = rect_csr(m, n_cols, nnz, h, f, row_ptr, col_ind, val);
+  return launch_gt_edge_fwd(g, E, Q, K, V, row_max, row_sum, out, as_stream(stream));
+}
+
 int dfgnn_gt_fwd_edge(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
                       const float *E, const float *Q, const float *K, const float *V, float *row_max, float *row_sum,
                       float *out, dfgnn_stream_t stream) {
-  if (int c = check_common(m, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
-  if (!Q || !K || !V || !out || (!row_max != !row_sum)) return kErrBadArg;  // (both statistics or neither: inference)
-  if (nnz > 0 && !E) return kErrBadArg;
-  const Csr g{m, nnz, h, f, row_ptr, col_ind, nullptr, val};
-  return launch_gt_edge_fwd(g, E, Q, K, V, row_max, row_sum, out, as_stream(stream));
+  return dfgnn_gt_fwd_edge_rect(m, m, nnz, h, f, row_ptr, col_ind, val, E, Q, K, V, row_max, row_sum, out, stream);
+}
+
+int dfgnn_gt_bwd_edge_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                           const float *E, const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q,
+                           const float *K, const float *V, const float *out, const float *row_max, const float *row_sum,
+                           const float *grad_out, float *delta, float *dQ, float *dK, float *dV, float *dE,
+                           dfgnn_stream_t stream) {
+  if (int c = check_rect(m, n_cols, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (m > 0 && (!Q || !out || !row_max || !row_sum || !grad_out || !delta || !dQ)) return kErrBadArg;
+  if (n_cols > 0 && (!K || !V || !dK || !dV || !col_ptr)) return kErrBadArg;
+  if (nnz > 0 && (!E || !row_ind || !val_idx)) return kErrBadArg;  // (the CSC pass finds an entry's E row through val_idx)
+  const Csr g = rect_csr(m, n_cols, nnz, h, f, row_ptr, col_ind, val);
+  if (int rc = launch_gt_edge_bwd_rows(g, E, Q, K, V, out, row_max, row_sum, grad_out, delta, dQ, dE, as_stream(stream)))
+    return rc;
+  return launch_gt_edge_bwd_cols(g, E, col_ptr, row_ind, val_idx, Q, K, V, row_max, row_sum, delta, grad_out, dK, dV,
+                                 as_stream(stream));
 }
 
 int dfgnn_gt_bwd_edge(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
@@ -297,15 +373,8 @@ int dfgnn_gt_bwd_edge(int m, int nnz, int h, int f, const int *row_ptr, const in
                       const float *K, const float *V, const float *out, const float *row_max, const float *row_sum,
                       const float *grad_out, float *delta, float *dQ, float *dK, float *dV, float *dE,
                       dfgnn_stream_t stream) {
-  if (int c = check_common(m, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
-  if (!Q || !K || !V || !out || !row_max || !row_sum || !grad_out || !delta || !dQ || !dK || !dV || !col_ptr)
-    return kErrBadArg;
-  if (nnz > 0 && (!E || !row_ind || !val_idx)) return kErrBadArg;  // (the CSC pass finds an entry's E row through val_idx)
-  const Csr g{m, nnz, h, f, row_ptr, col_ind, nullptr, val};
-  if (int rc = launch_gt_edge_bwd_rows(g, E, Q, K, V, out, row_max, row_sum, grad_out, delta, dQ, dE, as_stream(stream)))
-    return rc;
-  return launch_gt_edge_bwd_cols(g, E, col_ptr, row_ind, val_idx, Q, K, V, row_max, row_sum, delta, grad_out, dK, dV,
-                                 as_stream(stream));
+  return dfgnn_gt_bwd_edge_rect(m, m, nnz, h, f, row_ptr, col_ind, val, E, col_ptr, row_ind, val_idx, Q, K, V, out, row_max,
+                                row_sum, grad_out, delta, dQ, dK, dV, dE, stream);
 }
 
 // ---- GATv2 (gatv2_train.hip): fused inference and training pair, any graph ------------------------------------------------
@@ -316,29 +385,45 @@ int dfgnn_gatv2_bwd_ws_floats(int h, int f) {
   return n > 0x7fffffffLL ? kErrUnsupported : (int)n;
 }
 
+int dfgnn_gatv2_fwd_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *attn,
+                         float negative_slope, const float *X_row, const float *X_col, float *row_max, float *row_sum,
+                         float *out, dfgnn_stream_t stream) {
+  if (int c = check_rect(m, n_cols, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (m == 0) return 0;  // (no row: nothing to write)
+  if (!attn || !X_row || (n_cols > 0 && !X_col) || !out || (!row_max != !row_sum)) return kErrBadArg;  // (both statistics or neither)
+  const Csr g = rect_csr(m, n_cols, nnz, h, f, row_ptr, col_ind, nullptr);
+  return launch_gatv2_fwd(g, Gatv2Graph{nullptr, nullptr, attn, negative_slope}, X_row, X_col, row_max, row_sum, out,
+                          as_stream(stream));
+}
+
 int dfgnn_gatv2_fwd(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *attn,
                     float negative_slope, const float *X_row, const float *X_col, float *row_max, float *row_sum,
                     float *out, dfgnn_stream_t stream) {
-  if (int c = check_common(m, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
-  if (!attn || !X_row || !X_col || !out || (!row_max != !row_sum)) return kErrBadArg;  // (both statistics or neither)
-  const Csr g{m, nnz, h, f, row_ptr, col_ind, nullptr, nullptr};
-  return launch_gatv2_fwd(g, Gatv2Graph{nullptr, nullptr, attn, negative_slope}, X_row, X_col, row_max, row_sum, out,
-                          as_stream(stream));
+  return dfgnn_gatv2_fwd_rect(m, m, nnz, h, f, row_ptr, col_ind, attn, negative_slope, X_row, X_col, row_max, row_sum, out,
+                              stream);
+}
+
+int dfgnn_gatv2_bwd_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const int *col_ptr,
+                         const int *row_ind, const float *attn, float negative_slope, const float *X_row, const float *X_col,
+                         const float *out, const float *row_max, const float *row_sum, const float *grad_out, float *delta,
+                         float *ws, float *dX_row, float *dX_col, float *dattn, dfgnn_stream_t stream) {
+  if (int c = check_rect(m, n_cols, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (!attn || !ws || !dattn || (nnz > 0 && !row_ind)) return kErrBadArg;
+  if (m > 0 && (!X_row || !out || !row_max || !row_sum || !grad_out || !delta || !dX_row)) return kErrBadArg;
+  if (n_cols > 0 && (!X_col || !dX_col || !col_ptr)) return kErrBadArg;
+  if (dX_row && dX_row == dX_col) return kErrBadArg;  // (the two passes each write their buffer in full)
+  if (dfgnn_gatv2_bwd_ws_floats(h, f) < 0) return kErrUnsupported;
+  const Csr g = rect_csr(m, n_cols, nnz, h, f, row_ptr, col_ind, nullptr);
+  return launch_gatv2_bwd(g, Gatv2Graph{col_ptr, row_ind, attn, negative_slope}, X_row, X_col, out, row_max, row_sum,
+                          grad_out, delta, ws, dX_row, dX_col, dattn, as_stream(stream));
 }
 
 int dfgnn_gatv2_bwd(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const int *col_ptr,
                     const int *row_ind, const float *attn, float negative_slope, const float *X_row, const float *X_col,
                     const float *out, const float *row_max, const float *row_sum, const float *grad_out, float *delta,
                     float *ws, float *dX_row, float *dX_col, float *dattn, dfgnn_stream_t stream) {
-  if (int c = check_common(m, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
-  if (!attn || !X_row || !X_col || !out || !row_max || !row_sum || !grad_out || !delta || !ws || !dX_row || !dX_col ||
-      !dattn || !col_ptr || (nnz > 0 && !row_ind))
-    return kErrBadArg;
-  if (dX_row == dX_col) return kErrBadArg;  // (the two passes each write their buffer in full)
-  if (dfgnn_gatv2_bwd_ws_floats(h, f) < 0) return kErrUnsupported;
-  const Csr g{m, nnz, h, f, row_ptr, col_ind, nullptr, nullptr};
-  return launch_gatv2_bwd(g, Gatv2Graph{col_ptr, row_ind, attn, negative_slope}, X_row, X_col, out, row_max, row_sum,
-                          grad_out, delta, ws, dX_row, dX_col, dattn, as_stream(stream));
+  return dfgnn_gatv2_bwd_rect(m, m, nnz, h, f, row_ptr, col_ind, col_ptr, row_ind, attn, negative_slope, X_row, X_col, out,
+                              row_max, row_sum, grad_out, delta, ws, dX_row, dX_col, dattn, stream);
 }
 
 int dfgnn_gt_tiling_fwd(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,

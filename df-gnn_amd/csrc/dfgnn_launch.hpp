@@ -9,7 +9,7 @@
 namespace dfgnn {
 
 struct Csr {
-  int m, nnz, h, f;
+  int m, nnz, h, f;  // m rows; the columns: n_cols below
   const int *row_ptr;
   const int *col_ind;
   const int *rows;   // sorted COO row ids (hyper / softmax formats), may be null for CSR-only ops
@@ -25,6 +25,10 @@ struct Csr {
   // wdense[256 i + c] = val of the edge from node i to the node c places after the first node of its range.  Read by the
   // WEIGHTED instances of the statistics-saving pair (gt_dense_stats_w.hip) wherever the edge bitmap has a bit; null = unit values
   const float *wdense = nullptr;
+  // columns (keys / values; col_ind < n_cols, col_ptr has n_cols + 1 entries) of the pairs that take a rectangular graph:
+  // gt_train / gt_bias_train / gt_edge_train / gatv2_train.hip, whose C entries set it (the square ones to m).  Nothing
+  // else reads it: every other kernel takes m for both sides
+  int n_cols = 0;
 };
 constexpr int kPlanWeightStride = 256;
 
@@ -241,7 +245,8 @@ int launch_gatv2_fwd(const Csr &g, const Gatv2Graph &v, const float *X_row, cons
 int launch_gatv2_bwd(const Csr &g, const Gatv2Graph &v, const float *X_row, const float *X_col, const float *out,
                      const float *row_max, const float *row_sum, const float *grad_out, float *delta, float *ws,
                      float *dX_row, float *dX_col, float *dattn, hipStream_t s);
-// graphs with fewer than kBlockMinAvgDegree edges per row on average take the row-per-lane-group kernels
+// graphs with fewer than kBlockMinAvgDegree edges per row on average take the row-per-lane-group kernels.  The pairs that
+// take an m x n_cols graph ask per pass: (m, nnz) for the forward and the CSR pass, (n_cols, nnz) for the CSC pass
 inline bool low_degree(int m, int nnz) { return (long)nnz < (long)kBlockMinAvgDegree * m; }
 int launch_gat_hyper_fwd(const Csr &g, const float *attn_row, const float *attn_col, float slope,
                          const float *X, float *out, const int *chunks, int nchunks, hipStream_t s);

@@ -24,7 +24,7 @@ namespace dfgnn {
 
 // Everything the per-row routines need; at_head() offsets the feature pointers to the workgroup's head.
 struct Gatv2 {
-  int m, nnz, h, f, head;
+  int m, n_cols, nnz, h, f, head;             // m rows (queries, outputs) x n_cols columns (keys, values)
   size_t hf;
   float slope;
   const int *row_ptr, *col_ind;            // CSR
@@ -315,14 +315,15 @@ __global__ __launch_bounds__(kBlock) void gatv2_wave_kernel(Gatv2 a) {
   Frag<C> av, da;
   frag_load<C>(av, a.ah, a.f, gl);
   frag_zero<C>(da);
+  const int n = PASS == 2 ? a.n_cols : a.m;  // the extent this pass walks: rows, or (CSC pass) columns
   const int beg = blockIdx.x * kWavesPerBlock + wave, step = gridDim.x * kWavesPerBlock;
   if constexpr (PASS == 0) {
     __shared__ __attribute__((aligned(16))) float lds[kWavesPerBlock * kScratchFloatsPerWave];
     float *sw = lds + wave * kScratchFloatsPerWave;
     int *sc = reinterpret_cast<int *>(sw + kWave);
-    for (int r = beg; r < a.m; r += step) gatv2_fwd_row_wave<C>(a, av, r, lane, sw, sc);
+    for (int r = beg; r < n; r += step) gatv2_fwd_row_wave<C>(a, av, r, lane, sw, sc);
   } else {
-    for (int r = beg; r < a.m; r += step) gatv2_group_pass<C, PASS, true>(a, av, da, r, gid, gl);
+    for (int r = beg; r < n; r += step) gatv2_group_pass<C, PASS, true>(a, av, da, r, gid, gl);
   }
   if constexpr (PASS == 1) gatv2_store_part<C>(a, da, wave, gid, gl);
 }
@@ -341,13 +342,14 @@ __global__ __launch_bounds__(kBlock) void gatv2_group_kernel(Gatv2 a) {
   frag_load<C>(av, a.ah, a.f, gl);
   frag_zero<C>(da);
   const int *ptr = PASS == 2 ? a.col_ptr : a.row_ptr;
-  for (int b0 = blockIdx.x * R; b0 < a.m; b0 += gridDim.x * R) {
+  const int n = PASS == 2 ? a.n_cols : a.m;  // the extent this pass walks: rows, or (CSC pass) columns
+  for (int b0 = blockIdx.x * R; b0 < n; b0 += gridDim.x * R) {
     const int r = b0 + threadIdx.x / G;
-    const int deg = r < a.m ? ptr[r + 1] - ptr[r] : 0;
+    const int deg = r < n ? ptr[r + 1] - ptr[r] : 0;
     if (__any(deg > kGatv2GroupMaxDegree)) {
-      for (int rr = b0 + wave * C::EPW; rr < min(a.m, b0 + (wave + 1) * C::EPW); ++rr)
+      for (int rr = b0 + wave * C::EPW; rr < min(n, b0 + (wave + 1) * C::EPW); ++rr)
         gatv2_group_pass<C, PASS, true>(a, av, da, rr, gid, gl);
-    } else if (r < a.m) {
+    } else if (r < n) {
       gatv2_group_pass<C, PASS, false>(a, av, da, r, gid, gl);
     }
   }
@@ -391,11 +393,13 @@ static dim3 gatv2_wave_grid(int m, int h, long cap) {
 // -> the launch status; *nparts (PASS 1): the number of partials the pass writes
 template <int PASS>
 static int launch_gatv2_pass(const Gatv2 &a, bool v4, hipStream_t s, int *nparts = nullptr) {
-  const bool groups = low_degree(a.m, a.nnz);
+  const int n = PASS == 2 ? a.n_cols : a.m;  // the form is chosen per pass, by the average degree of what it walks
+  if (n == 0) return 0;  // nothing to walk and nothing to write (a rectangular graph without rows / without columns)
+  const bool groups = low_degree(n, a.nnz);
   return dispatch_cfg(a.f, v4, [&](auto cfg) {
     using C = decltype(cfg);
-    const dim3 grid = groups ? gatv2_group_grid(a.m, a.h, C::G, PASS == 1 ? kGatv2Parts : 16384)
-                             : gatv2_wave_grid(a.m, a.h, PASS == 1 ? kGatv2Parts : (1 << 20));
+    const dim3 grid = groups ? gatv2_group_grid(n, a.h, C::G, PASS == 1 ? kGatv2Parts : 16384)
+                             : gatv2_wave_grid(n, a.h, PASS == 1 ? kGatv2Parts : (1 << 20));
     if (nparts) *nparts = (int)grid.x;
     if (groups) gatv2_group_kernel<C, PASS><<<grid, kBlock, 0, s>>>(a);
     else gatv2_wave_kernel<C, PASS><<<grid, kBlock, 0, s>>>(a);
@@ -405,7 +409,7 @@ static int launch_gatv2_pass(const Gatv2 &a, bool v4, hipStream_t s, int *nparts
 
 static Gatv2 gatv2_args(const Csr &g, const Gatv2Graph &v, const float *X_row, const float *X_col) {
   Gatv2 a{};
-  a.m = g.m; a.nnz = g.nnz; a.h = g.h; a.f = g.f; a.hf = (size_t)g.h * g.f;
+  a.m = g.m; a.n_cols = g.n_cols; a.nnz = g.nnz; a.h = g.h; a.f = g.f; a.hf = (size_t)g.h * g.f;
   a.slope = v.slope;
   a.row_ptr = g.row_ptr; a.col_ind = g.col_ind; a.col_ptr = v.col_ptr; a.row_ind = v.row_ind;
   a.ah = v.attn; a.Xrh = X_row; a.Xch = X_col;

@@ -38,7 +38,7 @@ namespace dfgnn {
 
 // Everything the per-row routines need; at_head() offsets the feature pointers, E and dE to the workgroup's head.
 struct GtEdge {
-  int m, nnz, h, f, head;
+  int m, n_cols, nnz, h, f, head;             // m rows (queries, outputs) x n_cols columns (keys, values)
   size_t hf;
   const int *row_ptr, *col_ind;                // CSR
   const float *val;                            // CSR order, NULL = unit values
@@ -388,14 +388,15 @@ template <class C, int PASS>
 __global__ __launch_bounds__(kBlock) void gt_edge_wave_kernel(GtEdge a) {
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
   a.at_head(blockIdx.y);
+  const int n = PASS == 2 ? a.n_cols : a.m;  // the extent this pass walks: rows, or (CSC pass) columns
   const int beg = blockIdx.x * kWavesPerBlock + wave, step = gridDim.x * kWavesPerBlock;
   if constexpr (PASS == 0) {
     __shared__ __attribute__((aligned(16))) float lds[kWavesPerBlock * kScratchFloatsPerWave];
     float *sw = lds + wave * kScratchFloatsPerWave;
     int *sc = reinterpret_cast<int *>(sw + kWave);
-    for (int r = beg; r < a.m; r += step) gte_fwd_row_wave<C>(a, r, lane, sw, sc);
+    for (int r = beg; r < n; r += step) gte_fwd_row_wave<C>(a, r, lane, sw, sc);
   } else {
-    for (int r = beg; r < a.m; r += step) gte_group_pass<C, PASS, true>(a, r, lane / C::G, lane % C::G);
+    for (int r = beg; r < n; r += step) gte_group_pass<C, PASS, true>(a, r, lane / C::G, lane % C::G);
   }
 }
 
@@ -410,13 +411,14 @@ __global__ __launch_bounds__(kBlock) void gt_edge_group_kernel(GtEdge a) {
   const int gid = (threadIdx.x & (kWave - 1)) / G, gl = threadIdx.x % G, wave = threadIdx.x / kWave;
   a.at_head(blockIdx.y);
   const int *ptr = PASS == 2 ? a.col_ptr : a.row_ptr;
-  for (int b0 = blockIdx.x * R; b0 < a.m; b0 += gridDim.x * R) {
+  const int n = PASS == 2 ? a.n_cols : a.m;  // the extent this pass walks: rows, or (CSC pass) columns
+  for (int b0 = blockIdx.x * R; b0 < n; b0 += gridDim.x * R) {
     const int r = b0 + threadIdx.x / G;
-    const int deg = r < a.m ? ptr[r + 1] - ptr[r] : 0;
+    const int deg = r < n ? ptr[r + 1] - ptr[r] : 0;
     if (__any(deg > kGtEdgeGroupMaxDegree)) {
-      for (int rr = b0 + wave * C::EPW; rr < min(a.m, b0 + (wave + 1) * C::EPW); ++rr)
+      for (int rr = b0 + wave * C::EPW; rr < min(n, b0 + (wave + 1) * C::EPW); ++rr)
         gte_group_pass<C, PASS, true>(a, rr, gid, gl);
-    } else if (r < a.m) {
+    } else if (r < n) {
       gte_group_pass<C, PASS, false>(a, r, gid, gl);
     }
   }
@@ -435,18 +437,20 @@ static dim3 gte_wave_grid(int m, int h) {
 
 template <int PASS>
 static int launch_gt_edge_pass(const GtEdge &a, bool v4, hipStream_t s) {
-  const bool groups = low_degree(a.m, a.nnz);
+  const int n = PASS == 2 ? a.n_cols : a.m;  // the form is chosen per pass, by the average degree of what it walks
+  if (n == 0) return 0;  // nothing to walk and nothing to write (a rectangular graph without rows / without columns)
+  const bool groups = low_degree(n, a.nnz);
   return dispatch_cfg(a.f, v4, [&](auto cfg) {
     using C = decltype(cfg);
-    if (groups) gt_edge_group_kernel<C, PASS><<<gte_group_grid(a.m, a.h, C::G), kBlock, 0, s>>>(a);
-    else gt_edge_wave_kernel<C, PASS><<<gte_wave_grid(a.m, a.h), kBlock, 0, s>>>(a);
+    if (groups) gt_edge_group_kernel<C, PASS><<<gte_group_grid(n, a.h, C::G), kBlock, 0, s>>>(a);
+    else gt_edge_wave_kernel<C, PASS><<<gte_wave_grid(n, a.h), kBlock, 0, s>>>(a);
     return launch_status();
   });
 }
 
 static GtEdge gt_edge_args(const Csr &g, const float *E, const float *Q, const float *K, const float *V) {
   GtEdge a{};
-  a.m = g.m; a.nnz = g.nnz; a.h = g.h; a.f = g.f; a.hf = (size_t)g.h * g.f;
+  a.m = g.m; a.n_cols = g.n_cols; a.nnz = g.nnz; a.h = g.h; a.f = g.f; a.hf = (size_t)g.h * g.f;
   a.row_ptr = g.row_ptr; a.col_ind = g.col_ind; a.val = g.val; a.Eh = E;
   a.Qh = Q; a.Kh = K; a.Vh = V;
   return a;

@@ -112,10 +112,18 @@ size_t dfgnn_preprocess_ws_bytes(int m, int nnz) {
   return temp + align256((size_t)nnz * sizeof(int));  // + the sorted column keys of the CSC sort
 }
 
-int dfgnn_preprocess_hyper(int m, int nnz, const void *src, const void *dst, int idx64, int *row_ptr, int *col_ind,
-                           int *rows, int *edge_order, int *col_ptr, int *row_ind, int *val_idx, void *ws,
-                           size_t ws_bytes, dfgnn_stream_t stream) {
-  if (m < 0 || nnz < 0) return kErrBadArg;
+int dfgnn_preprocess_ws_bytes_rect(int m, int n_cols, int nnz, size_t *bytes) {
+  if (m < 0 || n_cols < 0 || nnz < 0 || !bytes) return kErrBadArg;
+  const size_t rows = dfgnn_preprocess_ws_bytes(m, nnz), cols = n_cols == m ? rows : dfgnn_preprocess_ws_bytes(n_cols, nnz);
+  if (rows == 0 || cols == 0) return kErrUnsupported;  // (rocPRIM could not size a sort)
+  *bytes = rows > cols ? rows : cols;
+  return 0;
+}
+
+int dfgnn_preprocess_hyper_rect(int m, int n_cols, int nnz, const void *src, const void *dst, int idx64, int *row_ptr,
+                                int *col_ind, int *rows, int *edge_order, int *col_ptr, int *row_ind, int *val_idx, void *ws,
+                                size_t ws_bytes, dfgnn_stream_t stream) {
+  if (m < 0 || n_cols < 0 || nnz < 0) return kErrBadArg;
   if (!row_ptr) return kErrBadArg;
   const bool want_csc = col_ptr || row_ind || val_idx;
   if (want_csc && !col_ptr) return kErrBadArg;
@@ -123,27 +131,30 @@ int dfgnn_preprocess_hyper(int m, int nnz, const void *src, const void *dst, int
   if (nnz == 0) {  // pointers only
     if (hipError_t rc = hipMemsetAsync(row_ptr, 0, ((size_t)m + 1) * sizeof(int), s)) return (int)rc;
     if (want_csc)
-      if (hipError_t rc = hipMemsetAsync(col_ptr, 0, ((size_t)m + 1) * sizeof(int), s)) return (int)rc;
+      if (hipError_t rc = hipMemsetAsync(col_ptr, 0, ((size_t)n_cols + 1) * sizeof(int), s)) return (int)rc;
     return 0;
   }
-  if (m == 0) return kErrBadArg;  // edges without nodes
+  if (m == 0 || n_cols == 0) return kErrBadArg;  // edges without nodes
   if (!src || !dst || !col_ind || !rows || !edge_order || !ws) return kErrBadArg;
   if (want_csc && (!row_ind || !val_idx)) return kErrBadArg;
-  size_t temp = 0;
+  // the row sort runs on the key bits of m, the column sort on those of n_cols; the workspace serves the larger of the two
+  size_t temp = 0, temp_cols = 0;
   if (int rc = sort_temp_bytes(m, nnz, temp)) return rc;
+  if (n_cols != m)
+    if (int rc = sort_temp_bytes(n_cols, nnz, temp_cols)) return rc;
+  if (temp_cols > temp) temp = temp_cols;
   if (ws_bytes < temp + align256((size_t)nnz * sizeof(int))) return kErrBadArg;
   int *sorted_cols = reinterpret_cast<int *>(static_cast<char *>(ws) + temp);
-  const unsigned bits = key_bits(m);
-  const int eb = (nnz + 255) / 256, pb = m / 256 + 1;  // pointer kernel: m + 1 threads
+  const int eb = (nnz + 255) / 256;
 
   // CSR: (row, COO position) sorted by row; the sorted keys ARE the `rows` array of the hyper format
-  const IdNarrow srcs{src, idx64, m}, dsts{dst, idx64, m};
+  const IdNarrow srcs{src, idx64, m}, dsts{dst, idx64, n_cols};
   auto row_keys = rocprim::make_transform_iterator(rocprim::counting_iterator<int>(0), srcs);
   size_t tb = temp;
   if (hipError_t rc = sort_pairs(ws, tb, row_keys, rows, rocprim::counting_iterator<int>(0), edge_order, (unsigned)nnz,
-                                 bits, s))
+                                 key_bits(m), s))
     return (int)rc;
-  csr_pointers_kernel<<<pb, 256, 0, s>>>(m, nnz, rows, row_ptr);
+  csr_pointers_kernel<<<m / 256 + 1, 256, 0, s>>>(m, nnz, rows, row_ptr);  // (m + 1 threads)
   gather_ids_kernel<<<eb, 256, 0, s>>>(nnz, dsts, edge_order, col_ind);
   if (int rc = launch_status()) return rc;
   if (!want_csc) return 0;
@@ -151,11 +162,18 @@ int dfgnn_preprocess_hyper(int m, int nnz, const void *src, const void *dst, int
   // CSC: (column, CSR slot) sorted by column
   tb = temp;
   if (hipError_t rc = sort_pairs(ws, tb, (const int *)col_ind, sorted_cols, rocprim::counting_iterator<int>(0), val_idx,
-                                 (unsigned)nnz, bits, s))
+                                 (unsigned)nnz, key_bits(n_cols), s))
     return (int)rc;
-  csr_pointers_kernel<<<pb, 256, 0, s>>>(m, nnz, sorted_cols, col_ptr);
+  csr_pointers_kernel<<<n_cols / 256 + 1, 256, 0, s>>>(n_cols, nnz, sorted_cols, col_ptr);
   gather_int_kernel<<<eb, 256, 0, s>>>(nnz, rows, val_idx, row_ind);
   return launch_status();
+}
+
+int dfgnn_preprocess_hyper(int m, int nnz, const void *src, const void *dst, int idx64, int *row_ptr, int *col_ind,
+                           int *rows, int *edge_order, int *col_ptr, int *row_ind, int *val_idx, void *ws,
+                           size_t ws_bytes, dfgnn_stream_t stream) {
+  return dfgnn_preprocess_hyper_rect(m, m, nnz, src, dst, idx64, row_ptr, col_ind, rows, edge_order, col_ptr, row_ind, val_idx,
+                                     ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -15,6 +15,8 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>      // guard / stream types behind torch.cuda.*
 #include <torch/extension.h>
 
+#include <algorithm>
+#include <string>
 #include <vector>
 
 #include "../../include/dfgnn.h"
@@ -68,7 +70,20 @@ inline const Tensor *opt(const c10::optional<Tensor> &t) { return t ? &*t : null
 
 struct Dims {
   int m, nnz, h, f;
+  int n_cols = 0;  // set by the checks of the pairs that take an m x n_cols graph (gt_rect_checks, gatv2_checks)
 };
+inline std::string shape_str(const Tensor &t) {  // "(2, 3, 4)", as Python prints a shape
+  std::string s = "(";
+  for (int64_t i = 0; i < t.dim(); ++i) s += (i ? ", " : "") + std::to_string(t.size(i));
+  return s + (t.dim() == 1 ? ",)" : ")");
+}
+// the column side of a pair that takes an m x n_cols graph (K / V, GATv2's X_col): [n_cols, heads, feat] with the heads and
+// features of the row side `rows` (Q, X_row)
+inline void check_cols_feat(const Tensor &t, const char *name, const Tensor &rows, const char *rows_name) {
+  check_f32(t, name);
+  TORCH_CHECK(t.dim() == 3 && t.size(1) == rows.size(1) && t.size(2) == rows.size(2), name, " must have shape (n_cols, ",
+              rows.size(1), ", ", rows.size(2), "): the heads and features of ", rows_name, ", got ", shape_str(t));
+}
 // What every GT entry point checks: the CSR arrays + Q / K / V, and -- where the entry point takes them, else nullptr --
 // the COO rows and the edge values
 Dims gt_checks(const Tensor &row_ptr, const Tensor &col_ind, const Tensor *rows, const Tensor *val, const Tensor &Q,
@@ -93,7 +108,42 @@ Dims gt_checks(const Tensor &row_ptr, const Tensor &col_ind, const Tensor *rows,
   check_same_device(Q, {&row_ptr, &col_ind, rows, val, &K, &V});
   return Dims{(int)Q.size(0), (int)nnz, (int)Q.size(1), (int)Q.size(2)};
 }
-// ... of a backward: the CSC arrays next to the CSR structure,
+// ... of the four pairs that take an m x n_cols graph (rowstats, bias, edge; GATv2 has its own): K and V agree with each
+// other and with Q in [heads, feat]; their rows are the graph's columns
+Dims gt_rect_checks(const Tensor &row_ptr, const Tensor &col_ind, const Tensor *val, const Tensor &Q, const Tensor &K,
+                    const Tensor &V) {
+  check_i32(row_ptr, "row_ptr");
+  check_i32(col_ind, "col_ind");
+  check_feat3(Q, Q, "Q");
+  check_cols_feat(K, "K", Q, "Q");
+  check_f32(V, "V");
+  TORCH_CHECK(V.sizes() == K.sizes(), "V must have shape ", shape_str(K), " like K, got ", shape_str(V));
+  TORCH_CHECK(row_ptr.dim() == 1 && col_ind.dim() == 1, "indptr / indices must be 1-D");
+  TORCH_CHECK(row_ptr.size(0) - 1 == Q.size(0), "indptr describes ", row_ptr.size(0) - 1, " rows but features have ", Q.size(0),
+              " nodes");
+  const int64_t nnz = col_ind.size(0);
+  if (val) {
+    check_f32(*val, "val");
+    check_edges(*val, nnz, "val");
+  }
+  check_same_device(Q, {&row_ptr, &col_ind, val, &K, &V});
+  return Dims{(int)Q.size(0), (int)nnz, (int)Q.size(1), (int)Q.size(2), (int)K.size(0)};
+}
+// ... their CSC arrays: col_ptr has an entry per column and one more,
+void csc_rect_checks(const Dims &d, const Tensor &ref, const Tensor &col_ptr, const Tensor &row_ind, const Tensor *val_idx,
+                     const char *cols_name) {
+  check_i32(col_ptr, "col_ptr");
+  check_i32(row_ind, "row_ind");
+  check_edges(row_ind, d.nnz, "row_ind");
+  if (val_idx) {
+    check_i32(*val_idx, "val_idx");
+    check_edges(*val_idx, d.nnz, "val_idx");
+  }
+  TORCH_CHECK(col_ptr.dim() == 1 && col_ptr.size(0) == d.n_cols + 1, "col_ptr must have shape (", d.n_cols + 1,
+              ",): one entry for each of the ", d.n_cols, " rows of ", cols_name, " and one more");
+  check_same_device(ref, {&col_ptr, &row_ind, val_idx});
+}
+// ... of a backward of a square adjacency: the CSC arrays next to the CSR structure,
 void csc_checks(const Dims &d, const Tensor &ref, const Tensor &col_ptr, const Tensor &row_ind, const Tensor &val_idx) {
   check_i32(col_ptr, "col_ptr");
   check_i32(row_ind, "row_ind");
@@ -211,11 +261,11 @@ inline const float *edge_val_ptr(const c10::optional<Tensor> &val, bool unit_val
 
 std::vector<Tensor> gt_fwd_rowstats(const Tensor &row_ptr, const Tensor &col_ind, const c10::optional<Tensor> &val, const Tensor &Q,
                                     const Tensor &K, const Tensor &V, bool unit_val) {
-  const Dims d = gt_checks(row_ptr, col_ind, nullptr, opt(val), Q, K, V);
+  const Dims d = gt_rect_checks(row_ptr, col_ind, opt(val), Q, K, V);
   c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
   Tensor out = torch::empty_like(Q);
   Tensor row_max = torch::empty({d.m, d.h}, Q.options()), row_sum = torch::empty({d.m, d.h}, Q.options());
-  check_rc(dfgnn_gt_fwd_rowstats(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), edge_val_ptr(val, unit_val), f32(Q), f32(K),
+  check_rc(dfgnn_gt_fwd_rowstats_rect(d.m, d.n_cols, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), edge_val_ptr(val, unit_val), f32(Q), f32(K),
                                  f32(V), f32(row_max), f32(row_sum), f32(out), cur_stream()),
            "gt_forward_rowstats");
   return {out, row_max, row_sum};
@@ -225,8 +275,8 @@ std::vector<Tensor> gt_bwd_rowstats(const Tensor &row_ptr, const Tensor &col_ind
                                     const Tensor &row_ind, const Tensor &val_idx, const Tensor &Q, const Tensor &K,
                                     const Tensor &V, const Tensor &out, const Tensor &row_max, const Tensor &row_sum,
                                     const Tensor &grad, bool unit_val) {
-  const Dims d = gt_checks(row_ptr, col_ind, nullptr, opt(val), Q, K, V);
-  csc_checks(d, Q, col_ptr, row_ind, val_idx);
+  const Dims d = gt_rect_checks(row_ptr, col_ind, opt(val), Q, K, V);
+  csc_rect_checks(d, Q, col_ptr, row_ind, &val_idx, "K / V");
   check_feat3(out, Q, "out");
   check_feat3(grad, Q, "grad");
   row_stats_checks(d, Q, row_max, row_sum);
@@ -234,7 +284,7 @@ std::vector<Tensor> gt_bwd_rowstats(const Tensor &row_ptr, const Tensor &col_ind
   c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
   Tensor delta = torch::empty({d.m, d.h}, Q.options());
   Tensor dQ = torch::empty_like(Q), dK = torch::empty_like(K), dV = torch::empty_like(V);
-  check_rc(dfgnn_gt_bwd_rowstats(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), edge_val_ptr(val, unit_val), i32(col_ptr),
+  check_rc(dfgnn_gt_bwd_rowstats_rect(d.m, d.n_cols, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), edge_val_ptr(val, unit_val), i32(col_ptr),
                                  i32(row_ind), i32(val_idx), f32(Q), f32(K), f32(V), f32(out), f32(row_max), f32(row_sum),
                                  f32(grad), f32(delta), f32(dQ), f32(dK), f32(dV), cur_stream()),
            "gt_backward_rowstats");
@@ -253,7 +303,7 @@ void bias_checks(const Dims &d, const Tensor &ref, const Tensor &bias) {
 // save_stats = false: inference (-> {out})
 std::vector<Tensor> gt_fwd_bias(const Tensor &row_ptr, const Tensor &col_ind, const c10::optional<Tensor> &val, const Tensor &bias,
                                 const Tensor &Q, const Tensor &K, const Tensor &V, bool unit_val, bool save_stats) {
-  const Dims d = gt_checks(row_ptr, col_ind, nullptr, opt(val), Q, K, V);
+  const Dims d = gt_rect_checks(row_ptr, col_ind, opt(val), Q, K, V);
   bias_checks(d, Q, bias);
   c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
   Tensor out = torch::empty_like(Q);
@@ -262,7 +312,7 @@ std::vector<Tensor> gt_fwd_bias(const Tensor &row_ptr, const Tensor &col_ind, co
     row_max = torch::empty({d.m, d.h}, Q.options());
     row_sum = torch::empty({d.m, d.h}, Q.options());
   }
-  check_rc(dfgnn_gt_fwd_bias(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), edge_val_ptr(val, unit_val), f32(bias), f32(Q),
+  check_rc(dfgnn_gt_fwd_bias_rect(d.m, d.n_cols, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), edge_val_ptr(val, unit_val), f32(bias), f32(Q),
                              f32(K), f32(V), f32(row_max), f32(row_sum), f32(out), cur_stream()),
            save_stats ? "gt_forward_bias" : "gt_inference_bias");
   if (!save_stats) return {out};
@@ -274,9 +324,9 @@ std::vector<Tensor> gt_bwd_bias(const Tensor &row_ptr, const Tensor &col_ind, co
                                 const Tensor &col_ptr, const Tensor &row_ind, const Tensor &val_idx, const Tensor &Q,
                                 const Tensor &K, const Tensor &V, const Tensor &out, const Tensor &row_max,
                                 const Tensor &row_sum, const Tensor &grad, bool unit_val, bool need_dbias) {
-  const Dims d = gt_checks(row_ptr, col_ind, nullptr, opt(val), Q, K, V);
+  const Dims d = gt_rect_checks(row_ptr, col_ind, opt(val), Q, K, V);
   bias_checks(d, Q, bias);
-  csc_checks(d, Q, col_ptr, row_ind, val_idx);
+  csc_rect_checks(d, Q, col_ptr, row_ind, &val_idx, "K / V");
   check_feat3(out, Q, "out");
   check_feat3(grad, Q, "grad");
   row_stats_checks(d, Q, row_max, row_sum);
@@ -286,7 +336,7 @@ std::vector<Tensor> gt_bwd_bias(const Tensor &row_ptr, const Tensor &col_ind, co
   Tensor dQ = torch::empty_like(Q), dK = torch::empty_like(K), dV = torch::empty_like(V);
   Tensor dbias;
   if (need_dbias) dbias = torch::empty({d.h, d.nnz}, Q.options());
-  check_rc(dfgnn_gt_bwd_bias(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), edge_val_ptr(val, unit_val), f32(bias),
+  check_rc(dfgnn_gt_bwd_bias_rect(d.m, d.n_cols, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), edge_val_ptr(val, unit_val), f32(bias),
                              i32(col_ptr), i32(row_ind), i32(val_idx), f32(Q), f32(K), f32(V), f32(out), f32(row_max),
                              f32(row_sum), f32(grad), f32(delta), f32(dQ), f32(dK), f32(dV), f32(dbias), cur_stream()),
            "gt_backward_bias");
@@ -306,7 +356,7 @@ void edge_feat_checks(const Dims &d, const Tensor &ref, const Tensor &E) {
 // save_stats = false: inference (-> {out})
 std::vector<Tensor> gt_fwd_edge(const Tensor &row_ptr, const Tensor &col_ind, const c10::optional<Tensor> &val, const Tensor &E,
                                 const Tensor &Q, const Tensor &K, const Tensor &V, bool unit_val, bool save_stats) {
-  const Dims d = gt_checks(row_ptr, col_ind, nullptr, opt(val), Q, K, V);
+  const Dims d = gt_rect_checks(row_ptr, col_ind, opt(val), Q, K, V);
   edge_feat_checks(d, Q, E);
   c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
   Tensor out = torch::empty_like(Q);
@@ -315,7 +365,7 @@ std::vector<Tensor> gt_fwd_edge(const Tensor &row_ptr, const Tensor &col_ind, co
     row_max = torch::empty({d.m, d.h}, Q.options());
     row_sum = torch::empty({d.m, d.h}, Q.options());
   }
-  check_rc(dfgnn_gt_fwd_edge(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), edge_val_ptr(val, unit_val), f32(E), f32(Q),
+  check_rc(dfgnn_gt_fwd_edge_rect(d.m, d.n_cols, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), edge_val_ptr(val, unit_val), f32(E), f32(Q),
                              f32(K), f32(V), f32(row_max), f32(row_sum), f32(out), cur_stream()),
            save_stats ? "gt_forward_edge" : "gt_inference_edge");
   if (!save_stats) return {out};
@@ -327,9 +377,9 @@ std::vector<Tensor> gt_bwd_edge(const Tensor &row_ptr, const Tensor &col_ind, co
                                 const Tensor &col_ptr, const Tensor &row_ind, const Tensor &val_idx, const Tensor &Q,
                                 const Tensor &K, const Tensor &V, const Tensor &out, const Tensor &row_max,
                                 const Tensor &row_sum, const Tensor &grad, bool unit_val, bool need_dE) {
-  const Dims d = gt_checks(row_ptr, col_ind, nullptr, opt(val), Q, K, V);
+  const Dims d = gt_rect_checks(row_ptr, col_ind, opt(val), Q, K, V);
   edge_feat_checks(d, Q, E);
-  csc_checks(d, Q, col_ptr, row_ind, val_idx);
+  csc_rect_checks(d, Q, col_ptr, row_ind, &val_idx, "K / V");
   check_feat3(out, Q, "out");
   check_feat3(grad, Q, "grad");
   row_stats_checks(d, Q, row_max, row_sum);
@@ -339,7 +389,7 @@ std::vector<Tensor> gt_bwd_edge(const Tensor &row_ptr, const Tensor &col_ind, co
   Tensor dQ = torch::empty_like(Q), dK = torch::empty_like(K), dV = torch::empty_like(V);
   Tensor dE;
   if (need_dE) dE = torch::empty_like(E);
-  check_rc(dfgnn_gt_bwd_edge(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), edge_val_ptr(val, unit_val), f32(E),
+  check_rc(dfgnn_gt_bwd_edge_rect(d.m, d.n_cols, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), edge_val_ptr(val, unit_val), f32(E),
                              i32(col_ptr), i32(row_ind), i32(val_idx), f32(Q), f32(K), f32(V), f32(out), f32(row_max),
                              f32(row_sum), f32(grad), f32(delta), f32(dQ), f32(dK), f32(dV), f32(dE), cur_stream()),
            "gt_backward_edge");
@@ -514,7 +564,7 @@ Dims gatv2_checks(const Tensor &attn, const Tensor &row_ptr, const Tensor &col_i
   check_i32(row_ptr, "row_ptr");
   check_i32(col_ind, "col_ind");
   check_feat3(X_row, X_row, "X_row");
-  check_feat3(X_col, X_row, "X_col");
+  check_cols_feat(X_col, "X_col", X_row, "X_row");
   check_f32(attn, "attn");
   TORCH_CHECK(attn.dim() == 2 && attn.size(0) == X_row.size(1) && attn.size(1) == X_row.size(2), "attn must have shape (",
               X_row.size(1), ", ", X_row.size(2), "), got ", attn.sizes());
@@ -522,7 +572,7 @@ Dims gatv2_checks(const Tensor &attn, const Tensor &row_ptr, const Tensor &col_i
   TORCH_CHECK(row_ptr.size(0) - 1 == X_row.size(0), "indptr describes ", row_ptr.size(0) - 1, " rows but features have ",
               X_row.size(0), " nodes");
   check_same_device(X_row, {&attn, &row_ptr, &col_ind, &X_col});
-  return Dims{(int)X_row.size(0), (int)col_ind.size(0), (int)X_row.size(1), (int)X_row.size(2)};
+  return Dims{(int)X_row.size(0), (int)col_ind.size(0), (int)X_row.size(1), (int)X_row.size(2), (int)X_col.size(0)};
 }
 
 // save_stats = false: inference -> {out}; else the training forward -> {out, row_max, row_sum}
@@ -536,7 +586,7 @@ std::vector<Tensor> gatv2_fwd(const Tensor &attn, const Tensor &row_ptr, const T
     row_max = torch::empty({d.m, d.h}, X_row.options());
     row_sum = torch::empty({d.m, d.h}, X_row.options());
   }
-  check_rc(dfgnn_gatv2_fwd(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), f32(attn), (float)slope, f32(X_row), f32(X_col),
+  check_rc(dfgnn_gatv2_fwd_rect(d.m, d.n_cols, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), f32(attn), (float)slope, f32(X_row), f32(X_col),
                            f32(row_max), f32(row_sum), f32(out), cur_stream()),
            save_stats ? "gatv2_forward" : "gatv2_inference");
   if (!save_stats) return {out};
@@ -547,23 +597,19 @@ std::vector<Tensor> gatv2_bwd(double slope, const Tensor &row_ptr, const Tensor 
                               const Tensor &attn, const Tensor &X_row, const Tensor &X_col, const Tensor &out, const Tensor &row_max,
                               const Tensor &row_sum, const Tensor &grad) {
   const Dims d = gatv2_checks(attn, row_ptr, col_ind, X_row, X_col);
-  check_i32(col_ptr, "col_ptr");
-  check_i32(row_ind, "row_ind");
-  check_edges(row_ind, d.nnz, "row_ind");
-  TORCH_CHECK(col_ptr.dim() == 1 && col_ptr.size(0) == d.m + 1, "col_ptr must have shape (", d.m + 1,
-              ",): the adjacency must be square");
+  csc_rect_checks(d, X_row, col_ptr, row_ind, nullptr, "X_col");
   check_feat3(out, X_row, "out");
   check_feat3(grad, X_row, "grad");
   row_stats_checks(d, X_row, row_max, row_sum);
-  check_same_device(X_row, {&col_ptr, &row_ind, &out, &grad});
+  check_same_device(X_row, {&out, &grad});
   c10::hip::HIPGuardMasqueradingAsCUDA guard(X_row.device());
   Tensor dX_row = torch::empty_like(X_row), dX_col = torch::empty_like(X_col);
-  if (d.m == 0) return {dX_row, dX_col, torch::zeros_like(attn)};  // (nothing to launch: no edge adds to dattn)
+  if (d.m == 0 && d.n_cols == 0) return {dX_row, dX_col, torch::zeros_like(attn)};  // (nothing to launch: no edge adds to dattn)
   const int ws_floats = dfgnn_gatv2_bwd_ws_floats(d.h, d.f);
   check_rc(ws_floats < 0 ? ws_floats : 0, "gatv2_backward");
   Tensor delta = torch::empty({d.m, d.h}, X_row.options()), ws = torch::empty({(int64_t)ws_floats}, X_row.options());
   Tensor dattn = torch::empty_like(attn);
-  check_rc(dfgnn_gatv2_bwd(d.m, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), i32(col_ptr), i32(row_ind), f32(attn), (float)slope,
+  check_rc(dfgnn_gatv2_bwd_rect(d.m, d.n_cols, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), i32(col_ptr), i32(row_ind), f32(attn), (float)slope,
                            f32(X_row), f32(X_col), f32(out), f32(row_max), f32(row_sum), f32(grad), f32(delta), f32(ws),
                            f32(dX_row), f32(dX_col), f32(dattn), cur_stream()),
            "gatv2_backward");
@@ -615,7 +661,8 @@ std::pair<Tensor, std::vector<int64_t>> plan_build(const Tensor &indptr, const T
 }
 
 // dfgnn_preprocess_hyper: COO -> (row_ptr, col_ind, rows, edge_order[, col_ptr, row_ind, val_idx]) (DFGNN/layers/util.py:82-142)
-std::vector<Tensor> preprocess_hyper(const Tensor &src, const Tensor &dst, int64_t num_nodes, bool csc) {
+// num_cols: the column extent of a rectangular graph (num_nodes then counts its rows); < 0: square
+std::vector<Tensor> preprocess_hyper(const Tensor &src, const Tensor &dst, int64_t num_nodes, bool csc, int64_t num_cols) {
   TORCH_CHECK(src.is_cuda() && dst.is_cuda(), "src / dst must be on CUDA");
   TORCH_CHECK(src.scalar_type() == dst.scalar_type() && (src.scalar_type() == torch::kInt64 || src.scalar_type() == torch::kInt32),
               "src / dst must both be int64 or int32, got ", src.scalar_type(), " / ", dst.scalar_type());
@@ -624,17 +671,19 @@ std::vector<Tensor> preprocess_hyper(const Tensor &src, const Tensor &dst, int64
   check_same_device(src, {&dst});
   const Tensor s = src.contiguous(), t = dst.contiguous();
   const int64_t nnz = s.numel();
-  TORCH_CHECK(nnz < (int64_t(1) << 31) && num_nodes < (int64_t(1) << 31) && num_nodes >= 0,
+  if (num_cols < 0) num_cols = num_nodes;
+  TORCH_CHECK(nnz < (int64_t(1) << 31) && num_nodes < (int64_t(1) << 31) && num_nodes >= 0 && num_cols < (int64_t(1) << 31),
               "graphs with 2^31 or more nodes / edges are not supported (int32 index arrays)");
-  const int m = (int)num_nodes;
+  const int m = (int)num_nodes, n_cols = (int)num_cols;
   c10::hip::HIPGuardMasqueradingAsCUDA guard(s.device());
   const auto i32o = s.options().dtype(torch::kInt32);
   std::vector<Tensor> outs = {torch::empty({m + 1}, i32o), torch::empty({nnz}, i32o), torch::empty({nnz}, i32o), torch::empty({nnz}, i32o)};
-  if (csc) outs.insert(outs.end(), {torch::empty({m + 1}, i32o), torch::empty({nnz}, i32o), torch::empty({nnz}, i32o)});
-  const size_t ws_bytes = dfgnn_preprocess_ws_bytes(m, (int)nnz);
+  if (csc) outs.insert(outs.end(), {torch::empty({n_cols + 1}, i32o), torch::empty({nnz}, i32o), torch::empty({nnz}, i32o)});
+  size_t ws_bytes = 0;
+  check_rc(dfgnn_preprocess_ws_bytes_rect(m, n_cols, (int)nnz, &ws_bytes), "dfgnn_preprocess_hyper");
   Tensor ws = torch::empty({(int64_t)ws_bytes}, s.options().dtype(torch::kUInt8));
   const Tensor none;
-  check_rc(dfgnn_preprocess_hyper(m, (int)nnz, s.data_ptr(), t.data_ptr(), s.scalar_type() == torch::kInt64 ? 1 : 0, i32(outs[0]),
+  check_rc(dfgnn_preprocess_hyper_rect(m, n_cols, (int)nnz, s.data_ptr(), t.data_ptr(), s.scalar_type() == torch::kInt64 ? 1 : 0, i32(outs[0]),
                                   i32(outs[1]), i32(outs[2]), i32(outs[3]), i32(csc ? outs[4] : none), i32(csc ? outs[5] : none),
                                   i32(csc ? outs[6] : none), ws.data_ptr(), ws_bytes, cur_stream()),
            "dfgnn_preprocess_hyper");

@@ -20,6 +20,8 @@ _vp, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 SIGNATURES = {
     "dfgnn_plan_build": [_i, _i, _i] + [_vp] * 5,
     "dfgnn_preprocess_hyper": [_i, _i, _vp, _vp, _i] + [_vp] * 8 + [ctypes.c_size_t, _vp],
+    "dfgnn_preprocess_ws_bytes_rect": [_i, _i, _i, _vp],
+    "dfgnn_preprocess_hyper_rect": [_i, _i, _i, _vp, _vp, _i] + [_vp] * 8 + [ctypes.c_size_t, _vp],
     "dfgnn_gt_hyper_fwd": [_i, _i, _i, _i] + [_vp] * 13,
     "dfgnn_gt_bwd": [_i, _i, _i, _i] + [_vp] * 19,
     "dfgnn_gt_stats_applies": [_i, _i, _i, _i, _vp],
@@ -37,6 +39,15 @@ SIGNATURES = {
     "dfgnn_gatv2_bwd_ws_floats": [_i, _i],
     "dfgnn_gatv2_fwd": [_i, _i, _i, _i] + [_vp] * 3 + [_f] + [_vp] * 6,
     "dfgnn_gatv2_bwd": [_i, _i, _i, _i] + [_vp] * 5 + [_f] + [_vp] * 12,
+    # the same pairs on an m x n_cols graph: (m, n_cols, nnz, h, f, ...)
+    "dfgnn_gt_fwd_rowstats_rect": [_i] * 5 + [_vp] * 10,
+    "dfgnn_gt_bwd_rowstats_rect": [_i] * 5 + [_vp] * 18,
+    "dfgnn_gt_fwd_bias_rect": [_i] * 5 + [_vp] * 11,
+    "dfgnn_gt_bwd_bias_rect": [_i] * 5 + [_vp] * 20,
+    "dfgnn_gt_fwd_edge_rect": [_i] * 5 + [_vp] * 11,
+    "dfgnn_gt_bwd_edge_rect": [_i] * 5 + [_vp] * 20,
+    "dfgnn_gatv2_fwd_rect": [_i] * 5 + [_vp] * 3 + [_f] + [_vp] * 6,
+    "dfgnn_gatv2_bwd_rect": [_i] * 5 + [_vp] * 5 + [_f] + [_vp] * 12,
     "dfgnn_gt_bwd_rows": [_i, _i, _i, _i] + [_vp] * 11,
     "dfgnn_gt_bwd_cols": [_i, _i, _i, _i] + [_vp] * 11,
     "dfgnn_gt_tiling_fwd": [_i, _i, _i, _i] + [_vp] * 8,

@@ -11,8 +11,8 @@ tensors from the training forward; its schedule argument only distributes work a
 import torch
 
 import dfgnn_native as _n
-from _binding_util import (_KeyedCache, as_int32, call, check_2d, check_csc, check_csr, check_edges, check_family,
-                           check_feats, get_plan_obj, get_rows, plan_ptrs)
+from _binding_util import (_KeyedCache, as_int32, call, check_2d, check_cols, check_csc, check_csc_rect, check_csr, check_edges,
+                           check_family, check_feats, get_plan_obj, get_rows, plan_ptrs)
 
 # Set to False to force the general (plan-less) kernels; results are identical either way.
 USE_BLOCK_PLAN = True
@@ -279,21 +279,23 @@ def gat_forward_tb(attn_row, attn_col, row_ptr, col_ind, negative_slope, in_feat
 
 
 def _check_v2(attn, row_ptr, col_ind, X_row, X_col, **like_X):
-    """What every GATv2 operator checks: X_row / X_col (and `like_X`: out, grad) fp32 [nodes, heads, feat] of one shape,
-    attn fp32 [heads, feat], the CSR arrays of those nodes -> (m, nnz, h, f)."""
-    m, h, f = check_feats(X_row=X_row, X_col=X_col, **like_X)
+    """What every GATv2 operator checks: X_row (and `like_X`: out, grad) fp32 [m, heads, feat], X_col fp32 [n_cols, heads,
+    feat] -- the graph may be rectangular: m rows, n_cols columns --, attn fp32 [heads, feat], the CSR arrays of the m rows
+    -> (m, n_cols, nnz, h, f)."""
+    m, h, f = check_feats(X_row=X_row, **like_X)
+    n_cols = check_cols("X_row", X_row, X_col=X_col)
     check_2d(X_row, h, f, attn=attn)
-    return m, check_csr(X_row, m, row_ptr, col_ind), h, f
+    return m, n_cols, check_csr(X_row, m, row_ptr, col_ind), h, f
 
 
 def _gatv2_fwd(what, save_stats, attn, row_ptr, col_ind, negative_slope, X_row, X_col):
     ext = _n.ext()
     if ext is not None:
         return ext.gatv2_fwd(attn, row_ptr, col_ind, float(negative_slope), X_row, X_col, save_stats)
-    m, nnz, h, f = _check_v2(attn, row_ptr, col_ind, X_row, X_col)
+    m, n_cols, nnz, h, f = _check_v2(attn, row_ptr, col_ind, X_row, X_col)
     out = torch.empty_like(X_row)
     row_max, row_sum = (_empty(X_row, m, h), _empty(X_row, m, h)) if save_stats else (None, None)
-    call("dfgnn_gatv2_fwd", what, X_row.device, m, nnz, h, f, row_ptr, col_ind, attn, float(negative_slope), X_row, X_col,
+    call("dfgnn_gatv2_fwd_rect", what, X_row.device, m, n_cols, nnz, h, f, row_ptr, col_ind, attn, float(negative_slope), X_row, X_col,
          row_max, row_sum, out)
     return [out, row_max, row_sum] if save_stats else [out]
 
@@ -315,16 +317,16 @@ def gatv2_backward(negative_slope, row_ptr, col_ind, col_ptr, row_ind, attn, X_r
     if ext is not None:
         return ext.gatv2_bwd(float(negative_slope), row_ptr, col_ind, col_ptr, row_ind, attn, X_row, X_col, out, row_max,
                              row_sum, grad)
-    m, nnz, h, f = _check_v2(attn, row_ptr, col_ind, X_row, X_col, out=out, grad=grad)
-    check_csc(X_row, m, nnz, col_ptr, row_ind=row_ind)
+    m, n_cols, nnz, h, f = _check_v2(attn, row_ptr, col_ind, X_row, X_col, out=out, grad=grad)
+    check_csc_rect(X_row, n_cols, nnz, col_ptr, "X_col", row_ind=row_ind)
     check_2d(X_row, m, h, row_max=row_max, row_sum=row_sum)
     dX_row, dX_col = torch.empty_like(X_row), torch.empty_like(X_col)
-    if m == 0:
+    if m == 0 and n_cols == 0:
         return [dX_row, dX_col, torch.zeros_like(attn)]    # (nothing to launch: no edge adds to dattn)
     ws_floats = int(_n.lib().dfgnn_gatv2_bwd_ws_floats(h, f))
     if ws_floats < 0:
         _n.check(ws_floats, "gatv2_backward")
     delta, ws, dattn = _empty(X_row, m, h), _empty(X_row, ws_floats), torch.empty_like(attn)
-    call("dfgnn_gatv2_bwd", "gatv2_backward", X_row.device, m, nnz, h, f, row_ptr, col_ind, col_ptr, row_ind, attn,
+    call("dfgnn_gatv2_bwd_rect", "gatv2_backward", X_row.device, m, n_cols, nnz, h, f, row_ptr, col_ind, col_ptr, row_ind, attn,
          float(negative_slope), X_row, X_col, out, row_max, row_sum, grad, delta, ws, dX_row, dX_col, dattn)
     return [dX_row, dX_col, dattn]

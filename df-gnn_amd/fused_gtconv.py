@@ -15,8 +15,8 @@ import torch
 import dfgnn_native as _n
 import os
 
-from _binding_util import (as_int32, call, check_2d, check_3d, check_csc, check_csr, check_edges, check_family, check_feats,
-                           get_plan_obj, plan_dense_weights, plan_ptrs, val_ptr)
+from _binding_util import (as_int32, call, check_2d, check_3d, check_cols, check_csc, check_csc_rect, check_csr, check_edges,
+                           check_family, check_feats, get_plan_obj, plan_dense_weights, plan_ptrs, val_ptr)
 
 # Set to False to force the general (plan-less) kernels; results are identical either way.
 USE_BLOCK_PLAN = True
@@ -35,6 +35,18 @@ def _checks(indptr, indices, Q, K, V, rows=None, val=None, **like_Q):
     if val is not None:
         check_edges(Q, nnz, torch.float32, val=val)
     return m, nnz, h, f
+
+
+def _checks_rect(indptr, indices, Q, K, V, val=None, **like_Q):
+    """_checks of the pairs that take an m x n_cols graph (rowstats, bias, edge): Q (and `like_Q`: grad, out) fp32
+    [m, heads, feat]; K and V agree with each other and with Q in [heads, feat], their rows are the graph's columns
+    -> (m, n_cols, nnz, h, f)."""
+    m, h, f = check_feats(Q=Q, **like_Q)
+    n_cols = check_cols("Q", Q, K=K, V=V)
+    nnz = check_csr(Q, m, indptr, indices)
+    if val is not None:
+        check_edges(Q, nnz, torch.float32, val=val)
+    return m, n_cols, nnz, h, f
 
 
 def _empty(like, *shape):
@@ -272,6 +284,9 @@ def gt_backward_stats(row_ptr, col_ind, Q, K, V, row_max, row_sum, grad, plan=No
 # Not part of the reference's module.  The same saved state as the pair above -- two floats per (row, head) -- but for
 # ANY graph: no plan, no degree limit, any f (csrc/gt_train.hip).  Opt-in: DFGNN.operators.fused_gtconv.GTConvFuse_rowstats
 # takes it; FusedGTFunction_hyper does not.
+# This pair and its two variants below also take a RECTANGULAR graph (a neighbour-sampled block, cross-attention): Q [m, h, f]
+# with row_ptr (m + 1,), K / V [n_cols, h, f] with col_ptr (n_cols + 1,), col_ind < n_cols; out, dQ and the statistics have
+# m rows, dK / dV n_cols.  Every other GT operator of this module is square-only and rejects Q / K / V of different shapes.
 
 
 def gt_forward_rowstats(row_ptr, col_ind, val, Q, K, V):
@@ -280,9 +295,9 @@ def gt_forward_rowstats(row_ptr, col_ind, val, Q, K, V):
     ext = _n.ext()
     if ext is not None:
         return ext.gt_fwd_rowstats(row_ptr, col_ind, val, Q, K, V, val_ptr(val) is None)
-    m, nnz, h, f = _checks(row_ptr, col_ind, Q, K, V, val=val)
+    m, n_cols, nnz, h, f = _checks_rect(row_ptr, col_ind, Q, K, V, val=val)
     out, row_max, row_sum = torch.empty_like(Q), _empty(Q, m, h), _empty(Q, m, h)
-    call("dfgnn_gt_fwd_rowstats", "gt_forward_rowstats", Q.device, m, nnz, h, f, row_ptr, col_ind, val_ptr(val), Q, K, V,
+    call("dfgnn_gt_fwd_rowstats_rect", "gt_forward_rowstats", Q.device, m, n_cols, nnz, h, f, row_ptr, col_ind, val_ptr(val), Q, K, V,
          row_max, row_sum, out)
     return [out, row_max, row_sum]
 
@@ -295,12 +310,12 @@ def gt_backward_rowstats(row_ptr, col_ind, val, col_ptr, row_ind, val_idx, Q, K,
     if ext is not None:
         return ext.gt_bwd_rowstats(row_ptr, col_ind, val, col_ptr, row_ind, val_idx, Q, K, V, out, row_max, row_sum, grad,
                                    val_ptr(val) is None)
-    m, nnz, h, f = _checks(row_ptr, col_ind, Q, K, V, val=val, out=out, grad=grad)
-    check_csc(Q, m, nnz, col_ptr, row_ind=row_ind, val_idx=val_idx)
+    m, n_cols, nnz, h, f = _checks_rect(row_ptr, col_ind, Q, K, V, val=val, out=out, grad=grad)
+    check_csc_rect(Q, n_cols, nnz, col_ptr, "K / V", row_ind=row_ind, val_idx=val_idx)
     check_2d(Q, m, h, row_max=row_max, row_sum=row_sum)
     delta = _empty(Q, m, h)
     dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
-    call("dfgnn_gt_bwd_rowstats", "gt_backward_rowstats", Q.device, m, nnz, h, f, row_ptr, col_ind, val_ptr(val), col_ptr,
+    call("dfgnn_gt_bwd_rowstats_rect", "gt_backward_rowstats", Q.device, m, n_cols, nnz, h, f, row_ptr, col_ind, val_ptr(val), col_ptr,
          row_ind, val_idx, Q, K, V, out, row_max, row_sum, grad, delta, dQ, dK, dV)
     return [dQ, dK, dV]
 
@@ -318,11 +333,11 @@ def _forward_bias(what, save_stats, row_ptr, col_ind, val, bias, Q, K, V):
     ext = _n.ext()
     if ext is not None:
         return ext.gt_fwd_bias(row_ptr, col_ind, val, bias, Q, K, V, val_ptr(val) is None, save_stats)
-    m, nnz, h, f = _checks(row_ptr, col_ind, Q, K, V, val=val)
+    m, n_cols, nnz, h, f = _checks_rect(row_ptr, col_ind, Q, K, V, val=val)
     _check_bias(Q, h, nnz, bias)
     out = torch.empty_like(Q)
     row_max, row_sum = (_empty(Q, m, h), _empty(Q, m, h)) if save_stats else (None, None)
-    call("dfgnn_gt_fwd_bias", what, Q.device, m, nnz, h, f, row_ptr, col_ind, val_ptr(val), bias, Q, K, V, row_max, row_sum,
+    call("dfgnn_gt_fwd_bias_rect", what, Q.device, m, n_cols, nnz, h, f, row_ptr, col_ind, val_ptr(val), bias, Q, K, V, row_max, row_sum,
          out)
     return [out, row_max, row_sum] if save_stats else [out]
 
@@ -349,14 +364,14 @@ def gt_backward_bias(row_ptr, col_ind, val, bias, col_ptr, row_ind, val_idx, Q, 
         res = ext.gt_bwd_bias(row_ptr, col_ind, val, bias, col_ptr, row_ind, val_idx, Q, K, V, out, row_max, row_sum, grad,
                               val_ptr(val) is None, need_dbias)
         return res if need_dbias else res + [None]
-    m, nnz, h, f = _checks(row_ptr, col_ind, Q, K, V, val=val, out=out, grad=grad)
+    m, n_cols, nnz, h, f = _checks_rect(row_ptr, col_ind, Q, K, V, val=val, out=out, grad=grad)
     _check_bias(Q, h, nnz, bias)
-    check_csc(Q, m, nnz, col_ptr, row_ind=row_ind, val_idx=val_idx)
+    check_csc_rect(Q, n_cols, nnz, col_ptr, "K / V", row_ind=row_ind, val_idx=val_idx)
     check_2d(Q, m, h, row_max=row_max, row_sum=row_sum)
     delta = _empty(Q, m, h)
     dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
     dbias = _empty(Q, h, nnz) if need_dbias else None
-    call("dfgnn_gt_bwd_bias", "gt_backward_bias", Q.device, m, nnz, h, f, row_ptr, col_ind, val_ptr(val), bias, col_ptr,
+    call("dfgnn_gt_bwd_bias_rect", "gt_backward_bias", Q.device, m, n_cols, nnz, h, f, row_ptr, col_ind, val_ptr(val), bias, col_ptr,
          row_ind, val_idx, Q, K, V, out, row_max, row_sum, grad, delta, dQ, dK, dV, dbias)
     return [dQ, dK, dV, dbias]
 
@@ -374,11 +389,11 @@ def _forward_edge(what, save_stats, row_ptr, col_ind, val, E, Q, K, V):
     ext = _n.ext()
     if ext is not None:
         return ext.gt_fwd_edge(row_ptr, col_ind, val, E, Q, K, V, val_ptr(val) is None, save_stats)
-    m, nnz, h, f = _checks(row_ptr, col_ind, Q, K, V, val=val)
+    m, n_cols, nnz, h, f = _checks_rect(row_ptr, col_ind, Q, K, V, val=val)
     _check_edge_feat(Q, nnz, h, f, E)
     out = torch.empty_like(Q)
     row_max, row_sum = (_empty(Q, m, h), _empty(Q, m, h)) if save_stats else (None, None)
-    call("dfgnn_gt_fwd_edge", what, Q.device, m, nnz, h, f, row_ptr, col_ind, val_ptr(val), E, Q, K, V, row_max, row_sum, out)
+    call("dfgnn_gt_fwd_edge_rect", what, Q.device, m, n_cols, nnz, h, f, row_ptr, col_ind, val_ptr(val), E, Q, K, V, row_max, row_sum, out)
     return [out, row_max, row_sum] if save_stats else [out]
 
 
@@ -404,14 +419,14 @@ def gt_backward_edge(row_ptr, col_ind, val, E, col_ptr, row_ind, val_idx, Q, K, 
         res = ext.gt_bwd_edge(row_ptr, col_ind, val, E, col_ptr, row_ind, val_idx, Q, K, V, out, row_max, row_sum, grad,
                               val_ptr(val) is None, need_dE)
         return res if need_dE else res + [None]
-    m, nnz, h, f = _checks(row_ptr, col_ind, Q, K, V, val=val, out=out, grad=grad)
+    m, n_cols, nnz, h, f = _checks_rect(row_ptr, col_ind, Q, K, V, val=val, out=out, grad=grad)
     _check_edge_feat(Q, nnz, h, f, E)
-    check_csc(Q, m, nnz, col_ptr, row_ind=row_ind, val_idx=val_idx)
+    check_csc_rect(Q, n_cols, nnz, col_ptr, "K / V", row_ind=row_ind, val_idx=val_idx)
     check_2d(Q, m, h, row_max=row_max, row_sum=row_sum)
     delta = _empty(Q, m, h)
     dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
     dE = torch.empty_like(E) if need_dE else None
-    call("dfgnn_gt_bwd_edge", "gt_backward_edge", Q.device, m, nnz, h, f, row_ptr, col_ind, val_ptr(val), E, col_ptr,
+    call("dfgnn_gt_bwd_edge_rect", "gt_backward_edge", Q.device, m, n_cols, nnz, h, f, row_ptr, col_ind, val_ptr(val), E, col_ptr,
          row_ind, val_idx, Q, K, V, out, row_max, row_sum, grad, delta, dQ, dK, dV, dE)
     return [dQ, dK, dV, dE]
 

@@ -95,6 +95,17 @@ size_t dfgnn_preprocess_ws_bytes(int m, int nnz);
 int dfgnn_preprocess_hyper(int m, int nnz, const void *src, const void *dst, int idx64, int *row_ptr,
                            int *col_ind, int *rows, int *edge_order, int *col_ptr, int *row_ind,
                            int *val_idx, void *ws, size_t ws_bytes, dfgnn_stream_t stream);
+/* The same for a RECTANGULAR graph of m rows and n_cols columns (a neighbour-sampled block, cross-attention): src ids are
+ * clamped to [0, m), dst ids to [0, n_cols); the row sort runs over the ceil(log2 m) low key bits, the column sort over
+ * ceil(log2 n_cols).  Extents:  row_ptr int32[m+1];  col_ptr int32[n_cols+1];  col_ind, rows, edge_order, row_ind, val_idx
+ * int32[nnz] as above.  ws: dfgnn_preprocess_ws_bytes_rect(m, n_cols, nnz, &bytes) bytes -- the larger of
+ * dfgnn_preprocess_ws_bytes(m, nnz) and dfgnn_preprocess_ws_bytes(n_cols, nnz); it returns 0 and writes *bytes (host), or a
+ * DFGNN_E_* code (a negative extent or bytes == NULL: BADARG).  nnz > 0 with m == 0 or n_cols == 0: DFGNN_E_BADARG.
+ * dfgnn_preprocess_hyper is this call with n_cols = m. */
+int dfgnn_preprocess_ws_bytes_rect(int m, int n_cols, int nnz, size_t *bytes);
+int dfgnn_preprocess_hyper_rect(int m, int n_cols, int nnz, const void *src, const void *dst, int idx64, int *row_ptr,
+                                int *col_ind, int *rows, int *edge_order, int *col_ptr, int *row_ind, int *val_idx,
+                                void *ws, size_t ws_bytes, dfgnn_stream_t stream);
 
 /* ---- GT (graph transformer) ------------------------------------------------------------------
  * replaces gt_hyper_inference  (DFGNN/src/fused_gtconv/fused_gtconv.cpp:278-314,
@@ -181,6 +192,34 @@ int dfgnn_gt_bwd_rowstats(int m, int nnz, int h, int f, const int *row_ptr, cons
                           const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q, const float *K,
                           const float *V, const float *out, const float *row_max, const float *row_sum,
                           const float *grad_out, float *delta, float *dQ, float *dK, float *dV, dfgnn_stream_t stream);
+/* RECTANGULAR graphs.  The four any-graph pairs -- the one above, its two variants below and GATv2 -- each have *_rect
+ * entries for a graph of m rows (queries, outputs) and n_cols columns (keys, values): what a neighbour-sampled block, a
+ * bipartite graph or cross-attention onto virtual nodes hands a layer as (x_src, x_dst).  Leading extents:
+ *   m          Q, out, grad_out, dQ            (GATv2: X_row, dX_row, out, grad_out)
+ *   [m, h]     row_max, row_sum, delta
+ *   n_cols     K, V, dK, dV                    (GATv2: X_col, dX_col)
+ *   m + 1      row_ptr
+ *   n_cols + 1 col_ptr
+ *   unchanged  the per-edge arrays: col_ind, val, bias[h, nnz], E[nnz, h, f], row_ind, val_idx
+ * col_ind[e] < n_cols and row_ind[t] < m are the caller's contract (as col_ind < m is for the square entries): the kernels
+ * gather by these ids without a check.  Everything else -- arithmetic, conventions, return codes -- is that of the square
+ * entry, which IS the *_rect entry with n_cols = m (same kernels, same grids, same bits).  Additionally:
+ *   DFGNN_E_BADARG       a negative extent; nnz > 0 with m == 0 or n_cols == 0 (an edge needs a row and a column)
+ *   DFGNN_E_UNSUPPORTED  h > 65535 or f outside the compiled range, as for the square entries (feature rows are addressed
+ *                        with 64-bit offsets: extent x h x f itself has no limit below the int32 extents)
+ * Degenerate extents launch no empty grid: m == 0 with n_cols > 0 -- the forward has nothing to write, the backward writes
+ * dK = dV = 0 in full (GATv2: dX_col = 0, dattn = 0); n_cols == 0 (then nnz == 0) -- out = 0, row_max = -1e38, row_sum = 0,
+ * dQ = 0.  The arrays of an empty side may be NULL.
+ * Each pass picks its form by the average degree of what it walks: forward and CSR pass a lane group per row when
+ * nnz < 8 m, the CSC pass a lane group per column when nnz < 8 n_cols (a fanout-10 block: a wave per row, a lane group
+ * per column). */
+int dfgnn_gt_fwd_rowstats_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind,
+                               const float *val, const float *Q, const float *K, const float *V, float *row_max,
+                               float *row_sum, float *out, dfgnn_stream_t stream);
+int dfgnn_gt_bwd_rowstats_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind,
+                               const float *val, const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q,
+                               const float *K, const float *V, const float *out, const float *row_max, const float *row_sum,
+                               const float *grad_out, float *delta, float *dQ, float *dK, float *dV, dfgnn_stream_t stream);
 
 /* The pair above with a per-edge, per-head ADDITIVE attention bias (csrc/gt_bias_train.hip): any graph, no plan, any f.
  *   s_e = val_e <Q_i, K_j> + bias[h, e],  P_e = exp(s_e - row_max_i) / row_sum_i,  out_i = sum_e P_e V_j
@@ -206,6 +245,15 @@ int dfgnn_gt_bwd_bias(int m, int nnz, int h, int f, const int *row_ptr, const in
                       const float *K, const float *V, const float *out, const float *row_max, const float *row_sum,
                       const float *grad_out, float *delta, float *dQ, float *dK, float *dV, float *dbias,
                       dfgnn_stream_t stream);
+/* ... for an m x n_cols graph (extents: see dfgnn_gt_fwd_rowstats_rect) */
+int dfgnn_gt_fwd_bias_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                           const float *bias, const float *Q, const float *K, const float *V, float *row_max,
+                           float *row_sum, float *out, dfgnn_stream_t stream);
+int dfgnn_gt_bwd_bias_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                           const float *bias, const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q,
+                           const float *K, const float *V, const float *out, const float *row_max, const float *row_sum,
+                           const float *grad_out, float *delta, float *dQ, float *dK, float *dV, float *dbias,
+                           dfgnn_stream_t stream);
 
 /* The general statistics pair with a per-edge FEATURE VECTOR added to keys and values (csrc/gt_edge_train.hip): any graph,
  * no plan, any f.  Edge e = (i, j) carries E_e in R^f per head; one E serves key and value (PyG's TransformerConv(edge_dim),
@@ -233,6 +281,15 @@ int dfgnn_gt_bwd_edge(int m, int nnz, int h, int f, const int *row_ptr, const in
                       const float *K, const float *V, const float *out, const float *row_max, const float *row_sum,
                       const float *grad_out, float *delta, float *dQ, float *dK, float *dV, float *dE,
                       dfgnn_stream_t stream);
+/* ... for an m x n_cols graph (extents: see dfgnn_gt_fwd_rowstats_rect) */
+int dfgnn_gt_fwd_edge_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                           const float *E, const float *Q, const float *K, const float *V, float *row_max, float *row_sum,
+                           float *out, dfgnn_stream_t stream);
+int dfgnn_gt_bwd_edge_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                           const float *E, const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q,
+                           const float *K, const float *V, const float *out, const float *row_max, const float *row_sum,
+                           const float *grad_out, float *delta, float *dQ, float *dK, float *dV, float *dE,
+                           dfgnn_stream_t stream);
 
 /* GATv2 convolution (csrc/gatv2_train.hip): fused inference and training pair for ANY graph, no plan, no degree limit,
  * any f.  The logit of edge (i, j) is neither rank-one (dfgnn_gat_*) nor a dot product (dfgnn_gt_*):
@@ -265,6 +322,16 @@ int dfgnn_gatv2_bwd(int m, int nnz, int h, int f, const int *row_ptr, const int 
                     const int *row_ind, const float *attn, float negative_slope, const float *X_row, const float *X_col,
                     const float *out, const float *row_max, const float *row_sum, const float *grad_out, float *delta,
                     float *ws, float *dX_row, float *dX_col, float *dattn, dfgnn_stream_t stream);
+/* ... for an m x n_cols graph: X_row, dX_row, out, grad_out fp32[m, h, f]; X_col, dX_col fp32[n_cols, h, f]; row_max,
+ * row_sum, delta fp32[m, h]; row_ptr int32[m+1], col_ptr int32[n_cols+1] (see dfgnn_gt_fwd_rowstats_rect).  The CSR pass
+ * keeps its bound of persistent workgroups, so `ws` is the same size. */
+int dfgnn_gatv2_fwd_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *attn,
+                         float negative_slope, const float *X_row, const float *X_col, float *row_max, float *row_sum,
+                         float *out, dfgnn_stream_t stream);
+int dfgnn_gatv2_bwd_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const int *col_ptr,
+                         const int *row_ind, const float *attn, float negative_slope, const float *X_row, const float *X_col,
+                         const float *out, const float *row_max, const float *row_sum, const float *grad_out, float *delta,
+                         float *ws, float *dX_row, float *dX_col, float *dattn, dfgnn_stream_t stream);
 
 /* weights[256 i + c] = val[e] for the edge e from node i to the c-th node of i's range of the plan, 0 elsewhere:
  * dfgnn_plan_dense_weights_floats(m) = 256 m floats (device, 16-byte aligned), written by one memset + one kernel on
