@@ -176,6 +176,52 @@ def GTConvFuse_inference_edge(row_ptr, col_ind, val, Q, K, V, E):
     return fused_gt.gt_inference_edge(row_ptr, col_ind, val, E, Q, K, V)
 
 
+class FusedGTFunction_typed(torch.autograd.Function):
+    """FusedGTFunction_edge with E_e = R[etype[e]] looked up in the kernels (include/dfgnn.h: dfgnn_gt_fwd_typed /
+    dfgnn_gt_bwd_typed, csrc/gt_typed_train.hip): R fp32[T, h, f], etype int32[nnz] in CSR edge order, etype_csc the same types
+    in CSC entry order (DFGNN.layers.preprocess_types).  Saved between forward and backward: Q, K, V, R, out, the row
+    statistics and the graph arrays (`val` only when it is not all ones) -- nothing of size nnz h f exists at any point.
+    dR[T, h, f] is computed (per-workgroup partial sums, a fixed-order reduction: no atomics) only when R requires a
+    gradient."""
+
+    @staticmethod
+    def forward(ctx, rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V, R, etype, etype_csc):
+        out_feat, row_max, row_sum = fused_gt.gt_forward_typed(row_ptr, col_ind, val, etype, R, Q, K, V)
+        keep_val = () if fused_gt.val_ptr(val) is None else (val,)
+        ctx.save_for_backward(row_ptr, col_ind, col_ptr, row_ind, val_idx, etype, etype_csc, Q, K, V, R, out_feat, row_max,
+                              row_sum, *keep_val)
+        return out_feat
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (row_ptr, col_ind, col_ptr, row_ind, val_idx, etype, etype_csc, Q, K, V, R, out_feat, row_max, row_sum,
+         *val) = ctx.saved_tensors
+        val = val[0] if val else None
+        grad_Q, grad_K, grad_V, grad_R = fused_gt.gt_backward_typed(
+            row_ptr, col_ind, val, etype, col_ptr, row_ind, val_idx, etype_csc, R, Q, K, V, out_feat, row_max, row_sum,
+            grad_out.contiguous(), need_dR=ctx.needs_input_grad[11])
+        return (None,) * 8 + (grad_Q, grad_K, grad_V, grad_R, None, None)
+
+
+def GTConvFuse_typed(rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V, R, etype, etype_csc):
+    """Differentiable conv of any graph with typed edges: R[etype[e]] (R fp32[T, h, f]) is added to the key and the value of
+    edge e; the argument list of GTConvFuse_rowstats plus `R`, `etype` and `etype_csc` (`rows` and `smem_consume` are
+    accepted and not used).
+    Where R needs a gradient and the table is beyond what the kernels reduce (fused_gt.gt_typed_dR_supported: T f <=
+    8192), this calls GTConvFuse_edge on the materialised R[etype]: the result is correct, but it allocates tensors of size
+    nnz h f and autograd reduces dE to dR with an atomic index_add, whose sum is not reproducible bit for bit."""
+    if R.requires_grad and torch.is_grad_enabled() and not fused_gt.gt_typed_dR_supported(R.shape[0], Q.shape[1], Q.shape[2]):
+        return GTConvFuse_edge(rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V,
+                               R[etype.long()])
+    return FusedGTFunction_typed.apply(
+        rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V, R, etype, etype_csc)
+
+
+def GTConvFuse_inference_typed(row_ptr, col_ind, val, Q, K, V, R, etype):
+    """Inference of any graph with typed edges: R[etype[e]] (R fp32[T, h, f]) added to keys and values; any T."""
+    return fused_gt.gt_inference_typed(row_ptr, col_ind, val, etype, R, Q, K, V)
+
+
 def GTConvFuse_inference_softmax(indptr, indices, rows, val, smem_consume, Q, K, V):
     """softmax: two kernels (COO SDDMM, then softmax + SpMM).  reference :238-259"""
     return fused_gt.gt_softmax_inference(indptr, indices, rows, val, smem_consume, Q, K, V)[0]

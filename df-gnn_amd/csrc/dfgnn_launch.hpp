@@ -231,6 +231,28 @@ int launch_gt_edge_bwd_rows(const Csr &g, const float *E, const float *Q, const 
 int launch_gt_edge_bwd_cols(const Csr &g, const float *E, const int *col_ptr, const int *row_ind, const int *val_idx,
                             const float *Q, const float *K, const float *V, const float *row_max, const float *row_sum,
                             const float *delta, const float *grad_out, float *dK, float *dV, hipStream_t s);
+// GT pair with typed edges (gt_typed_train.hip): launch_gt_edge_* with E_e = R[etype[e]], R [T, h, f], and never anything of
+// size nnz h f.  The CSC pass streams etype_csc (the types in CSC entry order) and reads val_idx only for edge values.  The
+// CSR pass with dR != NULL runs at most kGtTypedParts persistent workgroups per head, each storing one partial [T, h-slice,
+// f] to ws, and then reduces them into dR in a fixed order; it needs T f <= kGtTypedMaxTableFloats (a table per wave in
+// LDS) and answers kErrUnsupported beyond.  dR == NULL: the plain pass, any T, ws unused.
+constexpr int kGtTypedParts = 1024;            // per head (the grid is (parts, h)): 4 workgroups per CU on 256 CUs; LDS admits 5 at T f = 2048
+constexpr int kGtTypedMaxTableFloats = 8192;   // 4 waves x 32 KB = 128 KB of the CU's 160 KB
+struct GtTypedTable {
+  int T;
+  const int *etype, *etype_csc;  // [nnz] CSR order / CSC entry order
+  const float *R;                // [T, h, f]
+};
+bool gt_typed_table_fits(int T, int f);
+int launch_gt_typed_fwd(const Csr &g, const GtTypedTable &t, const float *Q, const float *K, const float *V,
+                        float *row_max, float *row_sum, float *out, hipStream_t s);
+int launch_gt_typed_bwd_rows(const Csr &g, const GtTypedTable &t, const float *Q, const float *K, const float *V,
+                             const float *out, const float *row_max, const float *row_sum, const float *grad_out,
+                             float *delta, float *dQ, float *ws, float *dR, hipStream_t s);
+int launch_gt_typed_bwd_cols(const Csr &g, const GtTypedTable &t, const int *col_ptr, const int *row_ind,
+                             const int *val_idx, const float *Q, const float *K, const float *V, const float *row_max,
+                             const float *row_sum, const float *delta, const float *grad_out, float *dK, float *dV,
+                             hipStream_t s);
 // GATv2 pair (gatv2_train.hip): any graph, no plan.  The forward saves row_max / row_sum [m, h] (both nullable: inference);
 // the backward is the CSR pass (delta, dX_row and at most kGatv2Parts partial sums [h, f] of dattn -> ws), the CSC pass
 // (dX_col) and the reduction of the partials into dattn, on one stream.

@@ -431,6 +431,81 @@ def gt_backward_edge(row_ptr, col_ind, val, E, col_ptr, row_ind, val_idx, Q, K, 
     return [dQ, dK, dV, dE]
 
 
+# ---- the general pair with typed edges (include/dfgnn.h: dfgnn_gt_fwd_typed / dfgnn_gt_bwd_typed) ------------------------
+# Not part of the reference's module.  The edge pair with E_e = R[etype[e]] (csrc/gt_typed_train.hip): R is fp32[T, h, f],
+# etype int32[nnz] in CSR edge order, etype_csc the same types in CSC entry order (etype[val_idx];
+# DFGNN.layers.preprocess_types makes both).  Nothing of size nnz h f exists; dR comes from per-workgroup partial sums and a
+# fixed-order reduction.  DFGNN.operators.fused_gtconv.GTConvFuse_typed takes it.
+
+
+def _check_typed(Q, nnz, h, f, R, **types):
+    """The table fp32[T >= 1, h, f] and the per-edge type arrays int32[nnz] -> T."""
+    check_edges(Q, nnz, torch.int32, **types)
+    check_family(Q, torch.float32, R=R)
+    if R.dim() != 3 or R.shape[0] < 1 or tuple(R.shape[1:]) != (h, f):
+        raise RuntimeError(f"R must have shape (T >= 1, {h}, {f}), got {tuple(R.shape)}")
+    return R.shape[0]
+
+
+def gt_typed_dR_supported(T, h, f):
+    """Whether gt_backward_typed computes dR for a table of T types at h heads of f features (include/dfgnn.h:
+    dfgnn_gt_typed_bwd_ws_floats; the limit is T f <= 8192).  The forward and the backward without dR take any T."""
+    return int(_n.lib().dfgnn_gt_typed_bwd_ws_floats(int(T), int(h), int(f))) > 0
+
+
+def _forward_typed(what, save_stats, row_ptr, col_ind, val, etype, R, Q, K, V):
+    ext = _n.ext()
+    if ext is not None:
+        return ext.gt_fwd_typed(row_ptr, col_ind, val, etype, R, Q, K, V, val_ptr(val) is None, save_stats)
+    m, n_cols, nnz, h, f = _checks_rect(row_ptr, col_ind, Q, K, V, val=val)
+    T = _check_typed(Q, nnz, h, f, R, etype=etype)
+    out = torch.empty_like(Q)
+    row_max, row_sum = (_empty(Q, m, h), _empty(Q, m, h)) if save_stats else (None, None)
+    call("dfgnn_gt_fwd_typed_rect", what, Q.device, m, n_cols, nnz, h, f, T, row_ptr, col_ind, val_ptr(val), etype, R, Q, K, V,
+         row_max, row_sum, out)
+    return [out, row_max, row_sum] if save_stats else [out]
+
+
+def gt_inference_typed(row_ptr, col_ind, val, etype, R, Q, K, V):
+    """-> out: inference of any graph with R[etype[e]] (R fp32[T, h, f], etype int32[nnz] in CSR order, 0 <= etype < T:
+    not checked here) added to keys and values.  val: edge values fp32[nnz] in CSR order; None or all ones: unit values."""
+    return _forward_typed("gt_inference_typed", False, row_ptr, col_ind, val, etype, R, Q, K, V)[0]
+
+
+def gt_forward_typed(row_ptr, col_ind, val, etype, R, Q, K, V):
+    """-> [out, row_max[m, h], row_sum[m, h]]: the training forward; an empty row has out = 0, row_max = -1e38,
+    row_sum = 0."""
+    return _forward_typed("gt_forward_typed", True, row_ptr, col_ind, val, etype, R, Q, K, V)
+
+
+def gt_backward_typed(row_ptr, col_ind, val, etype, col_ptr, row_ind, val_idx, etype_csc, R, Q, K, V, out, row_max, row_sum,
+                      grad, need_dR=True):
+    """-> [dQ, dK, dV, dR[T, h, f]] from the forward's output and row statistics; etype_csc = etype[val_idx].  dR is None
+    without need_dR (a frozen table: any T).  With need_dR the table must satisfy gt_typed_dR_supported, else the call
+    raises the library's "unsupported" RuntimeError before anything is launched."""
+    val_idx = as_int32(val_idx)
+    ext = _n.ext()
+    if ext is not None:
+        res = ext.gt_bwd_typed(row_ptr, col_ind, val, etype, col_ptr, row_ind, val_idx, etype_csc, R, Q, K, V, out, row_max,
+                               row_sum, grad, val_ptr(val) is None, need_dR)
+        return res if need_dR else res + [None]
+    m, n_cols, nnz, h, f = _checks_rect(row_ptr, col_ind, Q, K, V, val=val, out=out, grad=grad)
+    T = _check_typed(Q, nnz, h, f, R, etype=etype, etype_csc=etype_csc)
+    check_csc_rect(Q, n_cols, nnz, col_ptr, "K / V", row_ind=row_ind, val_idx=val_idx)
+    check_2d(Q, m, h, row_max=row_max, row_sum=row_sum)
+    ws = dR = None
+    if need_dR:
+        ws_floats = int(_n.lib().dfgnn_gt_typed_bwd_ws_floats(T, h, f))
+        if ws_floats < 0:
+            _n.check(ws_floats, "gt_backward_typed")
+        ws, dR = _empty(Q, ws_floats), torch.empty_like(R)
+    delta = _empty(Q, m, h)
+    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
+    call("dfgnn_gt_bwd_typed_rect", "gt_backward_typed", Q.device, m, n_cols, nnz, h, f, T, row_ptr, col_ind, val_ptr(val), etype,
+         col_ptr, row_ind, val_idx, etype_csc, R, Q, K, V, out, row_max, row_sum, grad, delta, ws, dQ, dK, dV, dR)
+    return [dQ, dK, dV, dR]
+
+
 # ---- the CSR-taking inference variants ----------------------------------------------------------------------------------
 _VARIANTS = ("gt_tiling", "gt_csr", "gt_csr_gm", "gt_softmax", "gt_softmax_gm")   # by `which` of torch_ext.cpp: gt_variant_fwd
 

@@ -291,6 +291,54 @@ int dfgnn_gt_bwd_edge_rect(int m, int n_cols, int nnz, int h, int f, const int *
                            const float *grad_out, float *delta, float *dQ, float *dK, float *dV, float *dE,
                            dfgnn_stream_t stream);
 
+/* The general statistics pair with TYPED edges (csrc/gt_typed_train.hip): any graph, no plan, any f.  The vector an edge
+ * adds to key and value is a row of a small table R[T, h, f], chosen by the edge's type (Shaw-style relative positions,
+ * RGAT / HGT-style relation vectors, bucketed distances, bond types).  With t = etype[e]:
+ *   k~_e = K_j + R_t,  v~_e = V_j + R_t,  s_e, P_e, out_i, delta_i, dS_e, dQ_i, dK_j, dV_j as in dfgnn_gt_*_edge
+ *   dR_t = sum_{e : etype[e] = t} (dS_e val_e Q_i + P_e grad_out_i)
+ * i.e. the edge pair on E = R[etype] with dR = index_add(dE, etype) -- out, the statistics, dQ, dK, dV are the edge pair's
+ * to the bit -- but an edge costs 4 bytes of type instead of 4 h f bytes of E, and nothing of size nnz h f is read or written.
+ *   T          number of types, >= 1
+ *   etype      int32[nnz] in CSR edge order, 0 <= etype < T (the caller's contract: not checked); duplicate edges each
+ *              carry their own type.  Required when nnz > 0
+ *   etype_csc  int32[nnz], the same types in CSC entry order: etype_csc[t] = etype[val_idx[t]].  Graph data, made once per
+ *              graph by the caller; the CSC pass streams it.  Required by the backward when nnz > 0
+ *   R          fp32[T, h, f]: the row of (type t, head) starts at (t h + head) f.  Required when nnz > 0
+ *   val        fp32[nnz], CSR order, NULL = unit values
+ *   val_idx    read only when val != NULL
+ *   dR         fp32[T, h, f], written in full (a type without an edge: zeros; m == 0 or nnz == 0: all zeros), or NULL: the
+ *              table is frozen, the CSR pass is the plain one with the edge pair's grid, any T, and ws is not used
+ *   ws         caller scratch of dfgnn_gt_typed_bwd_ws_floats(T, h, f) floats, 16-byte aligned; required when dR != NULL.
+ *              The CSR pass then runs a bounded number of persistent workgroups per head, each wave summing into a table
+ *              [T, f] of its own in LDS; a workgroup stores one partial per head to ws and a reduction in the same call
+ *              adds the partials in a fixed order.  No atomics: two calls give the same bits
+ *   row_max = row_sum = NULL in the forward: nothing is saved (inference)
+ * dfgnn_gt_typed_bwd_ws_floats: > 0 = the number of floats (independent of m and nnz); < 0 = a DFGNN_E_* code: BADARG for
+ * T < 1 or a negative size; UNSUPPORTED for h > 65535, for T f > 8192 (the LDS tables: 64 types at f = 128, 512 at f = 16)
+ * or a size that does not fit an int.  dfgnn_gt_bwd_typed with dR != NULL answers the same code before any launch.
+ * An empty row has out = 0, row_max = -1e38, row_sum = 0, dQ = 0.  Everything else as dfgnn_gt_fwd_edge / dfgnn_gt_bwd_edge;
+ * the _rect entries take an m x n_cols graph (extents: see dfgnn_gt_fwd_rowstats_rect) and the square ones are these with
+ * n_cols = m.  Nothing allocates or synchronises (capturable in a HIP graph).  With tables above 64 KB (T f > 4096) the first
+ * backward with dR of a process, per device and lane layout, raises the kernel's dynamic-LDS limit (hipFuncSetAttribute): run
+ * the step once before capturing it, as a warm-up does. */
+int dfgnn_gt_typed_bwd_ws_floats(int T, int h, int f);
+int dfgnn_gt_fwd_typed(int m, int nnz, int h, int f, int T, const int *row_ptr, const int *col_ind, const float *val,
+                       const int *etype, const float *R, const float *Q, const float *K, const float *V, float *row_max,
+                       float *row_sum, float *out, dfgnn_stream_t stream);
+int dfgnn_gt_bwd_typed(int m, int nnz, int h, int f, int T, const int *row_ptr, const int *col_ind, const float *val,
+                       const int *etype, const int *col_ptr, const int *row_ind, const int *val_idx, const int *etype_csc,
+                       const float *R, const float *Q, const float *K, const float *V, const float *out,
+                       const float *row_max, const float *row_sum, const float *grad_out, float *delta, float *ws, float *dQ,
+                       float *dK, float *dV, float *dR, dfgnn_stream_t stream);
+int dfgnn_gt_fwd_typed_rect(int m, int n_cols, int nnz, int h, int f, int T, const int *row_ptr, const int *col_ind,
+                            const float *val, const int *etype, const float *R, const float *Q, const float *K,
+                            const float *V, float *row_max, float *row_sum, float *out, dfgnn_stream_t stream);
+int dfgnn_gt_bwd_typed_rect(int m, int n_cols, int nnz, int h, int f, int T, const int *row_ptr, const int *col_ind,
+                            const float *val, const int *etype, const int *col_ptr, const int *row_ind, const int *val_idx,
+                            const int *etype_csc, const float *R, const float *Q, const float *K, const float *V,
+                            const float *out, const float *row_max, const float *row_sum, const float *grad_out,
+                            float *delta, float *ws, float *dQ, float *dK, float *dV, float *dR, dfgnn_stream_t stream);
+
 /* GATv2 convolution (csrc/gatv2_train.hip): fused inference and training pair for ANY graph, no plan, no degree limit,
  * any f.  The logit of edge (i, j) is neither rank-one (dfgnn_gat_*) nor a dot product (dfgnn_gt_*):
  *   z_e = X_row[i,h,:] + X_col[j,h,:],  s_e = sum_d attn[h,d] lrelu(z_e[d]),  lrelu(x) = x > 0 ? x : negative_slope x
