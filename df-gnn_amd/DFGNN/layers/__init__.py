@@ -3,6 +3,7 @@ from .GATv2 import GATv2Conv_forward, GATv2Conv_tiling, GATv2ConvDGL  # noqa: F4
 from .GT.gtconv_layer_bias import SparseMHA_bias  # noqa: F401
 from .GT.gtconv_layer_edge import SparseMHA_edge  # noqa: F401
 from .GT.gtconv_layer_typed import SparseMHA_typed, preprocess_types  # noqa: F401
+from .GT.gtconv_layer_tbias import SparseMHA_tbias  # noqa: F401
 from .GT.gtconv_layer_forward import SparseMHA_forward  # noqa: F401
 from .GT.gtconv_layer_rowstats import SparseMHA_rowstats  # noqa: F401
 from .model import Model, choose_Inproj  # noqa: F401

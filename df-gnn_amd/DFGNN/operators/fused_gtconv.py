@@ -222,6 +222,52 @@ def GTConvFuse_inference_typed(row_ptr, col_ind, val, Q, K, V, R, etype):
     return fused_gt.gt_inference_typed(row_ptr, col_ind, val, etype, R, Q, K, V)
 
 
+class FusedGTFunction_tbias(torch.autograd.Function):
+    """FusedGTFunction_bias with bias[hd, e] = B[etype[e], hd] looked up in the kernels (include/dfgnn.h: dfgnn_gt_fwd_tbias /
+    dfgnn_gt_bwd_tbias, csrc/gt_tbias_train.hip): B fp32[T, h], etype int32[nnz] in CSR edge order, etype_csc the same types
+    in CSC entry order (DFGNN.layers.preprocess_types).  Saved between forward and backward: Q, K, V, B, out, the row
+    statistics and the graph arrays (`val` only when it is not all ones) -- nothing of size h nnz exists at any point.
+    dB[T, h] is computed (per-workgroup partial sums, a fixed-order reduction: no atomics) only when B requires a
+    gradient."""
+
+    @staticmethod
+    def forward(ctx, rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V, B, etype, etype_csc):
+        out_feat, row_max, row_sum = fused_gt.gt_forward_tbias(row_ptr, col_ind, val, etype, B, Q, K, V)
+        keep_val = () if fused_gt.val_ptr(val) is None else (val,)
+        ctx.save_for_backward(row_ptr, col_ind, col_ptr, row_ind, val_idx, etype, etype_csc, Q, K, V, B, out_feat, row_max,
+                              row_sum, *keep_val)
+        return out_feat
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (row_ptr, col_ind, col_ptr, row_ind, val_idx, etype, etype_csc, Q, K, V, B, out_feat, row_max, row_sum,
+         *val) = ctx.saved_tensors
+        val = val[0] if val else None
+        grad_Q, grad_K, grad_V, grad_B = fused_gt.gt_backward_tbias(
+            row_ptr, col_ind, val, etype, col_ptr, row_ind, val_idx, etype_csc, B, Q, K, V, out_feat, row_max, row_sum,
+            grad_out.contiguous(), need_dB=ctx.needs_input_grad[11])
+        return (None,) * 8 + (grad_Q, grad_K, grad_V, grad_B, None, None)
+
+
+def GTConvFuse_tbias(rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V, B, etype, etype_csc):
+    """Differentiable conv of any graph with a typed attention bias: B[etype[e], hd] (B fp32[T, h]; -inf masks a type for a
+    head) is added to the logit of edge e before the softmax; the argument list of GTConvFuse_rowstats plus `B`, `etype` and
+    `etype_csc` (`rows` and `smem_consume` are accepted and not used).
+    Where B needs a gradient and the table is beyond what the kernels reduce (fused_gt.gt_tbias_dB_supported: T <= 4096),
+    this calls GTConvFuse_bias on the materialised B[etype].t(): the result is correct, but it allocates tensors of size
+    h nnz and autograd reduces dbias to dB with an atomic index_add, whose sum is not reproducible bit for bit."""
+    if B.requires_grad and torch.is_grad_enabled() and not fused_gt.gt_tbias_dB_supported(B.shape[0], Q.shape[1]):
+        return GTConvFuse_bias(rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V,
+                               B[etype.long()].t().contiguous())
+    return FusedGTFunction_tbias.apply(
+        rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V, B, etype, etype_csc)
+
+
+def GTConvFuse_inference_tbias(row_ptr, col_ind, val, Q, K, V, B, etype):
+    """Inference of any graph with a typed attention bias: B[etype[e], hd] (B fp32[T, h]) added to the logits; any T."""
+    return fused_gt.gt_inference_tbias(row_ptr, col_ind, val, etype, B, Q, K, V)
+
+
 def GTConvFuse_inference_softmax(indptr, indices, rows, val, smem_consume, Q, K, V):
     """softmax: two kernels (COO SDDMM, then softmax + SpMM).  reference :238-259"""
     return fused_gt.gt_softmax_inference(indptr, indices, rows, val, smem_consume, Q, K, V)[0]

@@ -436,6 +436,65 @@ int dfgnn_gt_bwd_typed(int m, int nnz, int h, int f, int T, const int *row_ptr, 
                                  K, V, out, row_max, row_sum, grad_out, delta, ws, dQ, dK, dV, dR, stream);
 }
 
+// ---- the general statistics pair with a typed attention bias: scalars looked up from a table (gt_tbias_train.hip) --------
+int dfgnn_gt_tbias_bwd_ws_floats(int T, int h) {
+  if (T < 1 || h < 0) return kErrBadArg;
+  if (h > 65535 || T > kGtTBiasMaxTypes) return kErrUnsupported;
+  const long long n = (long long)gt_tbias_parts(T) * T * (h > 0 ? h : 1);
+  return n > 0x7fffffffLL ? kErrUnsupported : (int)n;
+}
+
+int dfgnn_gt_fwd_tbias_rect(int m, int n_cols, int nnz, int h, int f, int T, const int *row_ptr, const int *col_ind,
+                            const float *val, const int *etype, const float *B, const float *Q, const float *K,
+                            const float *V, float *row_max, float *row_sum, float *out, dfgnn_stream_t stream) {
+  if (T < 1) return kErrBadArg;
+  if (int c = check_rect(m, n_cols, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (m == 0) return 0;  // (no row: nothing to write)
+  if (!Q || !out || (n_cols > 0 && (!K || !V)) || (!row_max != !row_sum)) return kErrBadArg;  // (both statistics or neither: inference)
+  if (nnz > 0 && (!etype || !B)) return kErrBadArg;
+  const Csr g = rect_csr(m, n_cols, nnz, h, f, row_ptr, col_ind, val);
+  return launch_gt_tbias_fwd(g, GtTBiasTable{T, etype, nullptr, B}, Q, K, V, row_max, row_sum, out, as_stream(stream));
+}
+
+int dfgnn_gt_fwd_tbias(int m, int nnz, int h, int f, int T, const int *row_ptr, const int *col_ind, const float *val,
+                       const int *etype, const float *B, const float *Q, const float *K, const float *V, float *row_max,
+                       float *row_sum, float *out, dfgnn_stream_t stream) {
+  return dfgnn_gt_fwd_tbias_rect(m, m, nnz, h, f, T, row_ptr, col_ind, val, etype, B, Q, K, V, row_max, row_sum, out, stream);
+}
+
+int dfgnn_gt_bwd_tbias_rect(int m, int n_cols, int nnz, int h, int f, int T, const int *row_ptr, const int *col_ind,
+                            const float *val, const int *etype, const int *col_ptr, const int *row_ind, const int *val_idx,
+                            const int *etype_csc, const float *B, const float *Q, const float *K, const float *V,
+                            const float *out, const float *row_max, const float *row_sum, const float *grad_out,
+                            float *delta, float *ws, float *dQ, float *dK, float *dV, float *dB, dfgnn_stream_t stream) {
+  if (T < 1) return kErrBadArg;
+  const int c = check_rect(m, n_cols, nnz, h, f, row_ptr, col_ind);
+  if (c < 0) return c;
+  if (dB) {  // (the partials of dB are the only use of ws)
+    if (!ws) return kErrBadArg;
+    if (int n = dfgnn_gt_tbias_bwd_ws_floats(T, h); n < 0) return n;
+  }
+  if (c > 0 && (!dB || h == 0)) return 0;  // (neither rows nor columns: dB = 0 is still written, below)
+  if (m > 0 && (!Q || !out || !row_max || !row_sum || !grad_out || !delta || !dQ)) return kErrBadArg;
+  if (n_cols > 0 && (!K || !V || !dK || !dV || !col_ptr)) return kErrBadArg;
+  if (c == 0 && nnz > 0 && (!etype || !etype_csc || !B || !row_ind || (val && !val_idx))) return kErrBadArg;  // (unit values never read val_idx)
+  const Csr g = rect_csr(m, n_cols, nnz, h, f, row_ptr, col_ind, val);
+  const GtTBiasTable t{T, etype, etype_csc, B};
+  if (int rc = launch_gt_tbias_bwd_rows(g, t, Q, K, V, out, row_max, row_sum, grad_out, delta, dQ, ws, dB, as_stream(stream)))
+    return rc;
+  return launch_gt_tbias_bwd_cols(g, t, col_ptr, row_ind, val_idx, Q, K, V, row_max, row_sum, delta, grad_out, dK, dV,
+                                  as_stream(stream));
+}
+
+int dfgnn_gt_bwd_tbias(int m, int nnz, int h, int f, int T, const int *row_ptr, const int *col_ind, const float *val,
+                       const int *etype, const int *col_ptr, const int *row_ind, const int *val_idx, const int *etype_csc,
+                       const float *B, const float *Q, const float *K, const float *V, const float *out,
+                       const float *row_max, const float *row_sum, const float *grad_out, float *delta, float *ws, float *dQ,
+                       float *dK, float *dV, float *dB, dfgnn_stream_t stream) {
+  return dfgnn_gt_bwd_tbias_rect(m, m, nnz, h, f, T, row_ptr, col_ind, val, etype, col_ptr, row_ind, val_idx, etype_csc, B, Q,
+                                 K, V, out, row_max, row_sum, grad_out, delta, ws, dQ, dK, dV, dB, stream);
+}
+
 // ---- GATv2 (gatv2_train.hip): fused inference and training pair, any graph ------------------------------------------------
 int dfgnn_gatv2_bwd_ws_floats(int h, int f) {
   if (h < 0 || f < 0) return kErrBadArg;

@@ -253,6 +253,28 @@ int launch_gt_typed_bwd_cols(const Csr &g, const GtTypedTable &t, const int *col
                              const int *val_idx, const float *Q, const float *K, const float *V, const float *row_max,
                              const float *row_sum, const float *delta, const float *grad_out, float *dK, float *dV,
                              hipStream_t s);
+// GT pair with a typed attention bias (gt_tbias_train.hip): launch_gt_bias_* with bias[hd, e] = B[etype[e], hd], B [T, h],
+// and never anything of size h nnz.  The CSC pass streams etype_csc (the types in CSC entry order) and reads val_idx only
+// for edge values.  The CSR pass with dB != NULL runs at most gt_tbias_parts(T) persistent workgroups per head, each
+// storing one partial [T, h-slice] to ws, and then reduces them into dB in a fixed order; it needs T <= kGtTBiasMaxTypes
+// (a table per wave in LDS) and answers kErrUnsupported beyond.  dB == NULL: the plain pass, any T, ws unused.
+constexpr int kGtTBiasParts = 1024;      // per head (the grid is (parts, h)): 4 workgroups per CU on 256 CUs
+constexpr int kGtTBiasMaxTypes = 4096;   // 4 waves x 16 KB = 64 KB, the default limit of dynamic LDS: no attribute call
+struct GtTBiasTable {
+  int T;
+  const int *etype, *etype_csc;  // [nnz] CSR order / CSC entry order
+  const float *B;                // [T, h]
+};
+int gt_tbias_parts(int T);  // partials per head that ws holds: min(kGtTBiasParts, 256 x the workgroups a CU's LDS admits)
+int launch_gt_tbias_fwd(const Csr &g, const GtTBiasTable &t, const float *Q, const float *K, const float *V,
+                        float *row_max, float *row_sum, float *out, hipStream_t s);
+int launch_gt_tbias_bwd_rows(const Csr &g, const GtTBiasTable &t, const float *Q, const float *K, const float *V,
+                             const float *out, const float *row_max, const float *row_sum, const float *grad_out,
+                             float *delta, float *dQ, float *ws, float *dB, hipStream_t s);
+int launch_gt_tbias_bwd_cols(const Csr &g, const GtTBiasTable &t, const int *col_ptr, const int *row_ind,
+                             const int *val_idx, const float *Q, const float *K, const float *V, const float *row_max,
+                             const float *row_sum, const float *delta, const float *grad_out, float *dK, float *dV,
+                             hipStream_t s);
 // GATv2 pair (gatv2_train.hip): any graph, no plan.  The forward saves row_max / row_sum [m, h] (both nullable: inference);
 // the backward is the CSR pass (delta, dX_row and at most kGatv2Parts partial sums [h, f] of dattn -> ws), the CSC pass
 // (dX_col) and the reduction of the partials into dattn, on one stream.

@@ -462,6 +462,70 @@ std::vector<Tensor> gt_bwd_typed(const Tensor &row_ptr, const Tensor &col_ind, c
   return {dQ, dK, dV, dR};
 }
 
+// ---- the general pair with a typed attention bias (include/dfgnn.h: dfgnn_gt_fwd_tbias / dfgnn_gt_bwd_tbias) -------------
+// etype: int32 [nnz] in CSR edge order; B: fp32 [T, h] -> T
+int tbias_checks(const Dims &d, const Tensor &ref, const Tensor &etype, const Tensor &B) {
+  check_i32(etype, "etype");
+  TORCH_CHECK(etype.dim() == 1 && etype.size(0) == d.nnz, "etype must have shape (", d.nnz, ",), got ", shape_str(etype));
+  check_f32(B, "B");
+  TORCH_CHECK(B.dim() == 2 && B.size(0) >= 1 && B.size(1) == d.h, "B must have shape (T >= 1, ", d.h, "), got ", shape_str(B));
+  check_same_device(ref, {&etype, &B});
+  return (int)B.size(0);
+}
+
+// save_stats = false: inference (-> {out})
+std::vector<Tensor> gt_fwd_tbias(const Tensor &row_ptr, const Tensor &col_ind, const c10::optional<Tensor> &val, const Tensor &etype,
+                                 const Tensor &B, const Tensor &Q, const Tensor &K, const Tensor &V, bool unit_val, bool save_stats) {
+  const Dims d = gt_rect_checks(row_ptr, col_ind, opt(val), Q, K, V);
+  const int T = tbias_checks(d, Q, etype, B);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
+  Tensor out = torch::empty_like(Q);
+  Tensor row_max, row_sum;
+  if (save_stats) {
+    row_max = torch::empty({d.m, d.h}, Q.options());
+    row_sum = torch::empty({d.m, d.h}, Q.options());
+  }
+  check_rc(dfgnn_gt_fwd_tbias_rect(d.m, d.n_cols, d.nnz, d.h, d.f, T, i32(row_ptr), i32(col_ind), edge_val_ptr(val, unit_val),
+                                   i32(etype), f32(B), f32(Q), f32(K), f32(V), f32(row_max), f32(row_sum), f32(out), cur_stream()),
+           save_stats ? "gt_forward_tbias" : "gt_inference_tbias");
+  if (!save_stats) return {out};
+  return {out, row_max, row_sum};
+}
+
+// -> {dQ, dK, dV, dB}, or {dQ, dK, dV} without need_dB
+std::vector<Tensor> gt_bwd_tbias(const Tensor &row_ptr, const Tensor &col_ind, const c10::optional<Tensor> &val, const Tensor &etype,
+                                 const Tensor &col_ptr, const Tensor &row_ind, const Tensor &val_idx, const Tensor &etype_csc,
+                                 const Tensor &B, const Tensor &Q, const Tensor &K, const Tensor &V, const Tensor &out,
+                                 const Tensor &row_max, const Tensor &row_sum, const Tensor &grad, bool unit_val, bool need_dB) {
+  const Dims d = gt_rect_checks(row_ptr, col_ind, opt(val), Q, K, V);
+  const int T = tbias_checks(d, Q, etype, B);
+  csc_rect_checks(d, Q, col_ptr, row_ind, &val_idx, "K / V");
+  check_i32(etype_csc, "etype_csc");
+  TORCH_CHECK(etype_csc.dim() == 1 && etype_csc.size(0) == d.nnz, "etype_csc must have shape (", d.nnz, ",), got ",
+              shape_str(etype_csc));
+  check_feat3(out, Q, "out");
+  check_feat3(grad, Q, "grad");
+  row_stats_checks(d, Q, row_max, row_sum);
+  check_same_device(Q, {&etype_csc, &out, &grad});
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
+  Tensor ws, dB;
+  if (need_dB) {
+    const int ws_floats = dfgnn_gt_tbias_bwd_ws_floats(T, d.h);
+    check_rc(ws_floats < 0 ? ws_floats : 0, "gt_backward_tbias");
+    ws = torch::empty({(int64_t)ws_floats}, Q.options());
+    dB = torch::empty_like(B);
+  }
+  Tensor delta = torch::empty({d.m, d.h}, Q.options());
+  Tensor dQ = torch::empty_like(Q), dK = torch::empty_like(K), dV = torch::empty_like(V);
+  check_rc(dfgnn_gt_bwd_tbias_rect(d.m, d.n_cols, d.nnz, d.h, d.f, T, i32(row_ptr), i32(col_ind), edge_val_ptr(val, unit_val),
+                                   i32(etype), i32(col_ptr), i32(row_ind), i32(val_idx), i32(etype_csc), f32(B), f32(Q), f32(K),
+                                   f32(V), f32(out), f32(row_max), f32(row_sum), f32(grad), f32(delta), f32(ws), f32(dQ),
+                                   f32(dK), f32(dV), f32(dB), cur_stream()),
+           "gt_backward_tbias");
+  if (!need_dB) return {dQ, dK, dV};
+  return {dQ, dK, dV, dB};
+}
+
 // ---- the attn_edge pair in rank order (include/dfgnn.h: dfgnn_gt_hyper_fwd_ranked / dfgnn_gt_bwd_ranked) ----------------
 std::vector<Tensor> gt_hyper_fwd_ranked(const Tensor &row_ptr, const Tensor &col_ind, const Tensor &Q, const Tensor &K,
                                         const Tensor &V, int64_t plan, int64_t meta) {
@@ -775,6 +839,8 @@ PYBIND11_MODULE(_dfgnn_ext, m) {
   m.def("gt_bwd_edge", &gt_bwd_edge, "fused GT conv backward of any graph with a per-edge feature vector in keys and values");
   m.def("gt_fwd_typed", &gt_fwd_typed, "fused GT conv forward of any graph with typed edges: key / value vectors from a table");
   m.def("gt_bwd_typed", &gt_bwd_typed, "fused GT conv backward of any graph with typed edges: key / value vectors from a table");
+  m.def("gt_fwd_tbias", &gt_fwd_tbias, "fused GT conv forward of any graph with a typed attention bias: scalars from a table");
+  m.def("gt_bwd_tbias", &gt_bwd_tbias, "fused GT conv backward of any graph with a typed attention bias: scalars from a table");
   m.def("gt_hyper_fwd_ranked", &gt_hyper_fwd_ranked, "fused GT conv 'hyper' training forward, attention values in rank order");
   m.def("gt_bwd_ranked", &gt_bwd_ranked, "fused GT conv backward from rank-ordered attention values");
   m.def("plan_dense_weights", &plan_dense_weights, "edge values of a plan's dense ranges in dense form (dfgnn_plan_dense_weights)");

@@ -51,6 +51,11 @@ SIGNATURES = {
     "dfgnn_gt_bwd_typed": [_i] * 5 + [_vp] * 23,
     "dfgnn_gt_fwd_typed_rect": [_i] * 6 + [_vp] * 12,
     "dfgnn_gt_bwd_typed_rect": [_i] * 6 + [_vp] * 23,
+    "dfgnn_gt_tbias_bwd_ws_floats": [_i, _i],
+    "dfgnn_gt_fwd_tbias": [_i] * 5 + [_vp] * 12,
+    "dfgnn_gt_bwd_tbias": [_i] * 5 + [_vp] * 23,
+    "dfgnn_gt_fwd_tbias_rect": [_i] * 6 + [_vp] * 12,
+    "dfgnn_gt_bwd_tbias_rect": [_i] * 6 + [_vp] * 23,
     "dfgnn_gatv2_fwd_rect": [_i] * 5 + [_vp] * 3 + [_f] + [_vp] * 6,
     "dfgnn_gatv2_bwd_rect": [_i] * 5 + [_vp] * 5 + [_f] + [_vp] * 12,
     "dfgnn_gt_bwd_rows": [_i, _i, _i, _i] + [_vp] * 11,

@@ -506,6 +506,82 @@ def gt_backward_typed(row_ptr, col_ind, val, etype, col_ptr, row_ind, val_idx, e
     return [dQ, dK, dV, dR]
 
 
+# ---- the general pair with a typed attention bias (include/dfgnn.h: dfgnn_gt_fwd_tbias / dfgnn_gt_bwd_tbias) --------------
+# Not part of the reference's module.  The bias pair with bias[hd, e] = B[etype[e], hd] (csrc/gt_tbias_train.hip): B is
+# fp32[T, h] (an embedding weight's layout), etype int32[nnz] in CSR edge order, etype_csc the same types in CSC entry order
+# (etype[val_idx]; DFGNN.layers.preprocess_types makes both).  Nothing of size h nnz exists; dB comes from per-workgroup
+# partial sums and a fixed-order reduction.  DFGNN.operators.fused_gtconv.GTConvFuse_tbias takes it.
+
+
+def _check_tbias(Q, nnz, h, B, **types):
+    """The table fp32[T >= 1, h] and the per-edge type arrays int32[nnz] -> T."""
+    check_edges(Q, nnz, torch.int32, **types)
+    check_family(Q, torch.float32, B=B)
+    if B.dim() != 2 or B.shape[0] < 1 or B.shape[1] != h:
+        raise RuntimeError(f"B must have shape (T >= 1, {h}), got {tuple(B.shape)}")
+    return B.shape[0]
+
+
+def gt_tbias_dB_supported(T, h):
+    """Whether gt_backward_tbias computes dB for a table of T types at h heads (include/dfgnn.h:
+    dfgnn_gt_tbias_bwd_ws_floats; the limit is T <= 4096).  The forward and the backward without dB take any T."""
+    return int(_n.lib().dfgnn_gt_tbias_bwd_ws_floats(int(T), int(h))) > 0
+
+
+def _forward_tbias(what, save_stats, row_ptr, col_ind, val, etype, B, Q, K, V):
+    ext = _n.ext()
+    if ext is not None:
+        return ext.gt_fwd_tbias(row_ptr, col_ind, val, etype, B, Q, K, V, val_ptr(val) is None, save_stats)
+    m, n_cols, nnz, h, f = _checks_rect(row_ptr, col_ind, Q, K, V, val=val)
+    T = _check_tbias(Q, nnz, h, B, etype=etype)
+    out = torch.empty_like(Q)
+    row_max, row_sum = (_empty(Q, m, h), _empty(Q, m, h)) if save_stats else (None, None)
+    call("dfgnn_gt_fwd_tbias_rect", what, Q.device, m, n_cols, nnz, h, f, T, row_ptr, col_ind, val_ptr(val), etype, B, Q, K, V,
+         row_max, row_sum, out)
+    return [out, row_max, row_sum] if save_stats else [out]
+
+
+def gt_inference_tbias(row_ptr, col_ind, val, etype, B, Q, K, V):
+    """-> out: inference of any graph with B[etype[e], hd] (B fp32[T, h], etype int32[nnz] in CSR order, 0 <= etype < T:
+    not checked here) added to the logit of edge e before the softmax; -inf masks a type for a head.  val: edge values
+    fp32[nnz] in CSR order; None or all ones: unit values."""
+    return _forward_tbias("gt_inference_tbias", False, row_ptr, col_ind, val, etype, B, Q, K, V)[0]
+
+
+def gt_forward_tbias(row_ptr, col_ind, val, etype, B, Q, K, V):
+    """-> [out, row_max[m, h], row_sum[m, h]]: the training forward; an empty or fully masked row has out = 0,
+    row_max = -1e38, row_sum = 0."""
+    return _forward_tbias("gt_forward_tbias", True, row_ptr, col_ind, val, etype, B, Q, K, V)
+
+
+def gt_backward_tbias(row_ptr, col_ind, val, etype, col_ptr, row_ind, val_idx, etype_csc, B, Q, K, V, out, row_max, row_sum,
+                      grad, need_dB=True):
+    """-> [dQ, dK, dV, dB[T, h]] from the forward's output and row statistics; etype_csc = etype[val_idx].  dB is None
+    without need_dB (a frozen table: any T).  With need_dB the table must satisfy gt_tbias_dB_supported, else the call
+    raises the library's "unsupported" RuntimeError before anything is launched."""
+    val_idx = as_int32(val_idx)
+    ext = _n.ext()
+    if ext is not None:
+        res = ext.gt_bwd_tbias(row_ptr, col_ind, val, etype, col_ptr, row_ind, val_idx, etype_csc, B, Q, K, V, out, row_max,
+                               row_sum, grad, val_ptr(val) is None, need_dB)
+        return res if need_dB else res + [None]
+    m, n_cols, nnz, h, f = _checks_rect(row_ptr, col_ind, Q, K, V, val=val, out=out, grad=grad)
+    T = _check_tbias(Q, nnz, h, B, etype=etype, etype_csc=etype_csc)
+    check_csc_rect(Q, n_cols, nnz, col_ptr, "K / V", row_ind=row_ind, val_idx=val_idx)
+    check_2d(Q, m, h, row_max=row_max, row_sum=row_sum)
+    ws = dB = None
+    if need_dB:
+        ws_floats = int(_n.lib().dfgnn_gt_tbias_bwd_ws_floats(T, h))
+        if ws_floats < 0:
+            _n.check(ws_floats, "gt_backward_tbias")
+        ws, dB = _empty(Q, ws_floats), torch.empty_like(B)
+    delta = _empty(Q, m, h)
+    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
+    call("dfgnn_gt_bwd_tbias_rect", "gt_backward_tbias", Q.device, m, n_cols, nnz, h, f, T, row_ptr, col_ind, val_ptr(val), etype,
+         col_ptr, row_ind, val_idx, etype_csc, B, Q, K, V, out, row_max, row_sum, grad, delta, ws, dQ, dK, dV, dB)
+    return [dQ, dK, dV, dB]
+
+
 # ---- the CSR-taking inference variants ----------------------------------------------------------------------------------
 _VARIANTS = ("gt_tiling", "gt_csr", "gt_csr_gm", "gt_softmax", "gt_softmax_gm")   # by `which` of torch_ext.cpp: gt_variant_fwd
 

@@ -339,6 +339,57 @@ int dfgnn_gt_bwd_typed_rect(int m, int n_cols, int nnz, int h, int f, int T, con
                             const float *out, const float *row_max, const float *row_sum, const float *grad_out,
                             float *delta, float *ws, float *dQ, float *dK, float *dV, float *dR, dfgnn_stream_t stream);
 
+/* The general statistics pair with a TYPED attention bias (csrc/gt_tbias_train.hip): any graph, no plan, any f.  The scalar
+ * an edge adds to its logit is an entry of a small table B[T, h], chosen by the edge's type (Graphormer's spatial encoding,
+ * T5 / Swin-style relative-position bias, any bucketed-distance or edge-type bias).  With t = etype[e], per head hd:
+ *   s_e = val_e <Q_i, K_j> + B[t, hd],  P_e, out_i, delta_i, dS_e, dQ_i, dK_j, dV_j as in dfgnn_gt_*_bias
+ *   dB[t, hd] = sum_{e : etype[e] = t} dS_e
+ * i.e. the bias pair on bias[hd, e] = B[etype[e], hd] with dB = index_add(dbias.t(), etype) -- out, the statistics, dQ, dK,
+ * dV are the bias pair's to the bit -- but an edge costs 4 bytes of type per pass instead of 4 h bytes of bias, and nothing
+ * of size h nnz is read or written.
+ *   T          number of types, >= 1
+ *   etype      int32[nnz] in CSR edge order, 0 <= etype < T (the caller's contract: not checked); duplicate edges each
+ *              carry their own type.  Required when nnz > 0
+ *   etype_csc  int32[nnz], the same types in CSC entry order: etype_csc[t] = etype[val_idx[t]].  Graph data, made once per
+ *              graph by the caller; the CSC pass streams it.  Required by the backward when nnz > 0
+ *   B          fp32[T, h] (the layout of an embedding weight): the bias of (type t, head) is B[t h + head].  -inf masks
+ *              every edge of that type for that head: P_e = 0, dB[t, head] = 0, and a (row, head) whose edges are all masked
+ *              is an empty row (out = 0, row_max = -1e38, row_sum = 0, dQ = 0); no output holds a NaN or an inf.  +inf and
+ *              NaN are the caller's error.  Required when nnz > 0
+ *   val        fp32[nnz], CSR order, NULL = unit values
+ *   val_idx    read only when val != NULL
+ *   dB         fp32[T, h], written in full (a type without an edge: zeros; m == 0 or nnz == 0: all zeros), or NULL: the
+ *              table is frozen, the CSR pass is the plain one with the bias pair's grid, any T, and ws is not used
+ *   ws         caller scratch of dfgnn_gt_tbias_bwd_ws_floats(T, h) floats; required when dB != NULL.  The CSR pass then
+ *              runs a bounded number of persistent workgroups per head, each wave summing into a table of T floats of its
+ *              own in LDS; a workgroup stores one partial per head to ws and a reduction in the same call adds the partials
+ *              in a fixed order.  No atomics: two calls give the same bits
+ *   row_max = row_sum = NULL in the forward: nothing is saved (inference)
+ * dfgnn_gt_tbias_bwd_ws_floats: > 0 = the number of floats, P(T) T max(h, 1) with P(T) = 1024 partials per head up to
+ * T = 2560, 768 up to 3413, 512 up to 4096 (independent of m and nnz); < 0 = a DFGNN_E_* code: BADARG for T < 1 or a
+ * negative h; UNSUPPORTED for h > 65535 and for T > 4096 (four wave tables of T floats in the 64 KB of dynamic LDS a kernel
+ * gets without an attribute call).  dfgnn_gt_bwd_tbias with dB != NULL answers the same code before any launch.
+ * Everything else as dfgnn_gt_fwd_bias / dfgnn_gt_bwd_bias; the _rect entries take an m x n_cols graph (extents: see
+ * dfgnn_gt_fwd_rowstats_rect) and the square ones are these with n_cols = m.  Nothing allocates or synchronises, and no call
+ * sets a function attribute: a step is capturable in a HIP graph without a warm-up. */
+int dfgnn_gt_tbias_bwd_ws_floats(int T, int h);
+int dfgnn_gt_fwd_tbias(int m, int nnz, int h, int f, int T, const int *row_ptr, const int *col_ind, const float *val,
+                       const int *etype, const float *B, const float *Q, const float *K, const float *V, float *row_max,
+                       float *row_sum, float *out, dfgnn_stream_t stream);
+int dfgnn_gt_bwd_tbias(int m, int nnz, int h, int f, int T, const int *row_ptr, const int *col_ind, const float *val,
+                       const int *etype, const int *col_ptr, const int *row_ind, const int *val_idx, const int *etype_csc,
+                       const float *B, const float *Q, const float *K, const float *V, const float *out,
+                       const float *row_max, const float *row_sum, const float *grad_out, float *delta, float *ws, float *dQ,
+                       float *dK, float *dV, float *dB, dfgnn_stream_t stream);
+int dfgnn_gt_fwd_tbias_rect(int m, int n_cols, int nnz, int h, int f, int T, const int *row_ptr, const int *col_ind,
+                            const float *val, const int *etype, const float *B, const float *Q, const float *K,
+                            const float *V, float *row_max, float *row_sum, float *out, dfgnn_stream_t stream);
+int dfgnn_gt_bwd_tbias_rect(int m, int n_cols, int nnz, int h, int f, int T, const int *row_ptr, const int *col_ind,
+                            const float *val, const int *etype, const int *col_ptr, const int *row_ind, const int *val_idx,
+                            const int *etype_csc, const float *B, const float *Q, const float *K, const float *V,
+                            const float *out, const float *row_max, const float *row_sum, const float *grad_out,
+                            float *delta, float *ws, float *dQ, float *dK, float *dV, float *dB, dfgnn_stream_t stream);
+
 /* GATv2 convolution (csrc/gatv2_train.hip): fused inference and training pair for ANY graph, no plan, no degree limit,
  * any f.  The logit of edge (i, j) is neither rank-one (dfgnn_gat_*) nor a dot product (dfgnn_gt_*):
  *   z_e = X_row[i,h,:] + X_col[j,h,:],  s_e = sum_d attn[h,d] lrelu(z_e[d]),  lrelu(x) = x > 0 ? x : negative_slope x
