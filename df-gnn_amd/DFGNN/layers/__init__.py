@@ -1,5 +1,5 @@
 from .AGNN import AGNNConv_forward  # noqa: F401
-from .GATv2 import GATv2Conv_forward, GATv2Conv_tiling, GATv2ConvDGL  # noqa: F401
+from .GATv2 import GATv2Conv_edge, GATv2Conv_forward, GATv2Conv_tiling, GATv2ConvDGL  # noqa: F401
 from .GT.gtconv_layer_bias import SparseMHA_bias  # noqa: F401
 from .GT.gtconv_layer_edge import SparseMHA_edge  # noqa: F401
 from .GT.gtconv_layer_typed import SparseMHA_typed, preprocess_types  # noqa: F401

@@ -20,7 +20,7 @@ from .AGNN import (AGNNConv_csr, AGNNConv_csr_gm, AGNNConv_hyper, AGNNConv_softm
 from .GAT_DOT import DOTGATConv_csr, DOTGATConv_hyper, DOTGATConv_softmax
 from .GAT import (GATConv_dgNN, GATConv_hyper, GATConv_hyper_ablation, GATConv_hyper_recompute, GATConv_hyper_v2,
                   GATConv_softmax, GATConv_softmax_gm, GATConv_tiling)
-from .GATv2 import GATv2Conv_forward, GATv2Conv_tiling
+from .GATv2 import GATv2Conv_edge_timing, GATv2Conv_forward, GATv2Conv_tiling
 from .GT import (SparseMHA_bias_timing, SparseMHA_CSR, SparseMHA_CSR_GM, SparseMHA_edge_timing, SparseMHA_forward_timing,
                  SparseMHA_hyper, SparseMHA_rowstats_timing, SparseMHA_softmax, SparseMHA_softmax_gm, SparseMHA_tbias_timing,
                  SparseMHA_tiling, SparseMHA_typed_timing)
@@ -144,8 +144,10 @@ _AGNN_LAYERS = {  # reference :424-442
     "tiling": AGNNConv_tiling, "softmax_gm": AGNNConv_softmax_gm,
 }
 # this build's addition (the reference has no GATv2): one fused kernel family serves any graph, so the CSR-taking formats
-# all name the inference layer; "forward" is the training layer on the fused pair
-_GATV2_LAYERS = {"tiling": GATv2Conv_tiling, "csr": GATv2Conv_tiling, "forward": GATv2Conv_forward}
+# all name the inference layer; "forward" is the training layer on the fused pair, "forward_edge" the one with per-edge feature
+# vectors inside the LeakyReLU (seeded random here)
+_GATV2_LAYERS = {"tiling": GATv2Conv_tiling, "csr": GATv2Conv_tiling, "forward": GATv2Conv_forward,
+                 "forward_edge": GATv2Conv_edge_timing}
 _DOTGAT_LAYERS = {"hyper": DOTGATConv_hyper, "csr": DOTGATConv_csr, "softmax": DOTGATConv_softmax}
 # formats of the reference that are baselines on NVIDIA-only libraries or paper experiments
 _OUT_OF_SCOPE = {"hybrid", "pyg", "cugraph", "subgraph"}

@@ -110,3 +110,39 @@ class FusedGATv2Function(torch.autograd.Function):
 
 def GATv2ConvFuse(attn, row_ptr, col_ind, col_ptr, row_ind, negative_slope, X_row, X_col):
     return FusedGATv2Function.apply(attn, row_ptr, col_ind, col_ptr, row_ind, negative_slope, X_row, X_col)
+
+
+# ---- GATv2 with per-edge feature vectors (fused_gatconv.gatv2_*_edge): logits a^T LeakyReLU(X_row[i] + X_col[j] + E_e) ----
+def GATv2ConvFuse_inference_edge(attn, row_ptr, col_ind, negative_slope, X_row, X_col, E):
+    """-> out[m, h, f]; E fp32 [nnz, heads, feat] in CSR edge order, added inside the LeakyReLU and not part of the message
+    (PyG's GATv2Conv(edge_dim))."""
+    return fused_gat.gatv2_inference_edge(attn, row_ptr, col_ind, negative_slope, X_row, X_col, E)
+
+
+class FusedGATv2Function_edge(torch.autograd.Function):
+    """FusedGATv2Function with E[nnz, heads, feat] inside the LeakyReLU (include/dfgnn.h: dfgnn_gatv2_fwd_edge /
+    dfgnn_gatv2_bwd_edge, csrc/gatv2_edge_train.hip).  Saved between forward and backward: attn, X_row, X_col, E, out, the row
+    statistics and the graph arrays -- nothing of size nnz h f beyond E itself.  dE[nnz, heads, feat] is computed only when E
+    requires a gradient; otherwise the backward allocates and writes nothing of that size."""
+
+    @staticmethod
+    def forward(ctx, attn, row_ptr, col_ind, col_ptr, row_ind, val_idx, negative_slope, X_row, X_col, E):
+        out, row_max, row_sum = fused_gat.gatv2_forward_edge(attn, row_ptr, col_ind, negative_slope, X_row, X_col, E)
+        ctx.save_for_backward(row_ptr, col_ind, col_ptr, row_ind, val_idx, attn, X_row, X_col, E, out, row_max, row_sum)
+        ctx.negative_slope = negative_slope
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        row_ptr, col_ind, col_ptr, row_ind, val_idx, attn, X_row, X_col, E, out, row_max, row_sum = ctx.saved_tensors
+        dX_row, dX_col, dattn, dE = fused_gat.gatv2_backward_edge(
+            ctx.negative_slope, row_ptr, col_ind, col_ptr, row_ind, val_idx, attn, X_row, X_col, E, out, row_max, row_sum,
+            grad_out.contiguous(), want_dE=ctx.needs_input_grad[9])
+        # (one tensor passed as both X_row and X_col: autograd adds the two gradients)
+        return dattn, None, None, None, None, None, None, dX_row, dX_col, dE
+
+
+def GATv2ConvFuse_edge(attn, row_ptr, col_ind, col_ptr, row_ind, val_idx, negative_slope, X_row, X_col, E):
+    """Differentiable GATv2 conv of any graph with the edge features fp32[nnz, h, f] (CSR edge order) inside the LeakyReLU;
+    the argument list of GATv2ConvFuse plus `val_idx` (the CSR position of each CSC entry) and `E`."""
+    return FusedGATv2Function_edge.apply(attn, row_ptr, col_ind, col_ptr, row_ind, val_idx, negative_slope, X_row, X_col, E)

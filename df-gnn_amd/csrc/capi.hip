@@ -544,6 +544,52 @@ int dfgnn_gatv2_bwd(int m, int nnz, int h, int f, const int *row_ptr, const int 
                               row_max, row_sum, grad_out, delta, ws, dX_row, dX_col, dattn, stream);
 }
 
+// ---- GATv2 with a per-edge feature vector inside the LeakyReLU (gatv2_edge_train.hip) ---------------------------------------
+int dfgnn_gatv2_fwd_edge_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind,
+                              const float *attn, float negative_slope, const float *X_row, const float *X_col, const float *E,
+                              float *row_max, float *row_sum, float *out, dfgnn_stream_t stream) {
+  if (int c = check_rect(m, n_cols, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (m == 0) return 0;  // (no row: nothing to write)
+  if (!attn || !X_row || (n_cols > 0 && !X_col) || !out || (!row_max != !row_sum)) return kErrBadArg;  // (both statistics or neither)
+  if (nnz > 0 && !E) return kErrBadArg;
+  const Csr g = rect_csr(m, n_cols, nnz, h, f, row_ptr, col_ind, nullptr);
+  return launch_gatv2_edge_fwd(g, Gatv2Graph{nullptr, nullptr, attn, negative_slope}, X_row, X_col, E, row_max, row_sum, out,
+                               as_stream(stream));
+}
+
+int dfgnn_gatv2_fwd_edge(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *attn,
+                         float negative_slope, const float *X_row, const float *X_col, const float *E, float *row_max,
+                         float *row_sum, float *out, dfgnn_stream_t stream) {
+  return dfgnn_gatv2_fwd_edge_rect(m, m, nnz, h, f, row_ptr, col_ind, attn, negative_slope, X_row, X_col, E, row_max, row_sum,
+                                   out, stream);
+}
+
+int dfgnn_gatv2_bwd_edge_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind,
+                              const int *col_ptr, const int *row_ind, const int *val_idx, const float *attn,
+                              float negative_slope, const float *X_row, const float *X_col, const float *E, const float *out,
+                              const float *row_max, const float *row_sum, const float *grad_out, float *delta, float *ws,
+                              float *dX_row, float *dX_col, float *dattn, float *dE, dfgnn_stream_t stream) {
+  if (int c = check_rect(m, n_cols, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (!attn || !ws || !dattn) return kErrBadArg;
+  if (nnz > 0 && (!E || !row_ind || !val_idx)) return kErrBadArg;  // (the CSC pass finds an entry's E row through val_idx)
+  if (m > 0 && (!X_row || !out || !row_max || !row_sum || !grad_out || !delta || !dX_row)) return kErrBadArg;
+  if (n_cols > 0 && (!X_col || !dX_col || !col_ptr)) return kErrBadArg;
+  if (dX_row && dX_row == dX_col) return kErrBadArg;  // (the two passes each write their buffer in full)
+  if (dfgnn_gatv2_bwd_ws_floats(h, f) < 0) return kErrUnsupported;
+  const Csr g = rect_csr(m, n_cols, nnz, h, f, row_ptr, col_ind, nullptr);
+  return launch_gatv2_edge_bwd(g, Gatv2Graph{col_ptr, row_ind, attn, negative_slope}, val_idx, X_row, X_col, E, out, row_max,
+                               row_sum, grad_out, delta, ws, dX_row, dX_col, dattn, dE, as_stream(stream));
+}
+
+int dfgnn_gatv2_bwd_edge(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const int *col_ptr,
+                         const int *row_ind, const int *val_idx, const float *attn, float negative_slope, const float *X_row,
+                         const float *X_col, const float *E, const float *out, const float *row_max, const float *row_sum,
+                         const float *grad_out, float *delta, float *ws, float *dX_row, float *dX_col, float *dattn,
+                         float *dE, dfgnn_stream_t stream) {
+  return dfgnn_gatv2_bwd_edge_rect(m, m, nnz, h, f, row_ptr, col_ind, col_ptr, row_ind, val_idx, attn, negative_slope, X_row,
+                                   X_col, E, out, row_max, row_sum, grad_out, delta, ws, dX_row, dX_col, dattn, dE, stream);
+}
+
 int dfgnn_gt_tiling_fwd(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
                         const float *Q, const float *K, const float *V, float *out, dfgnn_stream_t stream) {
   if (int c = check_common(m, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;

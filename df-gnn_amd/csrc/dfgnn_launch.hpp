@@ -289,6 +289,15 @@ int launch_gatv2_fwd(const Csr &g, const Gatv2Graph &v, const float *X_row, cons
 int launch_gatv2_bwd(const Csr &g, const Gatv2Graph &v, const float *X_row, const float *X_col, const float *out,
                      const float *row_max, const float *row_sum, const float *grad_out, float *delta, float *ws,
                      float *dX_row, float *dX_col, float *dattn, hipStream_t s);
+// GATv2 pair with a per-edge feature vector inside the LeakyReLU (gatv2_edge_train.hip): launch_gatv2_* with E [nnz, h, f]
+// (CSR order), z_e = X_row_i + X_col_j + E_e.  The CSR pass also writes dE [nnz, h, f] in full when it is not null; the CSC
+// pass gathers E rows through val_idx, which it therefore always reads.  `ws` as for launch_gatv2_bwd.
+int launch_gatv2_edge_fwd(const Csr &g, const Gatv2Graph &v, const float *X_row, const float *X_col, const float *E,
+                          float *row_max, float *row_sum, float *out, hipStream_t s);
+int launch_gatv2_edge_bwd(const Csr &g, const Gatv2Graph &v, const int *val_idx, const float *X_row, const float *X_col,
+                          const float *E, const float *out, const float *row_max, const float *row_sum,
+                          const float *grad_out, float *delta, float *ws, float *dX_row, float *dX_col, float *dattn,
+                          float *dE, hipStream_t s);
 // graphs with fewer than kBlockMinAvgDegree edges per row on average take the row-per-lane-group kernels.  The pairs that
 // take an m x n_cols graph ask per pass: (m, nnz) for the forward and the CSR pass, (n_cols, nnz) for the CSC pass
 inline bool low_degree(int m, int nnz) { return (long)nnz < (long)kBlockMinAvgDegree * m; }

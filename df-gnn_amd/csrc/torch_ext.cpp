@@ -745,6 +745,91 @@ std::vector<Tensor> gatv2_bwd(double slope, const Tensor &row_ptr, const Tensor 
   return {dX_row, dX_col, dattn};
 }
 
+// ---- GATv2 with a per-edge feature vector inside the LeakyReLU (include/dfgnn.h: dfgnn_gatv2_fwd_edge / dfgnn_gatv2_bwd_edge) ----
+// a dtype as Python prints it, so that a dtype error reads the same through either transport (_binding_util._family)
+std::string py_dtype(const Tensor &t) {
+  switch (t.scalar_type()) {
+    case torch::kInt32: return "torch.int32";
+    case torch::kInt64: return "torch.int64";
+    case torch::kFloat32: return "torch.float32";
+    case torch::kFloat64: return "torch.float64";
+    case torch::kFloat16: return "torch.float16";
+    case torch::kBFloat16: return "torch.bfloat16";
+    default: return std::string("torch.") + c10::toString(t.scalar_type());
+  }
+}
+// the CSR arrays' dtype, named and worded as the ctypes transport does (check_csr); everything else: gatv2_checks
+void gatv2_edge_csr_dtype(const Tensor &row_ptr, const Tensor &col_ind) {
+  TORCH_CHECK(!row_ptr.is_cuda() || !row_ptr.is_contiguous() || row_ptr.scalar_type() == torch::kInt32,
+              "indptr must have dtype torch.int32, got ", py_dtype(row_ptr));
+  TORCH_CHECK(!col_ind.is_cuda() || !col_ind.is_contiguous() || col_ind.scalar_type() == torch::kInt32,
+              "indices must have dtype torch.int32, got ", py_dtype(col_ind));
+}
+// E: fp32 [nnz, h, f] in CSR edge order
+void gatv2_edge_feat_checks(const Dims &d, const Tensor &ref, const Tensor &E) {
+  check_cuda_contig(E, "E");
+  TORCH_CHECK(E.scalar_type() == torch::kFloat32, "E must have dtype torch.float32, got ", py_dtype(E));
+  TORCH_CHECK(E.dim() == 3 && E.size(0) == d.nnz && E.size(1) == d.h && E.size(2) == d.f, "E must have shape (", d.nnz, ", ",
+              d.h, ", ", d.f, "), got ", shape_str(E));
+  check_same_device(ref, {&E});
+}
+
+// save_stats = false: inference -> {out}; else the training forward -> {out, row_max, row_sum}
+std::vector<Tensor> gatv2_fwd_edge(const Tensor &attn, const Tensor &row_ptr, const Tensor &col_ind, double slope,
+                                   const Tensor &X_row, const Tensor &X_col, const Tensor &E, bool save_stats) {
+  gatv2_edge_csr_dtype(row_ptr, col_ind);
+  const Dims d = gatv2_checks(attn, row_ptr, col_ind, X_row, X_col);
+  gatv2_edge_feat_checks(d, X_row, E);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(X_row.device());
+  Tensor out = torch::empty_like(X_row);
+  Tensor row_max, row_sum;
+  if (save_stats) {
+    row_max = torch::empty({d.m, d.h}, X_row.options());
+    row_sum = torch::empty({d.m, d.h}, X_row.options());
+  }
+  check_rc(dfgnn_gatv2_fwd_edge_rect(d.m, d.n_cols, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), f32(attn), (float)slope, f32(X_row),
+                                     f32(X_col), f32(E), f32(row_max), f32(row_sum), f32(out), cur_stream()),
+           save_stats ? "gatv2_forward_edge" : "gatv2_inference_edge");
+  if (!save_stats) return {out};
+  return {out, row_max, row_sum};
+}
+
+// -> {dX_row, dX_col, dattn, dE}, or {dX_row, dX_col, dattn} without want_dE
+std::vector<Tensor> gatv2_bwd_edge(double slope, const Tensor &row_ptr, const Tensor &col_ind, const Tensor &col_ptr,
+                                   const Tensor &row_ind, const Tensor &val_idx, const Tensor &attn, const Tensor &X_row,
+                                   const Tensor &X_col, const Tensor &E, const Tensor &out, const Tensor &row_max,
+                                   const Tensor &row_sum, const Tensor &grad, bool want_dE) {
+  gatv2_edge_csr_dtype(row_ptr, col_ind);
+  const Dims d = gatv2_checks(attn, row_ptr, col_ind, X_row, X_col);
+  gatv2_edge_feat_checks(d, X_row, E);
+  csc_rect_checks(d, X_row, col_ptr, row_ind, &val_idx, "X_col");
+  check_feat3(out, X_row, "out");
+  check_feat3(grad, X_row, "grad");
+  row_stats_checks(d, X_row, row_max, row_sum);
+  check_same_device(X_row, {&out, &grad});
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(X_row.device());
+  Tensor dX_row = torch::empty_like(X_row), dX_col = torch::empty_like(X_col);
+  Tensor dE;
+  if (want_dE) dE = torch::empty_like(E);
+  std::vector<Tensor> res;
+  if (d.m == 0 && d.n_cols == 0) {  // (nothing to launch: no edge adds to dattn)
+    res = {dX_row, dX_col, torch::zeros_like(attn)};
+  } else {
+    const int ws_floats = dfgnn_gatv2_bwd_ws_floats(d.h, d.f);
+    check_rc(ws_floats < 0 ? ws_floats : 0, "gatv2_backward_edge");
+    Tensor delta = torch::empty({d.m, d.h}, X_row.options()), ws = torch::empty({(int64_t)ws_floats}, X_row.options());
+    Tensor dattn = torch::empty_like(attn);
+    check_rc(dfgnn_gatv2_bwd_edge_rect(d.m, d.n_cols, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), i32(col_ptr), i32(row_ind),
+                                       i32(val_idx), f32(attn), (float)slope, f32(X_row), f32(X_col), f32(E), f32(out), f32(row_max),
+                                       f32(row_sum), f32(grad), f32(delta), f32(ws), f32(dX_row), f32(dX_col), f32(dattn), f32(dE),
+                                       cur_stream()),
+             "gatv2_backward_edge");
+    res = {dX_row, dX_col, dattn};
+  }
+  if (want_dE) res.push_back(dE);
+  return res;
+}
+
 // fused_gtconv.cpp:244-276 (tiling), :174-242 (csr, csr_gm), :316-389 (softmax, softmax_gm): the GT inference variants that
 // take CSR (+ the COO rows for the two-kernel forms).  which: 0 tiling, 1 csr, 2 csr_gm, 3 softmax, 4 softmax_gm
 Tensor gt_variant_fwd(int64_t which, const Tensor &indptr, const Tensor &indices, const c10::optional<Tensor> &rows, const Tensor &val,
@@ -851,6 +936,8 @@ PYBIND11_MODULE(_dfgnn_ext, m) {
   m.def("gat_bwd", &gat_bwd, "fused GAT conv backward");
   m.def("gatv2_fwd", &gatv2_fwd, "fused GATv2 conv forward of any graph (inference, or training with row statistics)");
   m.def("gatv2_bwd", &gatv2_bwd, "fused GATv2 conv backward of any graph from the forward's output and row statistics");
+  m.def("gatv2_fwd_edge", &gatv2_fwd_edge, "fused GATv2 conv forward of any graph with a per-edge feature vector inside the LeakyReLU");
+  m.def("gatv2_bwd_edge", &gatv2_bwd_edge, "fused GATv2 conv backward of any graph with a per-edge feature vector inside the LeakyReLU");
   m.def("gt_variant_fwd", &gt_variant_fwd, "fused GT conv inference: tiling / csr / csr_gm / softmax / softmax_gm");
   m.def("plan_build", &plan_build, "block plan of a CSR structure (dfgnn_plan_build)");
   m.def("preprocess_hyper", &preprocess_hyper, "COO -> CSR / COO rows / CSC on the GPU (dfgnn_preprocess_hyper)");

@@ -11,7 +11,7 @@ tensors from the training forward; its schedule argument only distributes work a
 import torch
 
 import dfgnn_native as _n
-from _binding_util import (_KeyedCache, as_int32, call, check_2d, check_cols, check_csc, check_csc_rect, check_csr, check_edges,
+from _binding_util import (_KeyedCache, as_int32, call, check_2d, check_3d, check_cols, check_csc, check_csc_rect, check_csr, check_edges,
                            check_family, check_feats, get_plan_obj, get_rows, plan_ptrs)
 
 # Set to False to force the general (plan-less) kernels; results are identical either way.
@@ -330,3 +330,63 @@ def gatv2_backward(negative_slope, row_ptr, col_ind, col_ptr, row_ind, attn, X_r
     call("dfgnn_gatv2_bwd_rect", "gatv2_backward", X_row.device, m, n_cols, nnz, h, f, row_ptr, col_ind, col_ptr, row_ind, attn,
          float(negative_slope), X_row, X_col, out, row_max, row_sum, grad, delta, ws, dX_row, dX_col, dattn)
     return [dX_row, dX_col, dattn]
+
+
+# ---- GATv2 with a per-edge feature vector inside the LeakyReLU (include/dfgnn.h: dfgnn_gatv2_fwd_edge / dfgnn_gatv2_bwd_edge) ---
+# Not part of the reference's module.  The pair above with z_e = X_row[i] + X_col[j] + E_e (csrc/gatv2_edge_train.hip), what
+# PyG's GATv2Conv(edge_dim) computes: E is fp32[nnz, h, f] in CSR edge order and is not part of the message.
+# DFGNN.operators.fused_gatconv.GATv2ConvFuse_edge takes it.
+
+
+def _gatv2_fwd_edge(what, save_stats, attn, row_ptr, col_ind, negative_slope, X_row, X_col, E):
+    ext = _n.ext()
+    if ext is not None:
+        return ext.gatv2_fwd_edge(attn, row_ptr, col_ind, float(negative_slope), X_row, X_col, E, save_stats)
+    m, n_cols, nnz, h, f = _check_v2(attn, row_ptr, col_ind, X_row, X_col)
+    check_3d(X_row, nnz, h, f, E=E)
+    out = torch.empty_like(X_row)
+    row_max, row_sum = (_empty(X_row, m, h), _empty(X_row, m, h)) if save_stats else (None, None)
+    call("dfgnn_gatv2_fwd_edge_rect", what, X_row.device, m, n_cols, nnz, h, f, row_ptr, col_ind, attn, float(negative_slope),
+         X_row, X_col, E, row_max, row_sum, out)
+    return [out, row_max, row_sum] if save_stats else [out]
+
+
+def gatv2_inference_edge(attn, row_ptr, col_ind, negative_slope, X_row, X_col, E):
+    """-> out[m, h, f] with the edge features fp32[nnz, h, f] (CSR order) added inside the LeakyReLU.  X_row and X_col may be
+    the same tensor (shared weights)."""
+    return _gatv2_fwd_edge("gatv2_inference_edge", False, attn, row_ptr, col_ind, negative_slope, X_row, X_col, E)[0]
+
+
+def gatv2_forward_edge(attn, row_ptr, col_ind, negative_slope, X_row, X_col, E):
+    """-> [out, row_max[m, h], row_sum[m, h]]: the training forward; the same `out` as gatv2_inference_edge."""
+    return _gatv2_fwd_edge("gatv2_forward_edge", True, attn, row_ptr, col_ind, negative_slope, X_row, X_col, E)
+
+
+def gatv2_backward_edge(negative_slope, row_ptr, col_ind, col_ptr, row_ind, val_idx, attn, X_row, X_col, E, out, row_max,
+                        row_sum, grad, want_dE=True):
+    """-> [dX_row, dX_col, dattn[h, f], dE[nnz, h, f]] from the forward's output and row statistics (each edge is
+    recomputed); dE is None without want_dE (then nothing of size nnz h f is allocated or written).  val_idx: the CSR
+    position of each CSC entry, through which the column pass finds an entry's row of E."""
+    if val_idx is None:
+        raise RuntimeError("gatv2_backward_edge: val_idx is required (the column pass finds an entry's row of E through it)")
+    val_idx = as_int32(val_idx)
+    ext = _n.ext()
+    if ext is not None:
+        res = ext.gatv2_bwd_edge(float(negative_slope), row_ptr, col_ind, col_ptr, row_ind, val_idx, attn, X_row, X_col, E, out,
+                                 row_max, row_sum, grad, want_dE)
+        return res if want_dE else res + [None]
+    m, n_cols, nnz, h, f = _check_v2(attn, row_ptr, col_ind, X_row, X_col, out=out, grad=grad)
+    check_3d(X_row, nnz, h, f, E=E)
+    check_csc_rect(X_row, n_cols, nnz, col_ptr, "X_col", row_ind=row_ind, val_idx=val_idx)
+    check_2d(X_row, m, h, row_max=row_max, row_sum=row_sum)
+    dX_row, dX_col = torch.empty_like(X_row), torch.empty_like(X_col)
+    dE = torch.empty_like(E) if want_dE else None
+    if m == 0 and n_cols == 0:
+        return [dX_row, dX_col, torch.zeros_like(attn), dE]    # (nothing to launch: no edge adds to dattn)
+    ws_floats = int(_n.lib().dfgnn_gatv2_bwd_ws_floats(h, f))
+    if ws_floats < 0:
+        _n.check(ws_floats, "gatv2_backward_edge")
+    delta, ws, dattn = _empty(X_row, m, h), _empty(X_row, ws_floats), torch.empty_like(attn)
+    call("dfgnn_gatv2_bwd_edge_rect", "gatv2_backward_edge", X_row.device, m, n_cols, nnz, h, f, row_ptr, col_ind, col_ptr, row_ind,
+         val_idx, attn, float(negative_slope), X_row, X_col, E, out, row_max, row_sum, grad, delta, ws, dX_row, dX_col, dattn, dE)
+    return [dX_row, dX_col, dattn, dE]

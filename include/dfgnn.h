@@ -432,6 +432,38 @@ int dfgnn_gatv2_bwd_rect(int m, int n_cols, int nnz, int h, int f, const int *ro
                          const float *out, const float *row_max, const float *row_sum, const float *grad_out, float *delta,
                          float *ws, float *dX_row, float *dX_col, float *dattn, dfgnn_stream_t stream);
 
+/* GATv2 with a per-edge FEATURE VECTOR inside the LeakyReLU (csrc/gatv2_edge_train.hip): the pair above with E, what PyG's
+ * GATv2Conv(edge_dim) computes with E = lin_edge(edge_attr) viewed [nnz, h, f]:
+ *   z_e = X_row[i,h,:] + X_col[j,h,:] + E[e,h,:],  s_e, P_e as above,  out[i,h,:] = sum_e P_e X_col[j,h,:]  (E is NOT in
+ *   the message),  g_e, dX_row, dX_col, dattn as above with this z_e,  dE[e,h,:] = g_e
+ *   E        fp32[nnz, h, f] in CSR edge order (the feature layout with the edge in place of the node: the row of
+ *            (edge e, head) starts at (e h + head) f); required when nnz > 0.  Duplicate edges each have their own row
+ *   dE       fp32[nnz, h, f], every slot written by plain stores (no pre-zeroing), or NULL: E needs no gradient and nothing
+ *            of size nnz h f is written
+ *   val_idx  int32[nnz], the CSR position of each CSC entry; required when nnz > 0: the CSC pass finds an entry's E row
+ *            through it
+ *   ws       dfgnn_gatv2_bwd_ws_floats(h, f) floats, as above
+ * E and dE take part in the float4 path's alignment rule (f % 4 == 0 and every base 16-byte aligned), as for
+ * dfgnn_gt_fwd_edge.  With E = 0 every output equals the pair above bit for bit.  Everything else as there: empty rows and
+ * columns, X_row == X_col, the size limits (DFGNN_E_UNSUPPORTED), no atomics, nothing allocates or synchronises.  The
+ * square entries are the n_cols = m case of the *_rect ones. */
+int dfgnn_gatv2_fwd_edge(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *attn,
+                         float negative_slope, const float *X_row, const float *X_col, const float *E, float *row_max,
+                         float *row_sum, float *out, dfgnn_stream_t stream);
+int dfgnn_gatv2_bwd_edge(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const int *col_ptr,
+                         const int *row_ind, const int *val_idx, const float *attn, float negative_slope, const float *X_row,
+                         const float *X_col, const float *E, const float *out, const float *row_max, const float *row_sum,
+                         const float *grad_out, float *delta, float *ws, float *dX_row, float *dX_col, float *dattn,
+                         float *dE, dfgnn_stream_t stream);
+int dfgnn_gatv2_fwd_edge_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind,
+                              const float *attn, float negative_slope, const float *X_row, const float *X_col, const float *E,
+                              float *row_max, float *row_sum, float *out, dfgnn_stream_t stream);
+int dfgnn_gatv2_bwd_edge_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind,
+                              const int *col_ptr, const int *row_ind, const int *val_idx, const float *attn,
+                              float negative_slope, const float *X_row, const float *X_col, const float *E, const float *out,
+                              const float *row_max, const float *row_sum, const float *grad_out, float *delta, float *ws,
+                              float *dX_row, float *dX_col, float *dattn, float *dE, dfgnn_stream_t stream);
+
 /* weights[256 i + c] = val[e] for the edge e from node i to the c-th node of i's range of the plan, 0 elsewhere:
  * dfgnn_plan_dense_weights_floats(m) = 256 m floats (device, 16-byte aligned), written by one memset + one kernel on
  * `stream`.  val: fp32[nnz] in CSR order.  Only the dense ranges of the plan are filled (dfgnn_gt_stats_applies == 1:
