@@ -1,6 +1,7 @@
 from .gtconv_layer import SparseMHA  # noqa: F401
 from .gtconv_layer_bias import SparseMHA_bias, SparseMHA_bias_timing  # noqa: F401
 from .gtconv_layer_edge import SparseMHA_edge, SparseMHA_edge_timing  # noqa: F401
+from .gtconv_layer_gate import SparseMHA_gate, SparseMHA_gate_timing  # noqa: F401
 from .gtconv_layer_typed import SparseMHA_typed, SparseMHA_typed_timing, preprocess_types  # noqa: F401
 from .gtconv_layer_tbias import SparseMHA_tbias, SparseMHA_tbias_timing  # noqa: F401
 from .gtconv_layer_csr_gm import SparseMHA_CSR_GM  # noqa: F401

@@ -2,6 +2,7 @@ from .AGNN import AGNNConv_forward  # noqa: F401
 from .GATv2 import GATv2Conv_edge, GATv2Conv_forward, GATv2Conv_tiling, GATv2ConvDGL  # noqa: F401
 from .GT.gtconv_layer_bias import SparseMHA_bias  # noqa: F401
 from .GT.gtconv_layer_edge import SparseMHA_edge  # noqa: F401
+from .GT.gtconv_layer_gate import SparseMHA_gate  # noqa: F401
 from .GT.gtconv_layer_typed import SparseMHA_typed, preprocess_types  # noqa: F401
 from .GT.gtconv_layer_tbias import SparseMHA_tbias  # noqa: F401
 from .GT.gtconv_layer_forward import SparseMHA_forward  # noqa: F401

@@ -22,8 +22,8 @@ from .GAT import (GATConv_dgNN, GATConv_hyper, GATConv_hyper_ablation, GATConv_h
                   GATConv_softmax, GATConv_softmax_gm, GATConv_tiling)
 from .GATv2 import GATv2Conv_edge_timing, GATv2Conv_forward, GATv2Conv_tiling
 from .GT import (SparseMHA_bias_timing, SparseMHA_CSR, SparseMHA_CSR_GM, SparseMHA_edge_timing, SparseMHA_forward_timing,
-                 SparseMHA_hyper, SparseMHA_rowstats_timing, SparseMHA_softmax, SparseMHA_softmax_gm, SparseMHA_tbias_timing,
-                 SparseMHA_tiling, SparseMHA_typed_timing)
+                 SparseMHA_gate_timing, SparseMHA_hyper, SparseMHA_rowstats_timing, SparseMHA_softmax, SparseMHA_softmax_gm,
+                 SparseMHA_tbias_timing, SparseMHA_tiling, SparseMHA_typed_timing)
 
 WARP_SIZE = 32  # only used by the smem_consume formula kept from the reference
 
@@ -130,6 +130,7 @@ _GT_LAYERS = {
     "forward_rowstats": SparseMHA_rowstats_timing,  # this build's addition: row statistics instead of attn_edge, any graph
     "forward_bias": SparseMHA_bias_timing,  # this build's addition: a per-edge additive attention bias (seeded random here)
     "forward_edge": SparseMHA_edge_timing,  # this build's addition: per-edge feature vectors in keys and values (seeded random here)
+    "forward_gate": SparseMHA_gate_timing,  # this build's addition: keys gated by per-edge feature vectors, with the edge output (seeded random here)
     "forward_typed": SparseMHA_typed_timing,  # this build's addition: key / value vectors from a table by edge type (16 seeded random types here)
     "forward_tbias": SparseMHA_tbias_timing,  # this build's addition: an attention bias from a table by edge type and head (16 seeded random types here)
     "hyper_ablation": SparseMHA_hyper,  # reference :385-386 (ablation entry; served by the production kernel)
@@ -207,6 +208,6 @@ def load_prepfunc(args):
         return preprocess_Hyper
     if args.format in ("softmax", "softmax_gm"):
         return preprocess_softmax
-    if args.format in ("forward", "forward_rowstats", "forward_bias", "forward_edge", "forward_typed", "forward_tbias"):
+    if args.format in ("forward", "forward_rowstats", "forward_bias", "forward_edge", "forward_gate", "forward_typed", "forward_tbias"):
         return preprocess_Hyper_fw_bw
     raise ValueError(f"Unsupported format {args.format}")

@@ -176,6 +176,51 @@ def GTConvFuse_inference_edge(row_ptr, col_ind, val, Q, K, V, E):
     return fused_gt.gt_inference_edge(row_ptr, col_ind, val, E, Q, K, V)
 
 
+class FusedGTFunction_gate(torch.autograd.Function):
+    """FusedGTFunction_rowstats with a per-edge multiplicative gate on the keys and an edge output (include/dfgnn.h:
+    dfgnn_gt_fwd_gate / dfgnn_gt_bwd_gate, csrc/gt_gate_train.hip): ke_e = K_j (.) E_e, s_e = val_e <Q_i, ke_e>,
+    W_e = val_e Q_i (.) ke_e, E and W fp32[nnz, h, f] in CSR edge order; no clamp on the logit.  -> (out, W), or out alone
+    with edge_out=False.  W is an OUTPUT the model trains through: its gradient G enters the backward next to grad_out
+    (None when W was not used: then nothing of G is read).  W is not saved -- the backward recomputes every edge from the
+    rows it gathers.  Saved between forward and backward: Q, K, V, E, out, the row statistics and the graph arrays (`val`
+    only when it is not all ones).  dE[nnz, h, f] is computed only when E requires a gradient."""
+
+    @staticmethod
+    def forward(ctx, rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V, E, edge_out):
+        out_feat, row_max, row_sum, W = fused_gt.gt_forward_gate(row_ptr, col_ind, val, E, Q, K, V, need_W=edge_out)
+        keep_val = () if fused_gt.val_ptr(val) is None else (val,)
+        ctx.save_for_backward(row_ptr, col_ind, col_ptr, row_ind, val_idx, Q, K, V, E, out_feat, row_max, row_sum,
+                              *keep_val)
+        ctx.edge_out = edge_out
+        ctx.set_materialize_grads(False)       # an unused W arrives as None, not as zeros [nnz, h, f]
+        return (out_feat, W) if edge_out else out_feat
+
+    @staticmethod
+    def backward(ctx, grad_out, grad_W=None):
+        row_ptr, col_ind, col_ptr, row_ind, val_idx, Q, K, V, E, out_feat, row_max, row_sum, *val = ctx.saved_tensors
+        val = val[0] if val else None
+        if grad_out is None:                   # only W was used
+            grad_out = torch.zeros_like(out_feat)
+        grad_Q, grad_K, grad_V, grad_E = fused_gt.gt_backward_gate(
+            row_ptr, col_ind, val, E, col_ptr, row_ind, val_idx, Q, K, V, out_feat, row_max, row_sum,
+            grad_out.contiguous(), G=None if grad_W is None else grad_W.contiguous(), need_dE=ctx.needs_input_grad[11])
+        return (None,) * 8 + (grad_Q, grad_K, grad_V, grad_E, None)
+
+
+def GTConvFuse_gate(rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V, E, edge_out=True):
+    """Differentiable conv of any graph with the keys gated by the edge features fp32[nnz, h, f] (CSR edge order) -> (out, W)
+    with the edge output W[nnz, h, f] = val_e Q_i (.) K_j (.) E_e, or out alone with edge_out=False; the argument list of
+    GTConvFuse_edge plus `edge_out` (`rows` and `smem_consume` are accepted and not used)."""
+    return FusedGTFunction_gate.apply(
+        rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V, E, edge_out)
+
+
+def GTConvFuse_inference_gate(row_ptr, col_ind, val, Q, K, V, E, edge_out=True):
+    """Inference of any graph with the keys gated by the edge features fp32[nnz, h, f] (CSR edge order) -> (out, W), or out
+    alone with edge_out=False."""
+    return fused_gt.gt_inference_gate(row_ptr, col_ind, val, E, Q, K, V, need_W=edge_out)
+
+
 class FusedGTFunction_typed(torch.autograd.Function):
     """FusedGTFunction_edge with E_e = R[etype[e]] looked up in the kernels (include/dfgnn.h: dfgnn_gt_fwd_typed /
     dfgnn_gt_bwd_typed, csrc/gt_typed_train.hip): R fp32[T, h, f], etype int32[nnz] in CSR edge order, etype_csc the same types

@@ -377,6 +377,49 @@ int dfgnn_gt_bwd_edge(int m, int nnz, int h, int f, const int *row_ptr, const in
                                 row_sum, grad_out, delta, dQ, dK, dV, dE, stream);
 }
 
+// ---- the general statistics pair with a per-edge multiplicative gate and an edge-output channel (gt_gate_train.hip) -------
+int dfgnn_gt_fwd_gate_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                           const float *E, const float *Q, const float *K, const float *V, float *row_max, float *row_sum,
+                           float *out, float *W, dfgnn_stream_t stream) {
+  if (int c = check_rect(m, n_cols, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (m == 0) return 0;  // (no row: nothing to write)
+  if (!Q || !out || (n_cols > 0 && (!K || !V)) || (!row_max != !row_sum)) return kErrBadArg;  // (both statistics or neither: inference)
+  if (nnz > 0 && !E) return kErrBadArg;
+  const Csr g = rect_csr(m, n_cols, nnz, h, f, row_ptr, col_ind, val);
+  return launch_gt_gate_fwd(g, E, Q, K, V, row_max, row_sum, out, W, as_stream(stream));
+}
+
+int dfgnn_gt_fwd_gate(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                      const float *E, const float *Q, const float *K, const float *V, float *row_max, float *row_sum,
+                      float *out, float *W, dfgnn_stream_t stream) {
+  return dfgnn_gt_fwd_gate_rect(m, m, nnz, h, f, row_ptr, col_ind, val, E, Q, K, V, row_max, row_sum, out, W, stream);
+}
+
+int dfgnn_gt_bwd_gate_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                           const float *E, const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q,
+                           const float *K, const float *V, const float *out, const float *row_max, const float *row_sum,
+                           const float *grad_out, const float *G, float *delta, float *dQ, float *dK, float *dV, float *dE,
+                           dfgnn_stream_t stream) {
+  if (int c = check_rect(m, n_cols, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (m > 0 && (!Q || !out || !row_max || !row_sum || !grad_out || !delta || !dQ)) return kErrBadArg;
+  if (n_cols > 0 && (!K || !V || !dK || !dV || !col_ptr)) return kErrBadArg;
+  if (nnz > 0 && (!E || !row_ind || !val_idx)) return kErrBadArg;  // (the CSC pass finds an entry's E and G rows through val_idx)
+  const Csr g = rect_csr(m, n_cols, nnz, h, f, row_ptr, col_ind, val);
+  if (int rc = launch_gt_gate_bwd_rows(g, E, Q, K, V, out, row_max, row_sum, grad_out, G, delta, dQ, dE, as_stream(stream)))
+    return rc;
+  return launch_gt_gate_bwd_cols(g, E, col_ptr, row_ind, val_idx, Q, K, V, row_max, row_sum, delta, grad_out, G, dK, dV,
+                                 as_stream(stream));
+}
+
+int dfgnn_gt_bwd_gate(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                      const float *E, const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q,
+                      const float *K, const float *V, const float *out, const float *row_max, const float *row_sum,
+                      const float *grad_out, const float *G, float *delta, float *dQ, float *dK, float *dV, float *dE,
+                      dfgnn_stream_t stream) {
+  return dfgnn_gt_bwd_gate_rect(m, m, nnz, h, f, row_ptr, col_ind, val, E, col_ptr, row_ind, val_idx, Q, K, V, out, row_max,
+                                row_sum, grad_out, G, delta, dQ, dK, dV, dE, stream);
+}
+
 // ---- the general statistics pair with typed edges: key / value vectors looked up from a table (gt_typed_train.hip) --------
 int dfgnn_gt_typed_bwd_ws_floats(int T, int h, int f) {
   if (T < 1 || h < 0 || f < 0) return kErrBadArg;

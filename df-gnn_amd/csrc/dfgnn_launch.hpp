@@ -231,6 +231,19 @@ int launch_gt_edge_bwd_rows(const Csr &g, const float *E, const float *Q, const 
 int launch_gt_edge_bwd_cols(const Csr &g, const float *E, const int *col_ptr, const int *row_ind, const int *val_idx,
                             const float *Q, const float *K, const float *V, const float *row_max, const float *row_sum,
                             const float *delta, const float *grad_out, float *dK, float *dV, hipStream_t s);
+// GT pair with a per-edge multiplicative gate on the keys and an edge-output channel (gt_gate_train.hip): launch_gt_train_*
+// with E [nnz, h, f] (CSR order), ke_e = K_j (.) E_e, s_e = val_e <Q_i, ke_e>.  The forward also writes W [nnz, h, f] =
+// val_e Q_i (.) ke_e when it is not null; both backward passes add G [nnz, h, f] = d loss / d W to dS per dimension when it
+// is not null (the CSC pass through val_idx, which it always reads); the CSR pass writes dE in full when it is not null.
+int launch_gt_gate_fwd(const Csr &g, const float *E, const float *Q, const float *K, const float *V, float *row_max,
+                       float *row_sum, float *out, float *W, hipStream_t s);
+int launch_gt_gate_bwd_rows(const Csr &g, const float *E, const float *Q, const float *K, const float *V,
+                            const float *out, const float *row_max, const float *row_sum, const float *grad_out,
+                            const float *G, float *delta, float *dQ, float *dE, hipStream_t s);
+int launch_gt_gate_bwd_cols(const Csr &g, const float *E, const int *col_ptr, const int *row_ind, const int *val_idx,
+                            const float *Q, const float *K, const float *V, const float *row_max, const float *row_sum,
+                            const float *delta, const float *grad_out, const float *G, float *dK, float *dV,
+                            hipStream_t s);
 // GT pair with typed edges (gt_typed_train.hip): launch_gt_edge_* with E_e = R[etype[e]], R [T, h, f], and never anything of
 // size nnz h f.  The CSC pass streams etype_csc (the types in CSC entry order) and reads val_idx only for edge values.  The
 // CSR pass with dR != NULL runs at most kGtTypedParts persistent workgroups per head, each storing one partial [T, h-slice,

@@ -397,6 +397,67 @@ std::vector<Tensor> gt_bwd_edge(const Tensor &row_ptr, const Tensor &col_ind, co
   return {dQ, dK, dV, dE};
 }
 
+// ---- the general pair with a per-edge multiplicative gate and an edge-output channel (include/dfgnn.h: dfgnn_gt_fwd_gate / dfgnn_gt_bwd_gate) ----
+// E, W, G, dE: fp32 [nnz, h, f] in CSR edge order
+void gate_grad_checks(const Dims &d, const Tensor &ref, const Tensor &G) {
+  check_f32(G, "G");
+  TORCH_CHECK(G.dim() == 3 && G.size(0) == d.nnz && G.size(1) == d.h && G.size(2) == d.f, "G must have shape (", d.nnz, ", ",
+              d.h, ", ", d.f, "), got ", G.sizes());
+  check_same_device(ref, {&G});
+}
+
+// save_stats = false: inference (-> {out}); need_W adds W at the end of either
+std::vector<Tensor> gt_fwd_gate(const Tensor &row_ptr, const Tensor &col_ind, const c10::optional<Tensor> &val, const Tensor &E,
+                                const Tensor &Q, const Tensor &K, const Tensor &V, bool unit_val, bool save_stats, bool need_W) {
+  const Dims d = gt_rect_checks(row_ptr, col_ind, opt(val), Q, K, V);
+  edge_feat_checks(d, Q, E);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
+  Tensor out = torch::empty_like(Q);
+  Tensor row_max, row_sum, W;
+  if (save_stats) {
+    row_max = torch::empty({d.m, d.h}, Q.options());
+    row_sum = torch::empty({d.m, d.h}, Q.options());
+  }
+  if (need_W) W = torch::empty_like(E);
+  check_rc(dfgnn_gt_fwd_gate_rect(d.m, d.n_cols, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), edge_val_ptr(val, unit_val), f32(E), f32(Q),
+                             f32(K), f32(V), f32(row_max), f32(row_sum), f32(out), f32(W), cur_stream()),
+           save_stats ? "gt_forward_gate" : "gt_inference_gate");
+  std::vector<Tensor> res = {out};
+  if (save_stats) {
+    res.push_back(row_max);
+    res.push_back(row_sum);
+  }
+  if (need_W) res.push_back(W);
+  return res;
+}
+
+// G: the gradient of W, or nothing (zero).  -> {dQ, dK, dV, dE}, or {dQ, dK, dV} without need_dE
+std::vector<Tensor> gt_bwd_gate(const Tensor &row_ptr, const Tensor &col_ind, const c10::optional<Tensor> &val, const Tensor &E,
+                                const Tensor &col_ptr, const Tensor &row_ind, const Tensor &val_idx, const Tensor &Q,
+                                const Tensor &K, const Tensor &V, const Tensor &out, const Tensor &row_max,
+                                const Tensor &row_sum, const Tensor &grad, const c10::optional<Tensor> &G, bool unit_val,
+                                bool need_dE) {
+  const Dims d = gt_rect_checks(row_ptr, col_ind, opt(val), Q, K, V);
+  edge_feat_checks(d, Q, E);
+  if (G) gate_grad_checks(d, Q, *G);
+  csc_rect_checks(d, Q, col_ptr, row_ind, &val_idx, "K / V");
+  check_feat3(out, Q, "out");
+  check_feat3(grad, Q, "grad");
+  row_stats_checks(d, Q, row_max, row_sum);
+  check_same_device(Q, {&out, &grad});
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(Q.device());
+  Tensor delta = torch::empty({d.m, d.h}, Q.options());
+  Tensor dQ = torch::empty_like(Q), dK = torch::empty_like(K), dV = torch::empty_like(V);
+  Tensor dE;
+  if (need_dE) dE = torch::empty_like(E);
+  check_rc(dfgnn_gt_bwd_gate_rect(d.m, d.n_cols, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), edge_val_ptr(val, unit_val), f32(E),
+                             i32(col_ptr), i32(row_ind), i32(val_idx), f32(Q), f32(K), f32(V), f32(out), f32(row_max),
+                             f32(row_sum), f32(grad), f32(G), f32(delta), f32(dQ), f32(dK), f32(dV), f32(dE), cur_stream()),
+           "gt_backward_gate");
+  if (!need_dE) return {dQ, dK, dV};
+  return {dQ, dK, dV, dE};
+}
+
 // ---- the general pair with typed edges (include/dfgnn.h: dfgnn_gt_fwd_typed / dfgnn_gt_bwd_typed) -----------------------
 // etype: int32 [nnz] in CSR edge order; R: fp32 [T, h, f] -> T
 int typed_checks(const Dims &d, const Tensor &ref, const Tensor &etype, const Tensor &R) {
@@ -922,6 +983,8 @@ PYBIND11_MODULE(_dfgnn_ext, m) {
   m.def("gt_bwd_bias", &gt_bwd_bias, "fused GT conv backward of any graph with a per-edge additive attention bias");
   m.def("gt_fwd_edge", &gt_fwd_edge, "fused GT conv forward of any graph with a per-edge feature vector in keys and values");
   m.def("gt_bwd_edge", &gt_bwd_edge, "fused GT conv backward of any graph with a per-edge feature vector in keys and values");
+  m.def("gt_fwd_gate", &gt_fwd_gate, "fused GT conv forward of any graph with a per-edge multiplicative gate and an edge output");
+  m.def("gt_bwd_gate", &gt_bwd_gate, "fused GT conv backward of any graph with a per-edge multiplicative gate and an edge output");
   m.def("gt_fwd_typed", &gt_fwd_typed, "fused GT conv forward of any graph with typed edges: key / value vectors from a table");
   m.def("gt_bwd_typed", &gt_bwd_typed, "fused GT conv backward of any graph with typed edges: key / value vectors from a table");
   m.def("gt_fwd_tbias", &gt_fwd_tbias, "fused GT conv forward of any graph with a typed attention bias: scalars from a table");

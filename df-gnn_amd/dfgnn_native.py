@@ -36,6 +36,8 @@ SIGNATURES = {
     "dfgnn_gt_bwd_bias": [_i, _i, _i, _i] + [_vp] * 20,
     "dfgnn_gt_fwd_edge": [_i, _i, _i, _i] + [_vp] * 11,
     "dfgnn_gt_bwd_edge": [_i, _i, _i, _i] + [_vp] * 20,
+    "dfgnn_gt_fwd_gate": [_i, _i, _i, _i] + [_vp] * 12,
+    "dfgnn_gt_bwd_gate": [_i, _i, _i, _i] + [_vp] * 21,
     "dfgnn_gatv2_bwd_ws_floats": [_i, _i],
     "dfgnn_gatv2_fwd": [_i, _i, _i, _i] + [_vp] * 3 + [_f] + [_vp] * 6,
     "dfgnn_gatv2_bwd": [_i, _i, _i, _i] + [_vp] * 5 + [_f] + [_vp] * 12,
@@ -46,6 +48,8 @@ SIGNATURES = {
     "dfgnn_gt_bwd_bias_rect": [_i] * 5 + [_vp] * 20,
     "dfgnn_gt_fwd_edge_rect": [_i] * 5 + [_vp] * 11,
     "dfgnn_gt_bwd_edge_rect": [_i] * 5 + [_vp] * 20,
+    "dfgnn_gt_fwd_gate_rect": [_i] * 5 + [_vp] * 12,
+    "dfgnn_gt_bwd_gate_rect": [_i] * 5 + [_vp] * 21,
     "dfgnn_gt_typed_bwd_ws_floats": [_i, _i, _i],
     "dfgnn_gt_fwd_typed": [_i] * 5 + [_vp] * 12,
     "dfgnn_gt_bwd_typed": [_i] * 5 + [_vp] * 23,

@@ -431,6 +431,65 @@ def gt_backward_edge(row_ptr, col_ind, val, E, col_ptr, row_ind, val_idx, Q, K, 
     return [dQ, dK, dV, dE]
 
 
+# ---- the general pair with a per-edge multiplicative gate and an edge output (include/dfgnn.h: dfgnn_gt_fwd_gate / _bwd_gate)
+# Not part of the reference's module.  The row-statistics pair with ke_e = K_j (.) E_e, s_e = val_e <Q_i, ke_e> and the
+# edge output W_e = val_e Q_i (.) ke_e (csrc/gt_gate_train.hip): E, W, the gradient G of W and dE are fp32[nnz, h, f] in CSR
+# edge order.  No clamp on the logit.  DFGNN.operators.fused_gtconv.GTConvFuse_gate takes it.
+
+
+def _forward_gate(what, save_stats, need_W, row_ptr, col_ind, val, E, Q, K, V):
+    ext = _n.ext()
+    if ext is not None:
+        return ext.gt_fwd_gate(row_ptr, col_ind, val, E, Q, K, V, val_ptr(val) is None, save_stats, need_W)
+    m, n_cols, nnz, h, f = _checks_rect(row_ptr, col_ind, Q, K, V, val=val)
+    _check_edge_feat(Q, nnz, h, f, E)
+    out = torch.empty_like(Q)
+    row_max, row_sum = (_empty(Q, m, h), _empty(Q, m, h)) if save_stats else (None, None)
+    W = torch.empty_like(E) if need_W else None
+    call("dfgnn_gt_fwd_gate_rect", what, Q.device, m, n_cols, nnz, h, f, row_ptr, col_ind, val_ptr(val), E, Q, K, V, row_max, row_sum,
+         out, W)
+    return [out] + ([row_max, row_sum] if save_stats else []) + ([W] if need_W else [])
+
+
+def gt_inference_gate(row_ptr, col_ind, val, E, Q, K, V, need_W=False):
+    """-> out, or (out, W) with need_W: inference of any graph with the keys gated by the edge features fp32[nnz, h, f]
+    (CSR order).  val: edge values fp32[nnz] in CSR order; None or all ones: unit values."""
+    res = _forward_gate("gt_inference_gate", False, need_W, row_ptr, col_ind, val, E, Q, K, V)
+    return tuple(res) if need_W else res[0]
+
+
+def gt_forward_gate(row_ptr, col_ind, val, E, Q, K, V, need_W=True):
+    """-> [out, row_max[m, h], row_sum[m, h], W[nnz, h, f]]: the training forward; W is None without need_W (then nothing
+    of size nnz h f is allocated or written).  An empty row has out = 0, row_max = -1e38, row_sum = 0."""
+    res = _forward_gate("gt_forward_gate", True, need_W, row_ptr, col_ind, val, E, Q, K, V)
+    return res if need_W else res + [None]
+
+
+def gt_backward_gate(row_ptr, col_ind, val, E, col_ptr, row_ind, val_idx, Q, K, V, out, row_max, row_sum, grad, G=None,
+                     need_dE=True):
+    """-> [dQ, dK, dV, dE[nnz, h, f]] from the forward's output and row statistics, the gradient `grad` of out and the
+    gradient G[nnz, h, f] of W (None: zero, nothing of it is read); dE is None without need_dE (then nothing of size
+    nnz h f is allocated or written)."""
+    val_idx = as_int32(val_idx)
+    ext = _n.ext()
+    if ext is not None:
+        res = ext.gt_bwd_gate(row_ptr, col_ind, val, E, col_ptr, row_ind, val_idx, Q, K, V, out, row_max, row_sum, grad, G,
+                              val_ptr(val) is None, need_dE)
+        return res if need_dE else res + [None]
+    m, n_cols, nnz, h, f = _checks_rect(row_ptr, col_ind, Q, K, V, val=val, out=out, grad=grad)
+    _check_edge_feat(Q, nnz, h, f, E)
+    if G is not None:
+        check_3d(Q, nnz, h, f, G=G)
+    check_csc_rect(Q, n_cols, nnz, col_ptr, "K / V", row_ind=row_ind, val_idx=val_idx)
+    check_2d(Q, m, h, row_max=row_max, row_sum=row_sum)
+    delta = _empty(Q, m, h)
+    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
+    dE = torch.empty_like(E) if need_dE else None
+    call("dfgnn_gt_bwd_gate_rect", "gt_backward_gate", Q.device, m, n_cols, nnz, h, f, row_ptr, col_ind, val_ptr(val), E, col_ptr,
+         row_ind, val_idx, Q, K, V, out, row_max, row_sum, grad, G, delta, dQ, dK, dV, dE)
+    return [dQ, dK, dV, dE]
+
+
 # ---- the general pair with typed edges (include/dfgnn.h: dfgnn_gt_fwd_typed / dfgnn_gt_bwd_typed) ------------------------
 # Not part of the reference's module.  The edge pair with E_e = R[etype[e]] (csrc/gt_typed_train.hip): R is fp32[T, h, f],
 # etype int32[nnz] in CSR edge order, etype_csc the same types in CSC entry order (etype[val_idx];

@@ -291,6 +291,52 @@ int dfgnn_gt_bwd_edge_rect(int m, int n_cols, int nnz, int h, int f, const int *
                            const float *grad_out, float *delta, float *dQ, float *dK, float *dV, float *dE,
                            dfgnn_stream_t stream);
 
+/* The general statistics pair with a per-edge MULTIPLICATIVE GATE on the keys and an EDGE-OUTPUT channel
+ * (csrc/gt_gate_train.hip): any graph, no plan, any f.  Edge e = (i, j) carries E_e in R^f per head, which scales the key
+ * dimension by dimension; the per-dimension products are returned as the next layer's edge features (the Graph Transformer
+ * layer with edge features of Dwivedi & Bresson, SAN, the GT variants of GraphGPS-type stacks):
+ *   ke_e = K_j (.) E_e                       (formed first, in every pass alike)
+ *   s_e = val_e <Q_i, ke_e>,  W_e[d] = val_e Q_i[d] ke_e[d],  P_e = exp(s_e - row_max_i) / row_sum_i,  out_i = sum_e P_e V_j
+ *   delta_i = <grad_out_i, out_i>,  dS_e = P_e (<grad_out_i, V_j> - delta_i),  g_e[d] = dS_e + G_e[d]
+ *   dQ_i[d] = sum val_e g_e[d] ke_e[d],  dK_j[d] = sum val_e g_e[d] Q_i[d] E_e[d],  dV_j = sum P_e grad_out_i
+ *   dE_e[d] = val_e g_e[d] Q_i[d] K_j[d]
+ * The caller applies the 1/sqrt(f) scale to Q; there is NO clamp on the logit.
+ *   E        fp32[nnz, h, f] in CSR edge order (the layout of dfgnn_gt_fwd_edge's E: the row of (edge e, head) starts at
+ *            (e h + head) f); required when nnz > 0.  Duplicate edges each have their own row
+ *   W        fp32[nnz, h, f], every slot written by plain stores, or NULL: the forward writes nothing of size nnz h f
+ *   G        fp32[nnz, h, f], the gradient of the loss with respect to W -- a second gradient stream next to grad_out, read
+ *            by both backward passes (the CSC pass through val_idx) -- or NULL = zero: nothing of it is read, and the
+ *            results equal those of G = zeros
+ *   dE       fp32[nnz, h, f], every slot written by plain stores (no pre-zeroing), or NULL: E needs no gradient and nothing
+ *            of size nnz h f is written
+ *   val      fp32[nnz], CSR order, NULL = unit values
+ *   val_idx  required when nnz > 0 (also for unit values): the CSC pass finds an entry's E and G rows through it
+ *   row_max = row_sum = NULL in the forward: nothing is saved (inference)
+ * ke = K (.) E is formed before the dot product, which is the routine of dfgnn_gt_fwd_rowstats: with E all ones, W = NULL and
+ * G = NULL, out, row_max, row_sum, dQ, dK and dV are those of dfgnn_gt_fwd_rowstats / dfgnn_gt_bwd_rowstats bit for bit.
+ * The float4 paths need f % 4 == 0 and 16-byte aligned feature arrays, E, W, G and dE included; otherwise the scalar layouts
+ * run (f <= 256).  An empty row has out = 0, row_max = -1e38, row_sum = 0, dQ = 0; an empty column dK = dV = 0.  Everything
+ * else as dfgnn_gt_fwd_edge / dfgnn_gt_bwd_edge: delta is caller scratch fp32[m, h]; every output is written in full; no
+ * atomics, the sums are deterministic; the same two forms by average degree; the same size limits and DFGNN_E_* codes;
+ * nothing allocates or synchronises (capturable in a HIP graph). */
+int dfgnn_gt_fwd_gate(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                      const float *E, const float *Q, const float *K, const float *V, float *row_max, float *row_sum,
+                      float *out, float *W, dfgnn_stream_t stream);
+int dfgnn_gt_bwd_gate(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                      const float *E, const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q,
+                      const float *K, const float *V, const float *out, const float *row_max, const float *row_sum,
+                      const float *grad_out, const float *G, float *delta, float *dQ, float *dK, float *dV, float *dE,
+                      dfgnn_stream_t stream);
+/* ... for an m x n_cols graph (extents: see dfgnn_gt_fwd_rowstats_rect) */
+int dfgnn_gt_fwd_gate_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                           const float *E, const float *Q, const float *K, const float *V, float *row_max, float *row_sum,
+                           float *out, float *W, dfgnn_stream_t stream);
+int dfgnn_gt_bwd_gate_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
+                           const float *E, const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q,
+                           const float *K, const float *V, const float *out, const float *row_max, const float *row_sum,
+                           const float *grad_out, const float *G, float *delta, float *dQ, float *dK, float *dV, float *dE,
+                           dfgnn_stream_t stream);
+
 /* The general statistics pair with TYPED edges (csrc/gt_typed_train.hip): any graph, no plan, any f.  The vector an edge
  * adds to key and value is a row of a small table R[T, h, f], chosen by the edge's type (Shaw-style relative positions,
  * RGAT / HGT-style relation vectors, bucketed distances, bond types).  With t = etype[e]:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel register / LDS / scratch use of a built libdfgnn.so (from the code object's metadata notes).
 usage: python tools/kernel_resources.py [pattern] [lib] [--check]
-pattern: a regular expression over the mangled kernel names, e.g. dense, gt_typed, gt_bias_(wave|group), gt_tbias, gatv2_edge.
+pattern: a regular expression over the mangled kernel names, e.g. dense, gt_typed, gt_bias_(wave|group), gt_tbias, gatv2_edge, gt_gate.
 --check: print a summary line and exit with status 1 if a matched kernel spills or uses scratch (or none matched) -- how
 the no-scratch rule of the any-graph pairs (gt_typed, gt_tbias, gatv2_edge) is checked without a GPU."""
 import re, subprocess, sys
