@@ -198,7 +198,8 @@ struct DenseStageRegs {
 // fr < F (a narrower matrix run on the F-wide kernels, e.g. f = 16 heads on the 32-wide instance): the pieces past fr are
 // read from the row's first piece instead (a valid address) and zeroed with the padding rows.
 // once (a literal at every call site, so that it folds): the matrix is read once and not again -- non-temporal loads.
-template <int F, int ROWS>
+// USED < ROWS: an image of USED rows travelling in the registers of a ROWS-row one (the later pieces are left alone).
+template <int F, int ROWS, int USED = ROWS>
 __device__ __forceinline__ void dense_stage_load(DenseStageRegs<F, ROWS> &r, const float *__restrict__ src, size_t hf,
                                                  int row0, int row_end, int fr = F, bool once = false) {
   constexpr int C8 = F / 8;
@@ -206,9 +207,9 @@ __device__ __forceinline__ void dense_stage_load(DenseStageRegs<F, ROWS> &r, con
   r.row0 = row0;
   r.row_end = row_end;
 #pragma unroll
-  for (int k = 0; k < DenseStageRegs<F, ROWS>::PER; ++k) {
+  for (int k = 0; k < DenseStageRegs<F, USED>::PER; ++k) {
     const int idx = tid + k * kDenseThreads;
-    const int row = min(idx / C8, ROWS - 1), c8 = idx % C8;
+    const int row = min(idx / C8, USED - 1), c8 = idx % C8;
     const unsigned off = (unsigned)min(row0 + row, row_end - 1) * (unsigned)hf + ((fr >= F || 8 * c8 < fr) ? 8u * c8 : 0u);
     r.a[k] = once ? ld32_f4_once(src, off) : ld32_f4(src, off);
     r.b[k] = once ? ld32_f4_once(src, off + 4) : ld32_f4(src, off + 4);
@@ -217,11 +218,11 @@ __device__ __forceinline__ void dense_stage_load(DenseStageRegs<F, ROWS> &r, con
 
 // Largest magnitude this thread holds of the image that is about to be stored.  (Clamped loads repeat valid rows and
 // pieces, so nothing needs masking.)
-template <int F, int ROWS>
+template <int F, int ROWS, int USED = ROWS>
 __device__ __forceinline__ float dense_stage_absmax(const DenseStageRegs<F, ROWS> &r) {
   float m = 0.f;
 #pragma unroll
-  for (int k = 0; k < DenseStageRegs<F, ROWS>::PER; ++k) m = fmaxf(m, absmax8(r.a[k], r.b[k]));
+  for (int k = 0; k < DenseStageRegs<F, USED>::PER; ++k) m = fmaxf(m, absmax8(r.a[k], r.b[k]));
   return m;
 }
 
@@ -245,15 +246,15 @@ __device__ __forceinline__ float wg_max_read(const float *slot) {
 // and the wait for the data to the previous barrier, measured 2 % slower.)
 // fr: real feature count (<= F, a multiple of 8): the image columns at or past it are stored as zeros.
 // scale: the image's power-of-two scale (pow2_scale of its largest magnitude).
-template <int F, int ROWS>
+template <int F, int ROWS, int USED = ROWS>
 __device__ __forceinline__ void dense_stage_store(DenseStageRegs<F, ROWS> &r, h16 *hi, h16 *lo, float scale, int fr = F) {
   constexpr int C8 = F / 8, RS = DenseCfg<F>::RS;
   const int tid = opaque_tid();
 #pragma unroll
-  for (int k = 0; k < DenseStageRegs<F, ROWS>::PER; ++k) {
+  for (int k = 0; k < DenseStageRegs<F, USED>::PER; ++k) {
     const int idx = tid + k * kDenseThreads;
     const int row = idx / C8, c8 = idx - row * C8;
-    if (idx < ROWS * C8) {
+    if (idx < USED * C8) {
       const bool valid = r.row0 + row < r.row_end && (fr >= F || 8 * c8 < fr);
       const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
       hx8 h, l;
@@ -405,7 +406,8 @@ __device__ __forceinline__ void dense_cols_mma(f32x4 (&acc)[F / 16], const h16 *
 // GUARD (padded widths only): feat0 = the feature of this lane's first value (4 mq, plus the tile offset of a
 // single-tile call), fr = the real feature count: nothing is stored (or read back) at or past it.  Unguarded, the
 // stores and the read-backs stay free of branches (a load under a branch is waited for right behind it).
-template <int NFT, bool GUARD = false>
+// NT = false: plain stores -- for partial sums that this lane reads back and adds to (a later row block of the same range).
+template <int NFT, bool GUARD = false, bool NT = true>
 __device__ __forceinline__ void dense_store_acc(const f32x4 (&acc)[NFT], float scale, float *__restrict__ base,
                                                 unsigned off, bool accumulate, int feat0 = 0, int fr = 1 << 30) {
 #pragma unroll
@@ -417,7 +419,8 @@ __device__ __forceinline__ void dense_store_acc(const f32x4 (&acc)[NFT], float s
       const float4 old = ld32_f4(base, off + 16 * ft);
       o.x += old.x; o.y += old.y; o.z += old.z; o.w += old.w;
     }
-    st32_f4_out(base, off + 16 * ft, o);
+    if constexpr (NT) st32_f4_out(base, off + 16 * ft, o);
+    else st32_f4(base, off + 16 * ft, o);
   }
 }
 
@@ -428,10 +431,24 @@ __device__ __forceinline__ void dense_store_acc(const f32x4 (&acc)[NFT], float s
 // 2k + 1 of row mi - 8 (one row_ror:8 DPP move per register), so the first instruction writes rows 0..7 of the strip
 // and the second rows 8..15, 128 contiguous bytes per row.  Must be called by all lanes of the wave; `row` = this
 // lane's row of the matrix (strip * 16 + mi), rows >= n are not stored.  NFT even; feature f of tile t = 16 t + 4 mq.
+// NT = false: plain stores; ACC: added onto `prev`, what the SAME call (same lanes, rows and tiles) stored before with NT = false
+// and dense_load_rows has fetched back (ahead of the product, so that the round trip is not waited for behind it).
 constexpr int kDppRowRor8 = 0x128;
 template <int NFT>
+__device__ __forceinline__ void dense_load_rows(float4 (&prev)[NFT], const float *__restrict__ base, unsigned hf, int row, int n,
+                                                const LaneIds &L) {
+  const bool low = L.mi < 8;
+  const int r1 = min(low ? row : row - 8, n - 1), r2 = min(low ? row + 8 : row, n - 1);  // (rows past the range: row n - 1, unused)
+  const unsigned o1 = (unsigned)r1 * hf + (low ? 0u : 16u) + 4u * L.mq, o2 = (unsigned)r2 * hf + (low ? 16u : 0u) + 4u * L.mq;
+#pragma unroll
+  for (int k = 0; k < NFT / 2; ++k) {
+    prev[2 * k] = ld32_f4(base, o1 + 32 * k);
+    prev[2 * k + 1] = ld32_f4(base, o2 + 32 * k);
+  }
+}
+template <int NFT, bool NT = true, bool ACC = false>
 __device__ __forceinline__ void dense_store_rows(const f32x4 (&acc)[NFT], float scale, float *__restrict__ base, unsigned hf,
-                                                 int row, int n, const LaneIds &L) {
+                                                 int row, int n, const LaneIds &L, const float4 *prev = nullptr) {
   static_assert(NFT % 2 == 0, "tiles are stored in pairs");
   const bool low = L.mi < 8;
   const int prow = low ? row + 8 : row - 8;  // the partner lane's row
@@ -445,9 +462,19 @@ __device__ __forceinline__ void dense_store_rows(const f32x4 (&acc)[NFT], float 
     b.y = dpp_perm<kDppRowRor8>(acc[2 * k + 1][1] * scale);
     b.z = dpp_perm<kDppRowRor8>(acc[2 * k + 1][2] * scale);
     b.w = dpp_perm<kDppRowRor8>(acc[2 * k + 1][3] * scale);
-    const float4 v1 = low ? a : b, v2 = low ? b : a;
-    if (r1 < n) st32_f4_out(base, o1 + 32 * k, v1);
-    if (r2 < n) st32_f4_out(base, o2 + 32 * k, v2);
+    float4 v1 = low ? a : b, v2 = low ? b : a;
+    if constexpr (ACC) {
+      const float4 p1 = prev[2 * k], p2 = prev[2 * k + 1];
+      v1.x += p1.x; v1.y += p1.y; v1.z += p1.z; v1.w += p1.w;
+      v2.x += p2.x; v2.y += p2.y; v2.z += p2.z; v2.w += p2.w;
+    }
+    if constexpr (NT) {
+      if (r1 < n) st32_f4_out(base, o1 + 32 * k, v1);
+      if (r2 < n) st32_f4_out(base, o2 + 32 * k, v2);
+    } else {
+      if (r1 < n) st32_f4(base, o1 + 32 * k, v1);
+      if (r2 < n) st32_f4(base, o2 + 32 * k, v2);
+    }
   }
 }
 

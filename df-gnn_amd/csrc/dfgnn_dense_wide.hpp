@@ -1,4 +1,5 @@
-// dfgnn_dense_wide.hpp -- matrix-core GT backward for dense ranges of up to 160 nodes, in ONE row block.
+// dfgnn_dense_wide.hpp -- matrix-core GT backward for dense ranges of up to 160 nodes, in ONE row block (and, at the end
+// of the file, of 161 .. 192 nodes at one head in two: dense_bwd_wide2_body).
 //
 // A third of the ranges of the headline workload (PATTERN: 119 +- 21 nodes per graph) have more than 128 nodes.  The
 // general backward body (gt_dense.hip: dense_bwd_body<160, 1>) takes them as two row blocks of <= 80 rows, because a
@@ -17,6 +18,8 @@
 // P is scattered straight into the tile as fp16 hi | lo halves (scale 2^14) and read back from there (hi + lo equals P
 // to 2^-24); dS replaces it in place.  Numerics, layouts and helpers: dfgnn_dense.hpp.
 #pragma once
+#include <type_traits>
+
 #include "dfgnn_dense.hpp"
 #include "dfgnn_dense_stamp.hpp"
 #ifndef DFGNN_RING160
@@ -466,6 +469,332 @@ __device__ __forceinline__ void dense_bwd_wide_body(float *lds, const Csr &g, in
     }
   }
   DFGNN_WSTAMP(11)
+}
+
+// ---- 161 .. 192 nodes, one head: two row blocks of <= 96 rows against all (<= 192) columns -----------------------------------
+// The same machinery with the tile cut in two by rows: a 96 x (192 + 8)-float P / dS tile (76.8 KB) is resident per row block,
+// the feature matrices are staged 64 columns at a time -- V and K as images of all (<= 192) rows, dO and Q as images of the row
+// block's rows (61.4 KB at most) -- and travel through the same ring of register sets, which runs on across the row blocks:
+//     per row block:  dO.h -> dV.h (+ the strips' dO operands) ; V.h -> dP += ...     for the feature halves h
+//                     dS ; K.h -> dQ.h ; Q.h -> dK.h                                   for the feature halves h
+// A row block holds whole rows, so t_i and dQ are complete inside it.  dK / dV of the second row block are added onto the first
+// one's by the lane that stored them (the output tiles are dealt to the waves the same way in both): fixed summation order,
+// no atomics; the first block's partial sums are therefore plain stores, the final values leave non-temporal.  The six strips
+// of a row block go to waves 0 .. 5 (the row products dP / dS / dQ), the column products (dV, dK: 12 column strips) are dealt
+// out as in dense_bwd_wide_body: the first 8 strips whole, the others in 16 x 16 output tiles.  The edges of a row block are
+// contiguous in both coordinate orders (CSR and rank order list the rows one after the other).
+constexpr int kDenseWide2Rows = 192;
+#ifndef DFGNN_RING192
+#define DFGNN_RING192 2  // prefetch distance (image phases) of the 161..192-node backward
+#endif
+
+template <int FR, int R = DFGNN_RING192>
+__device__ __forceinline__ void dense_bwd_wide2_body(float *lds, const Csr &g, int n0, int n, int e0, int ne,
+                                                     const float *__restrict__ Q, const float *__restrict__ K,
+                                                     const float *__restrict__ V, const float *__restrict__ attn_edge,
+                                                     const float *__restrict__ dO, float *__restrict__ dQ,
+                                                     float *__restrict__ dK, float *__restrict__ dV) {
+  static_assert(FR == 64 || FR == 128, "one head of 64 or 128 features");
+  constexpr int FW = 64, NH = FR / FW;  // image width, feature halves
+  using D = DenseCfg<FW>;
+  constexpr int RS = D::RS, KT = D::KT, FT = D::FT;
+  constexpr int NC = kDenseWide2Rows, RB = NC / 2, U = NC / 16, TS = NC + 8, TB = 2 * TS, PRE = kDensePre;
+  constexpr int NQ = 4 * NH;  // images of a row block: dO.0 V.0 [dO.1 V.1] K.0 Q.0 [K.1 Q.1]
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int ncs = (n + 15) >> 4;  // column strips
+  h16 *ihi = reinterpret_cast<h16 *>(lds), *ilo = ihi + (size_t)NC * RS;
+  float *T = reinterpret_cast<float *>(ilo + (size_t)NC * RS);
+  h16 *Tb = reinterpret_cast<h16 *>(T);
+  float *smax = T + RB * TS;  // [8] image maxima, [8] dS maxima
+  DFGNN_LDS_AT(lds, (unsigned)(reinterpret_cast<char *>(smax + 2 * kDenseWaves) - reinterpret_cast<char *>(lds)));  // the carve-up fits
+  constexpr unsigned hf = FR;
+  const float *Qb = Q + (size_t)n0 * hf, *Kb = K + (size_t)n0 * hf, *Vb = V + (size_t)n0 * hf, *dOb = dO + (size_t)n0 * hf;
+  float *dQb = dQ + (size_t)n0 * hf, *dKb = dK + (size_t)n0 * hf, *dVb = dV + (size_t)n0 * hf;
+  const int e1 = g.row_ptr[n0 + min(n, RB)];  // the second row block's first edge
+
+  // ---- edges: the first PRE per thread of a row block are requested ahead, the others in batches -------------------------
+  unsigned pc[PRE];  // packed (row, column) within the range (plan.hip: coords)
+  float pa[PRE];
+  auto edges_prefetch = [&](int ea, int cnt) {
+    const int tid = opaque_tid();
+    const int ea0 = min(ea, g.nnz - 1);  // (a row block without edges reads the last edge, unused)
+#pragma unroll
+    for (int k = 0; k < PRE; ++k) {
+      const unsigned e = (unsigned)min(tid + k * kDenseThreads, max(cnt, 1) - 1);
+      pc[k] = ld32_once(g.coords + ea0, e);
+      pa[k] = ld32_once(attn_edge + ea0, e);
+    }
+  };
+  // P of the row block's edges [ea, ea + cnt) -> the (cleared) tile, as fp16 hi | lo (scale 2^14); i0 = its first row
+  auto scatter = [&](int i0, int ea, int cnt) {
+    const int tid = opaque_tid();
+    auto put = [&](unsigned c, float p) {
+      const int at = ((int)(c >> 8) - i0) * TB + (int)(c & 0xFF);
+      const h16 hh = (h16)(p * kUnitScale);
+      Tb[at] = hh;
+      Tb[at + TS] = (h16)fmaf(p, kUnitScale, -(float)hh);
+    };
+#pragma unroll
+    for (int k = 0; k < PRE; ++k)
+      if (tid + k * kDenseThreads < cnt) put(pc[k], pa[k]);
+    constexpr int B = 8;
+    for (int base = PRE * kDenseThreads; base < cnt; base += B * kDenseThreads) {
+      unsigned bc[B];
+      float ba[B];
+#pragma unroll
+      for (int k = 0; k < B; ++k) {
+        const unsigned e = (unsigned)min(base + tid + k * kDenseThreads, cnt - 1);
+        bc[k] = ld32_once(g.coords + ea, e);
+        ba[k] = ld32_once(attn_edge + ea, e);
+      }
+#pragma unroll
+      for (int k = 0; k < B; ++k)
+        if (base + tid + k * kDenseThreads < cnt) put(bc[k], ba[k]);
+    }
+  };
+
+  // ---- images: number gq = NQ * row block + q travels in st[gq % R] (gq is a compile-time constant at every call) --------
+  DenseStageRegs<FW, NC> st[R];
+  Pow2Scale isc{1.f, 1.f};
+  auto image_rows = [](int gq) { const int q = gq % NQ; return (q < 2 * NH) == ((q & 1) == 0); };  // dO, Q: the row block's rows
+  auto image_fetch = [&](int gq) {
+    if (gq >= 2 * NQ) return;
+    const int q = gq % NQ, h = (q % (2 * NH)) / 2;
+    const int i0 = (gq / NQ) * RB, i1 = min(n, i0 + RB);
+    if (q < 2 * NH) {
+      if (q & 1) dense_stage_load<FW, NC>(st[gq % R], Vb + h * FW, hf, 0, n);
+      else dense_stage_load<FW, NC, RB>(st[gq % R], dOb + h * FW, hf, i0, i1, FW, true);  // (dO is read once)
+    } else {
+      if (q & 1) dense_stage_load<FW, NC, RB>(st[gq % R], Qb + h * FW, hf, i0, i1);
+      else dense_stage_load<FW, NC>(st[gq % R], Kb + h * FW, hf, 0, n);
+    }
+  };
+  auto image_post = [&](int gq) {
+    wg_max_post(smax, image_rows(gq) ? dense_stage_absmax<FW, NC, RB>(st[gq % R]) : dense_stage_absmax<FW, NC>(st[gq % R]));
+  };
+  auto image_store = [&](int gq) {  // ... and the register set is refilled with the image R phases on
+    isc = pow2_scale(wg_max_read(smax));
+    if (image_rows(gq)) dense_stage_store<FW, NC, RB>(st[gq % R], ihi, ilo, isc.s);
+    else dense_stage_store<FW, NC>(st[gq % R], ihi, ilo, isc.s);
+    image_fetch(gq + R);
+  };
+
+  // The second row block adds its dK / dV onto the first one's.  This wave's part of those (one whole strip, up to two tiles:
+  // what column_phase deals it) is fetched back BEFORE the image store that precedes the product issues the next prefetch:
+  // loads return in order, so fetched behind it they would be waited for together with an image that is not needed yet.
+  float4 pvs[FT], pvt[2];
+  auto prev_fetch = [&](const float *outb) {
+    const LaneIds L = lane_ids();
+    dense_load_rows<FT>(pvs, outb, hf, min(wave, ncs - 1) * 16 + L.mi, n, L);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int unit = min(wave + k * kDenseWaves, max(ncs - kDenseWaves, 1) * FT - 1);
+      const int j = min((kDenseWaves + unit / FT) * 16 + L.mi, n - 1);
+      pvt[k] = ld32_f4(outb, (unsigned)j * hf + 16u * (unit % FT) + 4u * L.mq);
+    }
+  };
+  // out^T[f][c] = sum_i X[i][f] Y[i][c] over the ni rows of the row block (X = the image, Y = the tile) for the output
+  // tile (column strip cs, feature tile ft; k = which of the wave's tiles), a whole strip when ft < 0.  ACC: the second row
+  // block, added onto the first.
+  auto column_unit = [&](float *outb, int cs, int ft, int k, int ni, float oscale, auto accc) {
+    constexpr bool ACC = decltype(accc)::value;
+    const LaneIds L = lane_ids();
+    const int j = cs * 16 + L.mi;
+    if (ft < 0) {
+      f32x4 acc[FT];
+#pragma unroll
+      for (int t = 0; t < FT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ib = 0; ib < RB / 32; ++ib) {
+        if (32 * ib < ni) {
+          const int yoff = (32 * ib + 4 * L.mq + L.tq) * TB + 16 * cs + 4 * L.tp;
+          const hx8 yh = dense_tr_pair(Tb + yoff, 16 * TB);
+          const hx8 yl = dense_tr_pair(Tb + yoff + TS, 16 * TB);
+          dense_kblock_mma<FW, 4>(acc, ihi, ilo, (32 * ib + 4 * L.mq + L.tq) * RS + 4 * L.tp, 16 * RS, yh, yl);
+        }
+      }
+      dense_store_rows<FT, ACC, ACC>(acc, oscale, outb, hf, j, n, L, pvs);
+    } else {
+      f32x4 acc[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+      for (int ib = 0; ib < RB / 32; ++ib) {
+        if (32 * ib < ni) {
+          const int yoff = (32 * ib + 4 * L.mq + L.tq) * TB + 16 * cs + 4 * L.tp;
+          const hx8 yh = dense_tr_pair(Tb + yoff, 16 * TB);
+          const hx8 yl = dense_tr_pair(Tb + yoff + TS, 16 * TB);
+          const int xoff = (32 * ib + 4 * L.mq + L.tq) * RS + 4 * L.tp + 16 * ft;
+          const hx8 xh = dense_tr_pair(ihi + xoff, 16 * RS);
+          const hx8 xl = dense_tr_pair(ilo + xoff, 16 * RS);
+          acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, yh, acc[0], 0, 0, 0);
+          acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xl, yh, acc[0], 0, 0, 0);
+          acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, yl, acc[0], 0, 0, 0);
+        }
+      }
+      if (j < n) {
+        const unsigned off = (unsigned)j * hf + 16u * ft + 4u * L.mq;
+        if constexpr (ACC) {
+          const float4 old = pvt[k];
+          st32_f4_out(outb, off, make_float4(fmaf(acc[0][0], oscale, old.x), fmaf(acc[0][1], oscale, old.y),
+                                             fmaf(acc[0][2], oscale, old.z), fmaf(acc[0][3], oscale, old.w)));
+        } else {
+          dense_store_acc<1, false, false>(acc, oscale, outb, off, false);
+        }
+      }
+    }
+  };
+  auto column_phase = [&](float *outb, int ni, float oscale, auto accc) {
+    if (wave < ncs) column_unit(outb, wave, -1, 0, ni, oscale, accc);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {  // (at most 4 strips past the eighth: 16 tiles for 8 waves)
+      const int unit = wave + k * kDenseWaves;
+      if (unit < (ncs - kDenseWaves) * FT) column_unit(outb, kDenseWaves + unit / FT, unit % FT, k, ni, oscale, accc);
+    }
+  };
+
+  edges_prefetch(e0, e1 - e0);
+#pragma unroll
+  for (int q = 0; q < R; ++q) image_fetch(q);
+
+  auto row_block = [&](auto rbc) {
+    constexpr int rb = decltype(rbc)::value, q0 = rb * NQ;
+    constexpr std::integral_constant<bool, (rb > 0)> onto{};
+    const int i0 = rb * RB, ni = min(n - i0, RB);
+    const bool row_wave = wave * 16 < ni;
+    // ---- tile := 0, then P of the row block's edges ---------------------------------------------------------------------
+    if (rb > 0) lds_barrier();  // the previous row block's dS tile and Q image are free
+    {
+      const int tid = opaque_tid();
+      for (int k = tid; k < RB * TS / 4; k += kDenseThreads) reinterpret_cast<float4 *>(T)[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    lds_barrier();
+    if (rb == 0) scatter(0, e0, e1 - e0);
+    else scatter(i0, e1, e0 + ne - e1);
+    image_post(q0);
+    lds_barrier();
+    if constexpr (rb > 0) prev_fetch(dVb);
+    image_store(q0);  // dO, half 0
+    lds_barrier();
+
+    // ---- dV.h (+)= dO.h^T P ; dP += V.h dO.h^T ---------------------------------------------------------------------------
+    f32x4 dP[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) dP[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+      const float doinv = isc.inv;
+      hx8 gh[KT], gl[KT];  // the strip's dO rows: the register operand of dP (same scale as the image)
+      {
+        const LaneIds L = lane_ids();
+        const int off = (min(wave, RB / 16 - 1) * 16 + L.mi) * RS + 8 * L.mq;
+#pragma unroll
+        for (int t = 0; t < KT; ++t) {
+          gh[t] = *reinterpret_cast<const hx8 *>(ihi + off + 32 * t);
+          gl[t] = *reinterpret_cast<const hx8 *>(ilo + off + 32 * t);
+        }
+      }
+      column_phase(dVb + h * FW, ni, doinv * kUnitScaleInv, onto);
+      image_post(q0 + 2 * h + 1);
+      lds_barrier();  // the dO image is free
+      image_store(q0 + 2 * h + 1);  // V, half h
+      lds_barrier();
+      if (row_wave) {
+        const float c = isc.inv * doinv;
+        const LaneIds L = lane_ids();
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+          if (16 * u < n) dP[u] += dense_rows_mma<FW>(ihi, ilo, u, gh, gl, L) * c;
+      }
+      if (h + 1 < NH) {
+        image_post(q0 + 2 * h + 2);
+        lds_barrier();  // the V image is free
+        if constexpr (rb > 0) prev_fetch(dVb + (h + 1) * FW);
+        image_store(q0 + 2 * h + 2);  // dO, half h + 1
+        lds_barrier();
+      }
+    }
+
+    // ---- t_i = sum_j P dP ; dS = P (dP - t), in place of dP ---------------------------------------------------------------
+    float tmax = 0.f;
+    if (row_wave) {
+      const LaneIds L = lane_ids();
+      const h16 *prow = Tb + (wave * 16 + L.mi) * TB + 4 * L.mq;
+      float t = 0.f;
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const hx4 ph = *reinterpret_cast<const hx4 *>(prow + 16 * u), pl = *reinterpret_cast<const hx4 *>(prow + TS + 16 * u);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) t = fmaf(((float)ph[r] + (float)pl[r]) * kUnitScaleInv, dP[u][r], t);
+      }
+      t = xor16_32_sum(t);
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const hx4 ph = *reinterpret_cast<const hx4 *>(prow + 16 * u), pl = *reinterpret_cast<const hx4 *>(prow + TS + 16 * u);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          dP[u][r] = ((float)ph[r] + (float)pl[r]) * kUnitScaleInv * (dP[u][r] - t);
+          tmax = fmaxf(tmax, fabsf(dP[u][r]));
+        }
+      }
+    }
+    wg_max_post(smax + kDenseWaves, tmax);
+    image_post(q0 + 2 * NH);
+    lds_barrier();  // the V image and every strip's P rows are free
+    const Pow2Scale ts = pow2_scale(wg_max_read(smax + kDenseWaves));
+    if (row_wave) {
+      const LaneIds L = lane_ids();
+      h16 *trow = Tb + (wave * 16 + L.mi) * TB + 4 * L.mq;
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        hx4 h4, l4;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const h16 hh = (h16)(dP[u][r] * ts.s);
+          h4[r] = hh;
+          l4[r] = (h16)fmaf(dP[u][r], ts.s, -(float)hh);
+        }
+        *reinterpret_cast<hx4 *>(trow + 16 * u) = h4;
+        *reinterpret_cast<hx4 *>(trow + TS + 16 * u) = l4;
+      }
+    }
+    image_store(q0 + 2 * NH);  // K, half 0
+    lds_barrier();
+
+    // ---- dQ.h = dS K.h ; dK.h (+)= dS^T Q.h -------------------------------------------------------------------------------
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+      if (row_wave) {
+        const LaneIds L = lane_ids();
+        f32x4 qacc[FT];
+#pragma unroll
+        for (int t = 0; t < FT; ++t) qacc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        const h16 *srow = Tb + (wave * 16 + L.mi) * TB + 8 * L.mq;
+#pragma unroll
+        for (int jb = 0; jb < NC / 32; ++jb) {
+          if (32 * jb < n) {
+            const hx8 sh = *reinterpret_cast<const hx8 *>(srow + 32 * jb);
+            const hx8 sl = *reinterpret_cast<const hx8 *>(srow + TS + 32 * jb);
+            dense_kblock_mma<FW, 4>(qacc, ihi, ilo, (32 * jb + 8 * L.mq + L.tq) * RS + 4 * L.tp, 4 * RS, sh, sl);
+          }
+        }
+        dense_store_rows<FT>(qacc, isc.inv * ts.inv, dQb + h * FW, hf, i0 + wave * 16 + L.mi, i0 + ni, L);
+      }
+      image_post(q0 + 2 * NH + 2 * h + 1);
+      lds_barrier();  // the K image is free
+      if constexpr (rb > 0) prev_fetch(dKb + h * FW);
+      image_store(q0 + 2 * NH + 2 * h + 1);  // Q, half h
+      lds_barrier();
+      if (rb == 0 && h + 1 == NH) edges_prefetch(e1, e0 + ne - e1);  // the second row block's first edges, under the last product
+      column_phase(dKb + h * FW, ni, isc.inv * ts.inv, onto);
+      if (h + 1 < NH) {
+        image_post(q0 + 2 * NH + 2 * h + 2);
+        lds_barrier();  // the Q image is free
+        image_store(q0 + 2 * NH + 2 * h + 2);  // K, half h + 1
+        lds_barrier();
+      }
+    }
+  };
+  row_block(std::integral_constant<int, 0>{});
+  row_block(std::integral_constant<int, 1>{});
 }
 
 }  // namespace dfgnn

@@ -139,7 +139,7 @@ template <int F>
 __global__ __launch_bounds__(kDenseThreads) void gt_dense_bwd_kernel(
     Csr g, const int *__restrict__ fit, const float *__restrict__ Q, const float *__restrict__ K,
     const float *__restrict__ V, const float *__restrict__ attn_edge, const float *__restrict__ dO,
-    float *__restrict__ dQ, float *__restrict__ dK, float *__restrict__ dV, int heads_from, int walk, int keep) {
+    float *__restrict__ dQ, float *__restrict__ dK, float *__restrict__ dV, int heads_from, int walk, int keep, int tail) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   DFGNN_TRACE_IN
   // heads_from < 0: grid (ranges, heads), one workgroup per (range, head).  heads_from >= 0 (multi-head, heads of at
@@ -162,11 +162,13 @@ __global__ __launch_bounds__(kDenseThreads) void gt_dense_bwd_kernel(
       nwalk = min(walk, g.h - head);
     }
   }
-  // keep >= 0 (one head): the first `keep` ranges of the plan (the largest) in place, the others in REVERSE plan order.  The
-  // forward walks the plan front to back, so the backward launched right behind it then starts with the ranges whose Q, K,
-  // V and attention values the forward touched last -- still in the Infinity Cache -- instead of those it touched first,
-  // which the rest of the forward has pushed out (launch_gt_dense_bwd says what that costs and buys).
-  if (keep >= 0 && heads_from < 0 && range >= keep) range = (int)gridDim.x - 1 - (range - keep);
+  // keep >= 0 (one head): the first `keep` ranges of the plan (the largest) and the last `tail` (the smallest) in place, those
+  // between them in REVERSE plan order.  The forward walks the plan front to back, so the backward launched right behind it
+  // then goes on from the front eighth to ranges whose Q, K, V and attention values the forward touched late -- still in the
+  // Infinity Cache -- instead of those it touched first, which the rest of the forward has pushed out; the smallest ranges
+  // are handed out last, largest of them first, so that the launch ends on short jobs (launch_gt_dense_bwd: cost and gain).
+  if (keep >= 0 && heads_from < 0 && range >= keep && range < (int)gridDim.x - tail)
+    range = (int)gridDim.x - tail - 1 - (range - keep);
   const int n0 = fit[2 * range], n1 = fit[2 * range + 1] & kPlanRangeMask;
   const int n = n1 - n0, e0 = g.row_ptr[n0], ne = g.row_ptr[n1] - e0;
   if constexpr (F <= 64) {
@@ -193,8 +195,16 @@ __global__ __launch_bounds__(kDenseThreads) void gt_dense_bwd_kernel(
 #else
     dense_bwd_wide_body<F, kDenseWideRows, DFGNN_RING160>(lds, g, n0, n, e0, ne, head, Q, K, V, attn_edge, dO, dQ, dK, dV);
 #endif
-  else
-    dense_bwd_body<F, kDenseChunkRows, 2>(lds, g, n0, n, e0, ne, head, Q, K, V, attn_edge, dO, dQ, dK, dV);
+  else {
+    bool wide2 = false;  // one head of 64 or 128 features, 161 .. 192 nodes: two row blocks of <= 96 rows, 64-column images
+#ifndef DFGNN_OLD_192_BWD  // (defined in A/B builds only: the 2 x 2-tile body for every range above 160 nodes)
+    if constexpr (F == 64 || F == 128) wide2 = g.h == 1 && n > kDenseWide2Rows / 2 && ((only < 0 && n <= kDenseWide2Rows) || only == 3);
+#endif
+    if constexpr (F == 64 || F == 128) {
+      if (wide2) dense_bwd_wide2_body<F>(lds, g, n0, n, e0, ne, Q, K, V, attn_edge, dO, dQ, dK, dV);
+    }
+    if (!wide2) dense_bwd_body<F, kDenseChunkRows, 2>(lds, g, n0, n, e0, ne, head, Q, K, V, attn_edge, dO, dQ, dK, dV);
+  }
   DFGNN_TRACE_OUT
 #ifdef DFGNN_STAMPS
   if (threadIdx.x == 0 && dfgnn_dense_stamps)
@@ -309,6 +319,14 @@ int bwd_reverse_keep(int num_dense) {
   return rev > 0 ? num_dense / rev : -1;
 }
 
+// The ranges at the end of the plan's list (the smallest) that the one-head backward hands out last and in plan order: a
+// quarter of them -- one round of jobs of the four-round launch the headline batch is (1024 ranges, 256 CUs) -- so that the
+// CUs that free up last take short jobs.  DFGNN_BWD_TAIL=k in the environment (read once): the smallest 1/k, 0 = none.
+static int bwd_order_tail(int num_dense, int keep) {
+  static const int div = [] { const char *e = getenv("DFGNN_BWD_TAIL"); return e ? atoi(e) : 4; }();
+  return (keep >= 0 && div > 0) ? min(num_dense / div, num_dense - keep) : 0;
+}
+
 int launch_gt_dense_bwd(const Csr &g_in, const Plan &p, const float *Q, const float *K, const float *V,
                         const float *attn_edge, const float *grad_out, float *dQ, float *dK, float *dV,
                         hipStream_t s, bool ranked) {
@@ -326,15 +344,19 @@ int launch_gt_dense_bwd(const Csr &g_in, const Plan &p, const float *Q, const fl
   // REVERSE: it begins where the forward ended and ends where the next forward begins.  Headline step 237 -> 226 us
   // (backward 143 -> 135 us, the forward behind it 94 -> 90 us; 1/8 and 1/10 best, 1/4: 237, everything reversed: 277 us
   // -- the long jobs last); timed back to back with itself the backward does not lose either (138 -> 135 us).
+  // Reversed to the end, the last jobs handed out are the largest behind the front eighth (~145 nodes), and they go to the
+  // CUs that free up last: the smallest quarter of the ranges therefore stays where the plan has it, at the end and
+  // descending (bwd_order_tail; DESIGN 3.3i has the measurement).
   // DFGNN_BWD_REVERSE=k in the environment (read once): keep the largest 1/k, 0 = plan order.
   const int keep = (g.h == 1) ? bwd_reverse_keep(p.num_dense) : -1;  // (several heads: measured with the statistics pair, no gain)
+  const int tail = bwd_order_tail(p.num_dense, keep);
   const int chunks = walk ? (g.h + walk - 1) / walk : 0;
   const dim3 grid = walk ? dim3(p.num_dense_wide * g.h + (p.num_dense - p.num_dense_wide) * chunks, 1) : dim3(p.num_dense, g.h);
   return dispatch_dense(g.f, [&](auto fc) {
     constexpr int F = decltype(fc)::value;
     if (int rc = set_max_lds_cached(gt_dense_bwd_kernel<F>)) return rc;
     gt_dense_bwd_kernel<F><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.fit(), Q, K, V, attn_edge, grad_out, dQ, dK, dV,
-                                                                  heads_from, walk, keep);
+                                                                  heads_from, walk, keep, tail);
     return launch_status();
   });
 }

@@ -10,7 +10,7 @@ import fused_gtconv as gt
 from DFGNN.layers import preprocess_Hyper_fw_bw
 from DFGNN.utils import synthetic as S
 dev = "cuda:0"
-sizes = [int(a) for a in sys.argv[1:]] or [107, 128, 140, 160, 175]
+sizes = [int(a) for a in sys.argv[1:]] or [107, 128, 140, 160, 175, 176, 192]
 bs, reps = 1024, 20
 for n in sizes:
     g = S.pattern_like(batch_size=bs, seed=1, mean_nodes=float(n), std_nodes=0.0, lo=n, hi=n, mean_deg=0.43 * (n - 1)).to(dev)
