@@ -38,12 +38,30 @@ assert L.dfgnn_debug_lds_selftest(4096, buf.data_ptr(), None) == 0
 torch.cuda.synchronize()
 out["selftest"] = dict(report(), readback=float(buf[0]))     # one counted store just past 4096 bytes, limit 4096
 launches = 0
-for n in (40, 107, 128, 140, 160, 175, 250):                  # every range class of the plan's dense kernels
-    g = S.pattern_like(batch_size=12, seed=n, mean_nodes=float(n), std_nodes=0.0, lo=n, hi=n, mean_deg=0.43 * (n - 1)).to(dev)
+ALL_WIDTHS = ((1, 128), (1, 64), (1, 32), (2, 64), (4, 32), (8, 16), (2, 128))
+BOUNDARY_WIDTHS = ((1, 128), (1, 64), (8, 16))
+
+
+def boundary_batch(name):
+    """tests/dense_cases.py: one range of every size next to a strip, column-block or size-class boundary."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import dense_cases
+    from DFGNN.utils import Graph, batch
+    return batch([Graph(s, d, n) for s, d, n in dense_cases.graph(name)["members"]])
+
+
+# every range class of the plan's dense kernels, then the boundary sizes ("narrow": no range of more than 128 nodes)
+CASES = [(n, ALL_WIDTHS) for n in (40, 107, 128, 140, 160, 175, 250)] + [(name, BOUNDARY_WIDTHS) for name in ("narrow", "wide")]
+for n, widths in CASES:
+    if isinstance(n, str):
+        g, seed0 = boundary_batch(n).to(dev), len(n)
+    else:
+        g, seed0 = S.pattern_like(batch_size=12, seed=n, mean_nodes=float(n), std_nodes=0.0, lo=n, hi=n,
+                                  mean_deg=0.43 * (n - 1)).to(dev), n
     A, rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem = preprocess_Hyper_fw_bw(g)
     m = g.num_nodes()
-    for h, f in ((1, 128), (1, 64), (1, 32), (2, 64), (4, 32), (8, 16), (2, 128)):
-        Q, K, V = S.gt_features(m, h, f, seed=n + h, device=dev)
+    for h, f in widths:
+        Q, K, V = S.gt_features(m, h, f, seed=seed0 + h, device=dev)
         dO = torch.randn_like(Q)
         args = (row_ptr, col_ind, rows, val, col_ptr, row_ind, val_idx, smem, Q, K, V)
         o, attn = gt.gt_hyper_forward(*args)                                  # attn_edge pair
@@ -59,7 +77,7 @@ for n in (40, 107, 128, 140, 160, 175, 250):                  # every range clas
             gt.gt_backward_ranked(row_ptr, col_ind, Q, K, V, attn_r, dO)
             launches += 2
         if h == 1:                                                            # GAT training pair, with and without dropout
-            ar, ac, X = S.gat_features(m, 1, f, seed=n, device=dev)
+            ar, ac, X = S.gat_features(m, 1, f, seed=seed0, device=dev)
             for drop in (0.0, 0.3):
                 res = gat.gat_forward(ar, ac, row_ptr, col_ind, 0.2, X, drop)
                 gat.gat_backward(0.2, drop, row_ptr, col_ind, col_ptr, row_ind, val_idx, res[1], res[2], res[3], X, ar, ac, dO)
