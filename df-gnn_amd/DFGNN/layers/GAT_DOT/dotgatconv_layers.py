@@ -79,3 +79,38 @@ class DOTGATConv_hyper(_DOTGATInference):      # params = (g, indptr, indices, r
 
 class DOTGATConv_softmax(_DOTGATInference):    # params = (g, indptr, indices, rows, val, smem)
     op = staticmethod(ops.GTConvFuse_inference_softmax)
+
+
+class _Transposed:
+    """A graph with every edge turned round: what DotGatConv (softmax over the edges that ARRIVE at a node, message from
+    the source) has to be given to normalise over a row's out-edges like the fused operators (module docstring)."""
+
+    def __init__(self, rows, cols, n):
+        self._rows, self._cols, self._n = rows, cols, n
+
+    def edges(self):
+        return self._cols.long(), self._rows.long()
+
+    def num_nodes(self):
+        return self._n
+
+
+class DOTGATConv_forward(DOTGATConvDGL):
+    """Training layer -- this build's addition; the reference has none for DOTGAT.  forward(params, feat, fuse) ->
+    out[N, heads * out], differentiable in both branches; params = (g, *preprocess_Hyper_fw_bw's tuple).  The fused branch
+    is AGNNConvFuse with cosine=False (csrc/agnn_train.hip) on (H, H): the 1 / sqrt(out) factor is the operator's `beta`, a
+    buffer, so no scaled copy of H exists and H is gathered once per edge.  The non-fused branch is DotGatConv on the
+    transposed edge list of the adjacency, so both branches normalise over a row's out-edges on any graph."""
+
+    def __init__(self, in_size, out_size, num_heads):
+        super().__init__(in_size, out_size, num_heads)
+        self.register_buffer("beta", torch.full((num_heads,), out_size ** -0.5))
+
+    def forward(self, params, feat, fuse=False):
+        A, _, row_ptr, col_ind, _, col_ptr, row_ind, _, _ = params[1:]
+        if fuse:
+            H = self.conv_nofuse.fc(feat).view(-1, self.num_heads, self.out_size).contiguous()
+            out = ops.AGNNConvFuse(row_ptr, col_ind, col_ptr, row_ind, self.beta, H, H, cosine=False)
+        else:
+            out = self.conv_nofuse(_Transposed(A.row, A.col, len(feat)), feat)
+        return out.reshape(len(feat), -1)

@@ -15,9 +15,9 @@ import torch
 
 from DFGNN.utils import sparse as dglsp
 
-from .AGNN import (AGNNConv_csr, AGNNConv_csr_gm, AGNNConv_hyper, AGNNConv_softmax, AGNNConv_softmax_gm,
+from .AGNN import (AGNNConv_beta, AGNNConv_csr, AGNNConv_csr_gm, AGNNConv_hyper, AGNNConv_softmax, AGNNConv_softmax_gm,
                    AGNNConv_tiling)
-from .GAT_DOT import DOTGATConv_csr, DOTGATConv_hyper, DOTGATConv_softmax
+from .GAT_DOT import DOTGATConv_csr, DOTGATConv_forward, DOTGATConv_hyper, DOTGATConv_softmax
 from .GAT import (GATConv_dgNN, GATConv_hyper, GATConv_hyper_ablation, GATConv_hyper_recompute, GATConv_hyper_v2,
                   GATConv_softmax, GATConv_softmax_gm, GATConv_tiling)
 from .GATv2 import GATv2Conv_edge_timing, GATv2Conv_forward, GATv2Conv_tiling
@@ -143,13 +143,15 @@ _GAT_LAYERS = {
 _AGNN_LAYERS = {  # reference :424-442
     "hyper": AGNNConv_hyper, "csr": AGNNConv_csr, "softmax": AGNNConv_softmax, "csr_gm": AGNNConv_csr_gm,
     "tiling": AGNNConv_tiling, "softmax_gm": AGNNConv_softmax_gm,
+    "forward_beta": AGNNConv_beta,  # this build's addition: learnable beta, multi-head, any graph, on the fused AGNN pair
 }
 # this build's addition (the reference has no GATv2): one fused kernel family serves any graph, so the CSR-taking formats
 # all name the inference layer; "forward" is the training layer on the fused pair, "forward_edge" the one with per-edge feature
 # vectors inside the LeakyReLU (seeded random here)
 _GATV2_LAYERS = {"tiling": GATv2Conv_tiling, "csr": GATv2Conv_tiling, "forward": GATv2Conv_forward,
                  "forward_edge": GATv2Conv_edge_timing}
-_DOTGAT_LAYERS = {"hyper": DOTGATConv_hyper, "csr": DOTGATConv_csr, "softmax": DOTGATConv_softmax}
+# "forward": this build's addition, the training layer on the fused AGNN pair in dot mode
+_DOTGAT_LAYERS = {"hyper": DOTGATConv_hyper, "csr": DOTGATConv_csr, "softmax": DOTGATConv_softmax, "forward": DOTGATConv_forward}
 # formats of the reference that are baselines on NVIDIA-only libraries or paper experiments
 _OUT_OF_SCOPE = {"hybrid", "pyg", "cugraph", "subgraph"}
 
@@ -200,7 +202,8 @@ def load_graphconv_layer(args):
 
 def load_prepfunc(args):
     if getattr(args, "conv", None) == "dotgat":
-        inner = {"csr": preprocess_CSR, "hyper": preprocess_Hyper, "softmax": preprocess_softmax}[args.format]
+        inner = {"csr": preprocess_CSR, "hyper": preprocess_Hyper, "softmax": preprocess_softmax,
+                 "forward": preprocess_Hyper_fw_bw}[args.format]
         return lambda g, **kw: (g,) + tuple(inner(g, **kw))
     if args.format in ("csr", "csr_gm", "tiling"):
         return preprocess_CSR
@@ -208,6 +211,7 @@ def load_prepfunc(args):
         return preprocess_Hyper
     if args.format in ("softmax", "softmax_gm"):
         return preprocess_softmax
-    if args.format in ("forward", "forward_rowstats", "forward_bias", "forward_edge", "forward_gate", "forward_typed", "forward_tbias"):
+    if args.format in ("forward", "forward_rowstats", "forward_bias", "forward_edge", "forward_gate", "forward_typed", "forward_tbias",
+                       "forward_beta"):
         return preprocess_Hyper_fw_bw
     raise ValueError(f"Unsupported format {args.format}")

@@ -102,6 +102,41 @@ def GTConvFuse_rowstats(rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, 
         rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V)
 
 
+# ---- AGNN / dot-product attention with tied keys and values (this build's addition; fused_gtconv.agnn_*) -----------------
+def AGNNConvFuse_inference(row_ptr, col_ind, beta, X_row, X_col, cosine=True):
+    """-> out[m, h, f] = softmax_j(beta[h] cos(X_row_i, X_col_j)) X_col_j (cosine=False: beta[h] <X_row_i, X_col_j>); beta
+    fp32 [heads], X_row / X_col fp32 [nodes, heads, feat] (may be the same tensor)."""
+    return fused_gt.agnn_inference(row_ptr, col_ind, beta, X_row, X_col, cosine)
+
+
+class FusedAGNNFunction(torch.autograd.Function):
+    """Training pair (include/dfgnn.h: dfgnn_agnn_fwd / dfgnn_agnn_bwd, csrc/agnn_train.hip).  Saved between forward and
+    backward: beta, X_row, X_col, out, two floats per (row, head) and the graph arrays -- no normalised copy of the features,
+    nothing of size nnz in floating point.  The rows' shares of dbeta are requested only when beta needs a gradient."""
+
+    @staticmethod
+    def forward(ctx, row_ptr, col_ind, col_ptr, row_ind, beta, X_row, X_col, cosine):
+        out, row_max, row_sum = fused_gt.agnn_forward(row_ptr, col_ind, beta, X_row, X_col, cosine)
+        ctx.save_for_backward(row_ptr, col_ind, col_ptr, row_ind, beta, X_row, X_col, out, row_max, row_sum)
+        ctx.cosine = bool(cosine)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        row_ptr, col_ind, col_ptr, row_ind, beta, X_row, X_col, out, row_max, row_sum = ctx.saved_tensors
+        dX_row, dX_col, dbeta = fused_gt.agnn_backward(row_ptr, col_ind, col_ptr, row_ind, beta, X_row, X_col, out, row_max,
+                                                       row_sum, grad_out.contiguous(), ctx.cosine,
+                                                       need_dbeta=ctx.needs_input_grad[4])
+        # (one tensor passed as both X_row and X_col: autograd adds the two gradients)
+        return None, None, None, None, dbeta, dX_row, dX_col, None
+
+
+def AGNNConvFuse(row_ptr, col_ind, col_ptr, row_ind, beta, X_row, X_col, cosine=True):
+    """Differentiable AGNN (cosine=True) / dot-product (cosine=False) conv of any graph, square or m x n_cols; the gradient
+    goes to beta, X_row and X_col."""
+    return FusedAGNNFunction.apply(row_ptr, col_ind, col_ptr, row_ind, beta, X_row, X_col, cosine)
+
+
 class FusedGTFunction_bias(torch.autograd.Function):
     """FusedGTFunction_rowstats with a per-edge, per-head additive attention bias (include/dfgnn.h: dfgnn_gt_fwd_bias /
     dfgnn_gt_bwd_bias, csrc/gt_bias_train.hip): s_e = val_e <Q_i, K_j> + bias[h, e], bias fp32[h, nnz] in CSR edge order,

@@ -587,6 +587,48 @@ int dfgnn_gatv2_bwd(int m, int nnz, int h, int f, const int *row_ptr, const int 
                               row_max, row_sum, grad_out, delta, ws, dX_row, dX_col, dattn, stream);
 }
 
+// ---- AGNN / dot-product attention with tied keys and values (agnn_train.hip): fused inference and training pair, any graph ---
+int dfgnn_agnn_fwd_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *beta,
+                        int cosine, const float *X_row, const float *X_col, float *row_max, float *row_sum, float *out,
+                        dfgnn_stream_t stream) {
+  if (cosine != 0 && cosine != 1) return kErrBadArg;
+  if (int c = check_rect(m, n_cols, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (m == 0) return 0;  // (no row: nothing to write)
+  if (!beta || !X_row || (n_cols > 0 && !X_col) || !out || (!row_max != !row_sum)) return kErrBadArg;  // (both statistics or neither)
+  const Csr g = rect_csr(m, n_cols, nnz, h, f, row_ptr, col_ind, nullptr);
+  return launch_agnn_fwd(g, AgnnGraph{nullptr, nullptr, beta, cosine == 1}, X_row, X_col, row_max, row_sum, out,
+                         as_stream(stream));
+}
+
+int dfgnn_agnn_fwd(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *beta, int cosine,
+                   const float *X_row, const float *X_col, float *row_max, float *row_sum, float *out,
+                   dfgnn_stream_t stream) {
+  return dfgnn_agnn_fwd_rect(m, m, nnz, h, f, row_ptr, col_ind, beta, cosine, X_row, X_col, row_max, row_sum, out, stream);
+}
+
+int dfgnn_agnn_bwd_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const int *col_ptr,
+                        const int *row_ind, const float *beta, int cosine, const float *X_row, const float *X_col,
+                        const float *out, const float *row_max, const float *row_sum, const float *grad_out, float *delta,
+                        float *dX_row, float *dX_col, float *dbeta_rows, dfgnn_stream_t stream) {
+  if (cosine != 0 && cosine != 1) return kErrBadArg;
+  if (int c = check_rect(m, n_cols, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (!beta || (nnz > 0 && !row_ind)) return kErrBadArg;
+  if (m > 0 && (!X_row || !out || !row_max || !row_sum || !grad_out || !delta || !dX_row)) return kErrBadArg;
+  if (n_cols > 0 && (!X_col || !dX_col || !col_ptr)) return kErrBadArg;
+  if (dX_row && dX_row == dX_col) return kErrBadArg;  // (the two passes each write their buffer in full)
+  const Csr g = rect_csr(m, n_cols, nnz, h, f, row_ptr, col_ind, nullptr);
+  return launch_agnn_bwd(g, AgnnGraph{col_ptr, row_ind, beta, cosine == 1}, X_row, X_col, out, row_max, row_sum, grad_out,
+                         delta, dX_row, dX_col, dbeta_rows, as_stream(stream));
+}
+
+int dfgnn_agnn_bwd(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const int *col_ptr,
+                   const int *row_ind, const float *beta, int cosine, const float *X_row, const float *X_col,
+                   const float *out, const float *row_max, const float *row_sum, const float *grad_out, float *delta,
+                   float *dX_row, float *dX_col, float *dbeta_rows, dfgnn_stream_t stream) {
+  return dfgnn_agnn_bwd_rect(m, m, nnz, h, f, row_ptr, col_ind, col_ptr, row_ind, beta, cosine, X_row, X_col, out, row_max,
+                             row_sum, grad_out, delta, dX_row, dX_col, dbeta_rows, stream);
+}
+
 // ---- GATv2 with a per-edge feature vector inside the LeakyReLU (gatv2_edge_train.hip) ---------------------------------------
 int dfgnn_gatv2_fwd_edge_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind,
                               const float *attn, float negative_slope, const float *X_row, const float *X_col, const float *E,

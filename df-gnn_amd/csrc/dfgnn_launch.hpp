@@ -311,6 +311,20 @@ int launch_gatv2_edge_bwd(const Csr &g, const Gatv2Graph &v, const int *val_idx,
                           const float *E, const float *out, const float *row_max, const float *row_sum,
                           const float *grad_out, float *delta, float *ws, float *dX_row, float *dX_col, float *dattn,
                           float *dE, hipStream_t s);
+// AGNN / dot-product pair with tied keys and values (agnn_train.hip): any graph, no plan.  s_e = beta[h] r_i q_j <X_row_i,
+// X_col_j> with r, q the inverse row norms (cosine) or 1; X_col_j is key and value, gathered once per edge.  The forward
+// saves row_max / row_sum [m, h] (both nullable: inference); the backward is the CSR pass (delta, dX_row and, when it is not
+// null, dbeta_rows [m, h]) then the CSC pass (dX_col), on one stream.  No workspace.
+struct AgnnGraph {
+  const int *col_ptr, *row_ind;  // CSC (backward only)
+  const float *beta;             // [h]
+  bool cosine;
+};
+int launch_agnn_fwd(const Csr &g, const AgnnGraph &v, const float *X_row, const float *X_col, float *row_max,
+                    float *row_sum, float *out, hipStream_t s);
+int launch_agnn_bwd(const Csr &g, const AgnnGraph &v, const float *X_row, const float *X_col, const float *out,
+                    const float *row_max, const float *row_sum, const float *grad_out, float *delta, float *dX_row,
+                    float *dX_col, float *dbeta_rows, hipStream_t s);
 // graphs with fewer than kBlockMinAvgDegree edges per row on average take the row-per-lane-group kernels.  The pairs that
 // take an m x n_cols graph ask per pass: (m, nnz) for the forward and the CSR pass, (n_cols, nnz) for the CSC pass
 inline bool low_degree(int m, int nnz) { return (long)nnz < (long)kBlockMinAvgDegree * m; }

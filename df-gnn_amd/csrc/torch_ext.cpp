@@ -806,6 +806,63 @@ std::vector<Tensor> gatv2_bwd(double slope, const Tensor &row_ptr, const Tensor 
   return {dX_row, dX_col, dattn};
 }
 
+// ---- AGNN / dot-product attention with tied keys and values (include/dfgnn.h: dfgnn_agnn_fwd / dfgnn_agnn_bwd): any graph ----
+// What both entry points check: X_row fp32 [m, heads, feat], X_col fp32 [n_cols, heads, feat], beta fp32 [heads], the CSR arrays
+Dims agnn_checks(const Tensor &beta, const Tensor &row_ptr, const Tensor &col_ind, const Tensor &X_row, const Tensor &X_col) {
+  check_i32(row_ptr, "row_ptr");
+  check_i32(col_ind, "col_ind");
+  check_feat3(X_row, X_row, "X_row");
+  check_cols_feat(X_col, "X_col", X_row, "X_row");
+  check_f32(beta, "beta");
+  TORCH_CHECK(beta.dim() == 1 && beta.size(0) == X_row.size(1), "beta must have shape (", X_row.size(1), ",), got ",
+              shape_str(beta));
+  TORCH_CHECK(row_ptr.dim() == 1 && col_ind.dim() == 1, "indptr / indices must be 1-D");
+  TORCH_CHECK(row_ptr.size(0) - 1 == X_row.size(0), "indptr describes ", row_ptr.size(0) - 1, " rows but features have ",
+              X_row.size(0), " nodes");
+  check_same_device(X_row, {&beta, &row_ptr, &col_ind, &X_col});
+  return Dims{(int)X_row.size(0), (int)col_ind.size(0), (int)X_row.size(1), (int)X_row.size(2), (int)X_col.size(0)};
+}
+
+// save_stats = false: inference -> {out}; else the training forward -> {out, row_max, row_sum}
+std::vector<Tensor> agnn_fwd(const Tensor &row_ptr, const Tensor &col_ind, const Tensor &beta, bool cosine, const Tensor &X_row,
+                             const Tensor &X_col, bool save_stats) {
+  const Dims d = agnn_checks(beta, row_ptr, col_ind, X_row, X_col);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(X_row.device());
+  Tensor out = torch::empty_like(X_row);
+  Tensor row_max, row_sum;
+  if (save_stats) {
+    row_max = torch::empty({d.m, d.h}, X_row.options());
+    row_sum = torch::empty({d.m, d.h}, X_row.options());
+  }
+  check_rc(dfgnn_agnn_fwd_rect(d.m, d.n_cols, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), f32(beta), cosine ? 1 : 0, f32(X_row),
+                               f32(X_col), f32(row_max), f32(row_sum), f32(out), cur_stream()),
+           save_stats ? "agnn_forward" : "agnn_inference");
+  if (!save_stats) return {out};
+  return {out, row_max, row_sum};
+}
+
+// -> {dX_row, dX_col} and, with need_dbeta, dbeta [h]: the column sum of the rows' shares the CSR pass writes
+std::vector<Tensor> agnn_bwd(const Tensor &row_ptr, const Tensor &col_ind, const Tensor &col_ptr, const Tensor &row_ind,
+                             const Tensor &beta, bool cosine, const Tensor &X_row, const Tensor &X_col, const Tensor &out,
+                             const Tensor &row_max, const Tensor &row_sum, const Tensor &grad, bool need_dbeta) {
+  const Dims d = agnn_checks(beta, row_ptr, col_ind, X_row, X_col);
+  csc_rect_checks(d, X_row, col_ptr, row_ind, nullptr, "X_col");
+  check_feat3(out, X_row, "out");
+  check_feat3(grad, X_row, "grad");
+  row_stats_checks(d, X_row, row_max, row_sum);
+  check_same_device(X_row, {&out, &grad});
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(X_row.device());
+  Tensor dX_row = torch::empty_like(X_row), dX_col = torch::empty_like(X_col);
+  Tensor delta = torch::empty({d.m, d.h}, X_row.options()), dbeta_rows;
+  if (need_dbeta) dbeta_rows = torch::empty({d.m, d.h}, X_row.options());
+  check_rc(dfgnn_agnn_bwd_rect(d.m, d.n_cols, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), i32(col_ptr), i32(row_ind), f32(beta),
+                               cosine ? 1 : 0, f32(X_row), f32(X_col), f32(out), f32(row_max), f32(row_sum), f32(grad),
+                               f32(delta), f32(dX_row), f32(dX_col), f32(dbeta_rows), cur_stream()),
+           "agnn_backward");
+  if (!need_dbeta) return {dX_row, dX_col};
+  return {dX_row, dX_col, dbeta_rows.sum(0)};
+}
+
 // ---- GATv2 with a per-edge feature vector inside the LeakyReLU (include/dfgnn.h: dfgnn_gatv2_fwd_edge / dfgnn_gatv2_bwd_edge) ----
 // a dtype as Python prints it, so that a dtype error reads the same through either transport (_binding_util._family)
 std::string py_dtype(const Tensor &t) {
@@ -999,6 +1056,8 @@ PYBIND11_MODULE(_dfgnn_ext, m) {
   m.def("gat_bwd", &gat_bwd, "fused GAT conv backward");
   m.def("gatv2_fwd", &gatv2_fwd, "fused GATv2 conv forward of any graph (inference, or training with row statistics)");
   m.def("gatv2_bwd", &gatv2_bwd, "fused GATv2 conv backward of any graph from the forward's output and row statistics");
+  m.def("agnn_fwd", &agnn_fwd, "fused AGNN / dot-product conv forward of any graph, keys = values (inference, or training with row statistics)");
+  m.def("agnn_bwd", &agnn_bwd, "fused AGNN / dot-product conv backward of any graph from the forward's output and row statistics");
   m.def("gatv2_fwd_edge", &gatv2_fwd_edge, "fused GATv2 conv forward of any graph with a per-edge feature vector inside the LeakyReLU");
   m.def("gatv2_bwd_edge", &gatv2_bwd_edge, "fused GATv2 conv backward of any graph with a per-edge feature vector inside the LeakyReLU");
   m.def("gt_variant_fwd", &gt_variant_fwd, "fused GT conv inference: tiling / csr / csr_gm / softmax / softmax_gm");

@@ -66,6 +66,10 @@ SIGNATURES = {
     "dfgnn_gatv2_bwd_edge": [_i] * 4 + [_vp] * 6 + [_f] + [_vp] * 14,
     "dfgnn_gatv2_fwd_edge_rect": [_i] * 5 + [_vp] * 3 + [_f] + [_vp] * 7,
     "dfgnn_gatv2_bwd_edge_rect": [_i] * 5 + [_vp] * 6 + [_f] + [_vp] * 14,
+    "dfgnn_agnn_fwd": [_i] * 4 + [_vp] * 3 + [_i] + [_vp] * 6,
+    "dfgnn_agnn_bwd": [_i] * 4 + [_vp] * 5 + [_i] + [_vp] * 11,
+    "dfgnn_agnn_fwd_rect": [_i] * 5 + [_vp] * 3 + [_i] + [_vp] * 6,
+    "dfgnn_agnn_bwd_rect": [_i] * 5 + [_vp] * 5 + [_i] + [_vp] * 11,
     "dfgnn_gt_bwd_rows": [_i, _i, _i, _i] + [_vp] * 11,
     "dfgnn_gt_bwd_cols": [_i, _i, _i, _i] + [_vp] * 11,
     "dfgnn_gt_tiling_fwd": [_i, _i, _i, _i] + [_vp] * 8,

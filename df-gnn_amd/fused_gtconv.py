@@ -641,6 +641,66 @@ def gt_backward_tbias(row_ptr, col_ind, val, etype, col_ptr, row_ind, val_idx, e
     return [dQ, dK, dV, dB]
 
 
+# ---- AGNN / dot-product attention with tied keys and values (include/dfgnn.h: dfgnn_agnn_fwd / dfgnn_agnn_bwd) -----------
+# Not part of the reference's module.  s_e = beta[h] r_i q_j <X_row_i, X_col_j> with r, q the inverse row norms (cosine: AGNN)
+# or 1 (dot-product attention), message X_col_j (csrc/agnn_train.hip): the neighbour row is key and value, gathered once per
+# edge; nothing per node is precomputed.  Any graph, square or m x n_cols, no plan, any f.
+# DFGNN.operators.fused_gtconv.AGNNConvFuse takes it.
+
+
+def _check_agnn(row_ptr, col_ind, beta, X_row, X_col, **like_X):
+    """X_row (and `like_X`: out, grad) fp32 [m, heads, feat], X_col fp32 [n_cols, heads, feat], beta fp32 [heads], the CSR
+    arrays of the m rows -> (m, n_cols, nnz, h, f)."""
+    m, h, f = check_feats(X_row=X_row, **like_X)
+    n_cols = check_cols("X_row", X_row, X_col=X_col)
+    check_family(X_row, torch.float32, beta=beta)
+    if tuple(beta.shape) != (h,):
+        raise RuntimeError(f"beta must have shape ({h},), got {tuple(beta.shape)}")
+    return m, n_cols, check_csr(X_row, m, row_ptr, col_ind), h, f
+
+
+def _agnn_fwd(what, save_stats, row_ptr, col_ind, beta, X_row, X_col, cosine):
+    ext = _n.ext()
+    if ext is not None:
+        return ext.agnn_fwd(row_ptr, col_ind, beta, bool(cosine), X_row, X_col, save_stats)
+    m, n_cols, nnz, h, f = _check_agnn(row_ptr, col_ind, beta, X_row, X_col)
+    out = torch.empty_like(X_row)
+    row_max, row_sum = (_empty(X_row, m, h), _empty(X_row, m, h)) if save_stats else (None, None)
+    call("dfgnn_agnn_fwd_rect", what, X_row.device, m, n_cols, nnz, h, f, row_ptr, col_ind, beta, int(bool(cosine)), X_row, X_col,
+         row_max, row_sum, out)
+    return [out, row_max, row_sum] if save_stats else [out]
+
+
+def agnn_inference(row_ptr, col_ind, beta, X_row, X_col, cosine=True):
+    """-> out[m, h, f].  beta fp32[h]; X_row and X_col may be the same tensor.  cosine=False: plain dot-product logits."""
+    return _agnn_fwd("agnn_inference", False, row_ptr, col_ind, beta, X_row, X_col, cosine)[0]
+
+
+def agnn_forward(row_ptr, col_ind, beta, X_row, X_col, cosine=True):
+    """-> [out, row_max[m, h], row_sum[m, h]]: the training forward; the same `out` as agnn_inference."""
+    return _agnn_fwd("agnn_forward", True, row_ptr, col_ind, beta, X_row, X_col, cosine)
+
+
+def agnn_backward(row_ptr, col_ind, col_ptr, row_ind, beta, X_row, X_col, out, row_max, row_sum, grad, cosine=True,
+                  need_dbeta=True):
+    """-> [dX_row, dX_col, dbeta[h]] from the forward's output and row statistics (each edge is recomputed); dbeta is None
+    without need_dbeta (then the rows' shares [m, h] are neither allocated nor written; dX_row and dX_col are the same
+    bits).  With X_row is X_col the gradient of the shared tensor is dX_row + dX_col."""
+    ext = _n.ext()
+    if ext is not None:
+        res = ext.agnn_bwd(row_ptr, col_ind, col_ptr, row_ind, beta, bool(cosine), X_row, X_col, out, row_max, row_sum, grad,
+                           bool(need_dbeta))
+        return res if need_dbeta else res + [None]
+    m, n_cols, nnz, h, f = _check_agnn(row_ptr, col_ind, beta, X_row, X_col, out=out, grad=grad)
+    check_csc_rect(X_row, n_cols, nnz, col_ptr, "X_col", row_ind=row_ind)
+    check_2d(X_row, m, h, row_max=row_max, row_sum=row_sum)
+    dX_row, dX_col, delta = torch.empty_like(X_row), torch.empty_like(X_col), _empty(X_row, m, h)
+    dbeta_rows = _empty(X_row, m, h) if need_dbeta else None
+    call("dfgnn_agnn_bwd_rect", "agnn_backward", X_row.device, m, n_cols, nnz, h, f, row_ptr, col_ind, col_ptr, row_ind, beta,
+         int(bool(cosine)), X_row, X_col, out, row_max, row_sum, grad, delta, dX_row, dX_col, dbeta_rows)
+    return [dX_row, dX_col, dbeta_rows.sum(0) if need_dbeta else None]
+
+
 # ---- the CSR-taking inference variants ----------------------------------------------------------------------------------
 _VARIANTS = ("gt_tiling", "gt_csr", "gt_csr_gm", "gt_softmax", "gt_softmax_gm")   # by `which` of torch_ext.cpp: gt_variant_fwd
 

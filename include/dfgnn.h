@@ -510,6 +510,49 @@ int dfgnn_gatv2_bwd_edge_rect(int m, int n_cols, int nnz, int h, int f, const in
                               const float *row_max, const float *row_sum, const float *grad_out, float *delta, float *ws,
                               float *dX_row, float *dX_col, float *dattn, float *dE, dfgnn_stream_t stream);
 
+/* AGNN / dot-product attention with TIED keys and values (csrc/agnn_train.hip): fused inference and training pair for ANY
+ * graph, no plan, no degree limit, any f.  The neighbour row X_col[j] is the key AND the value of edge (i, j) -- up to one
+ * scalar per node, which is computed from the registers that hold the row -- so every pass gathers it once per edge and
+ * nothing per node is precomputed.  Per head:
+ *   cosine = 1:  r_i = 1 / max(|X_row[i]|_2, 1e-12),  q_j = 1 / max(|X_col[j]|_2, 1e-12)     (F.normalize's eps)
+ *   cosine = 0:  r_i = q_j = 1
+ *   c_e = r_i q_j <X_row[i], X_col[j]>,  s_e = beta[h] c_e
+ *   P_e = exp(s_e - row_max_i) / row_sum_i,  out_i = sum_e P_e X_col[j]
+ *   delta_i = <grad_out_i, out_i>,  dS_e = P_e (<grad_out_i, X_col[j]> - delta_i)
+ *   g_i  = sum_{e of row i} dS_e c_e  -> dbeta_rows[i, h]        (dbeta[h] = sum_i g_i: the caller's column sum)
+ *   g'_j = sum_{e into j} dS_e c_e
+ *   dX_row[i] = beta r_i ( sum_{e of i} dS_e q_j X_col[j]  -  k g_i r_i X_row[i] )
+ *   dX_col[j] = sum_{e into j} P_e grad_out_i  +  beta q_j ( sum_{e into j} dS_e r_i X_row[i]  -  k g'_j q_j X_col[j] ),  k = cosine
+ * cosine = 1 is AGNN (softmax_j(beta cos(h_i, h_j)), PyG's / DGL's AGNNConv); cosine = 0 with beta = f^-1/2 is dot-product
+ * graph attention (DotGatConv).  A feature row of zeros has norm 0, c = 0 and a gradient of order beta / 1e-12, exactly as
+ * F.normalize's autograd gives: no special case.
+ *   beta     fp32[h] on the device (a parameter)
+ *   cosine   0 or 1
+ *   X_row, X_col  fp32[m, h, f]; may be the same pointer.  dX_row and dX_col are distinct buffers
+ *   row_max = row_sum = NULL in the forward: nothing is saved (inference); otherwise both are set.  Empty row: out = 0,
+ *            row_max = -1e38, row_sum = 0, dX_row = 0, dbeta_rows = 0; empty column: dX_col = 0
+ *   delta    caller scratch fp32[m, h], written by the CSR pass and read by the CSC pass
+ *   dbeta_rows  fp32[m, h], written in full, or NULL: beta needs no gradient (everything else is bit-identical)
+ * No edge values.  No atomics, no workspace: every output is written in full by plain stores and is deterministic.
+ * Return codes as dfgnn_gatv2_*: DFGNN_E_BADARG for a missing pointer, one statistic without the other, a cosine other than
+ * 0 / 1, dX_row == dX_col; DFGNN_E_UNSUPPORTED for h > 65535 or f outside the compiled range.  The square entries are the
+ * n_cols = m case of the *_rect ones (X_col, dX_col fp32[n_cols, h, f], col_ptr int32[n_cols+1]; see
+ * dfgnn_gt_fwd_rowstats_rect, also for the degenerate extents): same kernels, same bits. */
+int dfgnn_agnn_fwd(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *beta, int cosine,
+                   const float *X_row, const float *X_col, float *row_max, float *row_sum, float *out,
+                   dfgnn_stream_t stream);
+int dfgnn_agnn_bwd(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const int *col_ptr,
+                   const int *row_ind, const float *beta, int cosine, const float *X_row, const float *X_col,
+                   const float *out, const float *row_max, const float *row_sum, const float *grad_out, float *delta,
+                   float *dX_row, float *dX_col, float *dbeta_rows, dfgnn_stream_t stream);
+int dfgnn_agnn_fwd_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *beta,
+                        int cosine, const float *X_row, const float *X_col, float *row_max, float *row_sum, float *out,
+                        dfgnn_stream_t stream);
+int dfgnn_agnn_bwd_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const int *col_ptr,
+                        const int *row_ind, const float *beta, int cosine, const float *X_row, const float *X_col,
+                        const float *out, const float *row_max, const float *row_sum, const float *grad_out, float *delta,
+                        float *dX_row, float *dX_col, float *dbeta_rows, dfgnn_stream_t stream);
+
 /* weights[256 i + c] = val[e] for the edge e from node i to the c-th node of i's range of the plan, 0 elsewhere:
  * dfgnn_plan_dense_weights_floats(m) = 256 m floats (device, 16-byte aligned), written by one memset + one kernel on
  * `stream`.  val: fp32[nnz] in CSR order.  Only the dense ranges of the plan are filled (dfgnn_gt_stats_applies == 1:
