@@ -24,7 +24,7 @@ constexpr int kLeanLdsBytes = 80 * 1024;
 // STATS: the forward of the statistics-saving training pair (see dense_fwd_body): edge bitmaps instead of the byte map,
 // row statistics (stat_max, stat_sum: [m, h]) instead of the attention values.
 template <int F, bool WRITE_ATTN, bool STATS = false>
-__global__ __launch_bounds__(kLeanThreads, 2) void gt_dense_fwd_lean_kernel(Csr g, const int *__restrict__ fit,
+__global__ __launch_bounds__(kLeanThreads, 2) void gt_dense_fwd_lean_kernel(Csr g, const PlanDesc *__restrict__ desc,
                                                                            const float *__restrict__ Q,
                                                                            const float *__restrict__ K,
                                                                            const float *__restrict__ V,
@@ -39,8 +39,8 @@ __global__ __launch_bounds__(kLeanThreads, 2) void gt_dense_fwd_lean_kernel(Csr 
   using D = DenseCfg<FW>;
   constexpr int RS = D::RS, KT = D::KT, FT = D::FT, MS = NP + 4;
   constexpr int PER = NP * (FW / 8) / kLeanThreads;  // 8-float pieces of an image per thread (4)
-  const int n0 = fit[2 * blockIdx.x], n1 = fit[2 * blockIdx.x + 1] & kPlanRangeMask;
-  const int n = n1 - n0, e0 = g.row_ptr[n0], ne = g.row_ptr[n1] - e0, head = blockIdx.y;
+  const PlanDesc d = desc[blockIdx.x];  // (one scalar load: dfgnn_launch.hpp)
+  const int n0 = d.n0, n = (d.n1f & kPlanRangeMask) - n0, e0 = d.e0, ne = d.ne, head = blockIdx.y;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
   const int npad = (n + 31) & ~31, ntile = npad >> 4, nstrip = (n + 15) >> 4;
   h16 *ihi = reinterpret_cast<h16 *>(lds), *ilo = ihi + NP * RS;

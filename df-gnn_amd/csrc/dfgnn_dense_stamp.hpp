@@ -30,10 +30,22 @@ __device__ unsigned long long *dfgnn_wg_trace = nullptr;
     t_[1] = __builtin_amdgcn_s_memtime();                                                           \
     t_[4] = __builtin_amdgcn_s_memrealtime();                                                       \
   }
+// kernel entry / exit around the phase stamps: the entry time is TAKEN first thing, ahead of the range's descriptor load,
+// but kept in registers and stored with the exit time (slot 14 = entry, 13 = exit) -- so the entry stamp puts no load or
+// wait of its own in front of the chain it measures (entry -> DFGNN_DSTAMP(0): tools/diag/desc_chain.py)
+#define DFGNN_STAMP_ENTRY const unsigned long long dfgnn_t_entry_ = __builtin_amdgcn_s_memtime();
+#define DFGNN_STAMP_EXIT                                                                            \
+  if (threadIdx.x == 0 && dfgnn_dense_stamps) {                                                     \
+    unsigned long long *s_ = dfgnn_dense_stamps + ((size_t)blockIdx.x * gridDim.y + blockIdx.y) * 16; \
+    s_[14] = dfgnn_t_entry_;                                                                        \
+    s_[13] = __builtin_amdgcn_s_memtime();                                                          \
+  }
 #else
 #define DFGNN_DSTAMP(k)
 #define DFGNN_TRACE_IN
 #define DFGNN_TRACE_OUT
+#define DFGNN_STAMP_ENTRY
+#define DFGNN_STAMP_EXIT
 #endif
 
 }  // namespace dfgnn

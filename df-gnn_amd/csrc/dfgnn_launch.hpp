@@ -62,7 +62,23 @@ constexpr int kPlanRangeMask = ~(kPlanEdgeGlobal | kPlanDense);
 constexpr int kPlanMaskWords = 8;                        // 32-bit words of a node's edge bitmap (dense ranges: < 256 nodes)
 // int32 offset of the edge bitmaps in a plan buffer whose packed coordinates start at coords_off
 inline size_t plan_mask_off(size_t coords_off, int nnz) { return (coords_off + ((size_t)nnz + 1) / 2 + 4 + 3) & ~(size_t)3; }
-
+// int32 offset of the dense ranges' descriptors: right behind the fit and spill lists, 16-byte aligned (kPlanHeader is a
+// multiple of 4) -- over the scratch of the build (pairs, bounds, count, rocPRIM storage: plan.hip), which is dead once
+// plan_cut_kernel has sorted the fit list.  The buffer keeps its size and every other offset.
+inline size_t plan_desc_off(int m) { return kPlanHeader + 4 * (size_t)m; }
+// Descriptors that fit between there and the packed coordinates (>= (3 m + 68) / 4).  The merge of plan_cut_kernel never
+// leaves two neighbouring groups that would still merge: two dense ranges in a row were kept apart by the 128-node limit
+// or by the LDS budget (duplicate-free, so edges <= nodes^2) and hold dozens of nodes together, every other pair of
+// neighbours has at most one dense range on two nodes or more -- num_dense <= (m + 1) / 2, i.e. 2 m + 2 words.
+// dfgnn_plan_build checks it all the same (kErrUnsupported), and plan_coords_kernel writes no descriptor past it.
+inline size_t plan_desc_capacity(int m, size_t coords_off) { return (coords_off - plan_desc_off(m)) / 4; }
+// What a matrix-core kernel needs to know of its range before its first vector load, in one 16-byte scalar load: the
+// fit entry (n0, n1 | flags) and e0 = row_ptr[n0], ne = row_ptr[n1] - e0.  Read through fit and row_ptr these are three
+// dependent scalar round trips (kernel arguments, fit pair, two row_ptr words on lines nothing else in the launch touches);
+// the plan knows all four when it is built.  desc[k] describes fit range k, k < num_dense.
+struct alignas(16) PlanDesc {
+  int n0, n1f, e0, ne;
+};
 struct Plan {              // host view of a built plan (see plan.hip for the device layout)
   const int *dev;          // device buffer, may be null (= no plan: general kernels only)
   int num_fit, num_spill, max_fit_nodes, max_fit_edges, m, nnz, f, num_edge_global;
@@ -79,6 +95,10 @@ struct Plan {              // host view of a built plan (see plan.hip for the de
   // (gt_dense_fwd_ranked_kernel) and its backward therefore reads them in
   size_t ranked_off() const { return mask_off() + 2 * (size_t)kPlanMaskWords * (size_t)m; }
   const unsigned short *coords_ranked() const { return reinterpret_cast<const unsigned short *>(dev + ranked_off()); }
+  // one descriptor per dense range, in the order of the fit list, behind the spill list: what the matrix-core kernels read
+  // where the edge-walking kernels read fit()
+  size_t desc_off() const { return plan_desc_off(m); }
+  const PlanDesc *desc() const { return reinterpret_cast<const PlanDesc *>(dev + desc_off()); }
   const int *fit() const { return dev + kPlanHeader; }
   const int *spill() const { return dev + kPlanHeader + 2 * (size_t)m; }
 };

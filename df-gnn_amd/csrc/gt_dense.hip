@@ -44,7 +44,7 @@
 namespace dfgnn {
 
 template <int F, bool WRITE_ATTN>
-__global__ __launch_bounds__(kDenseThreads) void gt_dense_fwd_kernel(Csr g, const int *__restrict__ fit,
+__global__ __launch_bounds__(kDenseThreads) void gt_dense_fwd_kernel(Csr g, const PlanDesc *__restrict__ desc,
                                                                      const float *__restrict__ Q,
                                                                      const float *__restrict__ K,
                                                                      const float *__restrict__ V,
@@ -52,8 +52,8 @@ __global__ __launch_bounds__(kDenseThreads) void gt_dense_fwd_kernel(Csr g, cons
                                                                      float *__restrict__ out, int lds_bytes) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   DFGNN_TRACE_IN
-  const int n0 = fit[2 * blockIdx.x], n1 = fit[2 * blockIdx.x + 1] & kPlanRangeMask;
-  const int n = n1 - n0, e0 = g.row_ptr[n0], ne = g.row_ptr[n1] - e0;
+  const PlanDesc d = desc[blockIdx.x];  // (one scalar load: dfgnn_launch.hpp)
+  const int n0 = d.n0, n = (d.n1f & kPlanRangeMask) - n0, e0 = d.e0, ne = d.ne;
   if (g.h == 1) {
     if (n <= kDenseChunkRows)
       dense_fwd_body<F, WRITE_ATTN, 1, kDenseChunkRows, 1>(lds, lds_bytes, g, n0, n, e0, ne, 0, 1, Q, K, V, attn_edge, out);
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(kDenseThreads) void gt_dense_fwd_kernel(Csr g, cons
 // GAT 'hyper' forward over the dense ranges: replaces fused_gat_hyper_inference{,_vec4}
 // (DFGNN/src/fused_gatconv/fused_gatconv_hyper.cu:5-224) for them.
 template <int F>
-__global__ __launch_bounds__(kDenseThreads) void gat_dense_fwd_kernel(Csr g, const int *__restrict__ fit,
+__global__ __launch_bounds__(kDenseThreads) void gat_dense_fwd_kernel(Csr g, const PlanDesc *__restrict__ desc,
                                                                       const float *__restrict__ attn_row,
                                                                       const float *__restrict__ attn_col, float slope,
                                                                       const float *__restrict__ X,
@@ -102,8 +102,8 @@ __global__ __launch_bounds__(kDenseThreads) void gat_dense_fwd_kernel(Csr g, con
                                                                       float *__restrict__ edge_max,
                                                                       float *__restrict__ edge_sum, DenseDrop drop) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int n0 = fit[2 * blockIdx.x], n1 = fit[2 * blockIdx.x + 1] & kPlanRangeMask;
-  const int n = n1 - n0, e0 = g.row_ptr[n0], ne = g.row_ptr[n1] - e0;
+  const PlanDesc d = desc[blockIdx.x];  // (one scalar load: dfgnn_launch.hpp)
+  const int n0 = d.n0, n = (d.n1f & kPlanRangeMask) - n0, e0 = d.e0, ne = d.ne;
   if (n <= kDenseChunkRows)
     dense_fwd_body<F, false, 1, kDenseChunkRows, 1, true>(lds, lds_bytes, g, n0, n, e0, ne, blockIdx.y, 1, attn_row, attn_col, X,
                                                           nullptr, out, slope, edge_max, edge_sum, drop);
@@ -119,11 +119,11 @@ __global__ __launch_bounds__(kDenseThreads) void gat_dense_fwd_kernel(Csr g, con
 // fused_backward_kernel (DFGNN/src/fused_gatconv/fused_gatconv_kernel.cu:609-865) for them.
 template <int F>
 __global__ __launch_bounds__(kDenseThreads) void gat_dense_bwd_kernel(
-    Csr g, const int *__restrict__ fit, const float *__restrict__ attn_row, const float *__restrict__ attn_col,
+    Csr g, const PlanDesc *__restrict__ desc, const float *__restrict__ attn_row, const float *__restrict__ attn_col,
     const float *__restrict__ X, const float *__restrict__ dO, float *__restrict__ grad_feat, GatBwdArgs ga) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int n0 = fit[2 * blockIdx.x], n1 = fit[2 * blockIdx.x + 1] & kPlanRangeMask;
-  const int n = n1 - n0, e0 = g.row_ptr[n0], ne = g.row_ptr[n1] - e0;
+  const PlanDesc d = desc[blockIdx.x];  // (one scalar load: dfgnn_launch.hpp)
+  const int n0 = d.n0, n = (d.n1f & kPlanRangeMask) - n0, e0 = d.e0, ne = d.ne;
   if (n <= kDenseChunkRows)
     dense_bwd_body<F, kDenseChunkRows, 1, true>(lds, g, n0, n, e0, ne, blockIdx.y, attn_row, attn_col, X, nullptr, dO,
                                                 nullptr, nullptr, grad_feat, ga);
@@ -137,10 +137,11 @@ __global__ __launch_bounds__(kDenseThreads) void gat_dense_bwd_kernel(
 
 template <int F>
 __global__ __launch_bounds__(kDenseThreads) void gt_dense_bwd_kernel(
-    Csr g, const int *__restrict__ fit, const float *__restrict__ Q, const float *__restrict__ K,
+    Csr g, const PlanDesc *__restrict__ desc, const float *__restrict__ Q, const float *__restrict__ K,
     const float *__restrict__ V, const float *__restrict__ attn_edge, const float *__restrict__ dO,
     float *__restrict__ dQ, float *__restrict__ dK, float *__restrict__ dV, int heads_from, int walk, int keep, int tail) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
+  DFGNN_STAMP_ENTRY
   DFGNN_TRACE_IN
   // heads_from < 0: grid (ranges, heads), one workgroup per (range, head).  heads_from >= 0 (multi-head, heads of at
   // most 64 features): a 1-D grid -- the first heads_from ranges (those of more than 128 nodes: they come first in the
@@ -169,8 +170,8 @@ __global__ __launch_bounds__(kDenseThreads) void gt_dense_bwd_kernel(
   // are handed out last, largest of them first, so that the launch ends on short jobs (launch_gt_dense_bwd: cost and gain).
   if (keep >= 0 && heads_from < 0 && range >= keep && range < (int)gridDim.x - tail)
     range = (int)gridDim.x - tail - 1 - (range - keep);
-  const int n0 = fit[2 * range], n1 = fit[2 * range + 1] & kPlanRangeMask;
-  const int n = n1 - n0, e0 = g.row_ptr[n0], ne = g.row_ptr[n1] - e0;
+  const PlanDesc d = desc[range];  // (one scalar load: dfgnn_launch.hpp)
+  const int n0 = d.n0, n = (d.n1f & kPlanRangeMask) - n0, e0 = d.e0, ne = d.ne;
   if constexpr (F <= 64) {
     if (nwalk > 0) {  // (n <= 128 by construction)
       dense_bwd_heads_body<F>(lds, g, n0, n, e0, ne, head, nwalk, Q, K, V, attn_edge, dO, dQ, dK, dV);
@@ -206,6 +207,7 @@ __global__ __launch_bounds__(kDenseThreads) void gt_dense_bwd_kernel(
     if (!wide2) dense_bwd_body<F, kDenseChunkRows, 2>(lds, g, n0, n, e0, ne, head, Q, K, V, attn_edge, dO, dQ, dK, dV);
   }
   DFGNN_TRACE_OUT
+  DFGNN_STAMP_EXIT
 #ifdef DFGNN_STAMPS
   if (threadIdx.x == 0 && dfgnn_dense_stamps)
     dfgnn_dense_stamps[((size_t)blockIdx.x * gridDim.y + blockIdx.y) * 16 + 15] = ((unsigned long long)n << 32) | (unsigned)ne;
@@ -242,10 +244,10 @@ static int launch_gt_dense_fwd_single(const Csr &g_in, const Plan &p, const floa
     constexpr int F = decltype(fc)::value;
     if (attn_edge) {
       if (int rc = set_max_lds_cached(gt_dense_fwd_kernel<F, true>)) return rc;
-      gt_dense_fwd_kernel<F, true><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.fit(), Q, K, V, attn_edge, out, kLdsBytes);
+      gt_dense_fwd_kernel<F, true><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.desc(), Q, K, V, attn_edge, out, kLdsBytes);
     } else {
       if (int rc = set_max_lds_cached(gt_dense_fwd_kernel<F, false>)) return rc;
-      gt_dense_fwd_kernel<F, false><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.fit(), Q, K, V, nullptr, out, kLdsBytes);
+      gt_dense_fwd_kernel<F, false><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.desc(), Q, K, V, nullptr, out, kLdsBytes);
     }
     return launch_status();
   });
@@ -268,10 +270,10 @@ int launch_gt_dense_fwd(const Csr &g_in, const Plan &p, const float *Q, const fl
     if constexpr (F == 64 || F == 128) {
       if (attn_edge) {
         if (int rc = set_max_lds_cached(gt_dense_fwd_lean_kernel<F, true>)) return rc;
-        gt_dense_fwd_lean_kernel<F, true><<<grid, kLeanThreads, kLeanLdsBytes, s>>>(g, p.fit(), Q, K, V, attn_edge, out);
+        gt_dense_fwd_lean_kernel<F, true><<<grid, kLeanThreads, kLeanLdsBytes, s>>>(g, p.desc(), Q, K, V, attn_edge, out);
       } else {
         if (int rc = set_max_lds_cached(gt_dense_fwd_lean_kernel<F, false>)) return rc;
-        gt_dense_fwd_lean_kernel<F, false><<<grid, kLeanThreads, kLeanLdsBytes, s>>>(g, p.fit(), Q, K, V, nullptr, out);
+        gt_dense_fwd_lean_kernel<F, false><<<grid, kLeanThreads, kLeanLdsBytes, s>>>(g, p.desc(), Q, K, V, nullptr, out);
       }
     }
     return launch_status();
@@ -290,7 +292,7 @@ int launch_gat_dense_fwd(const Csr &g_in, const Plan &p, const float *attn_row, 
   return dispatch_dense(g.f, [&](auto fc) {
     constexpr int F = decltype(fc)::value;
     if (int rc = set_max_lds_cached(gat_dense_fwd_kernel<F>)) return rc;
-    gat_dense_fwd_kernel<F><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.fit(), attn_row, attn_col, slope, X, out, kLdsBytes,
+    gat_dense_fwd_kernel<F><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.desc(), attn_row, attn_col, slope, X, out, kLdsBytes,
                                                                    edge_max, edge_sum, drop);
     return launch_status();
   });
@@ -309,7 +311,7 @@ int launch_gat_dense_bwd(const Csr &g_in, const Plan &p, const float *attn_row, 
   return dispatch_dense(g.f, [&](auto fc) {
     constexpr int F = decltype(fc)::value;
     if (int rc = set_max_lds_cached(gat_dense_bwd_kernel<F>)) return rc;
-    gat_dense_bwd_kernel<F><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.fit(), attn_row, attn_col, X, grad_out, grad_feat, ga);
+    gat_dense_bwd_kernel<F><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.desc(), attn_row, attn_col, X, grad_out, grad_feat, ga);
     return launch_status();
   });
 }
@@ -355,7 +357,7 @@ int launch_gt_dense_bwd(const Csr &g_in, const Plan &p, const float *Q, const fl
   return dispatch_dense(g.f, [&](auto fc) {
     constexpr int F = decltype(fc)::value;
     if (int rc = set_max_lds_cached(gt_dense_bwd_kernel<F>)) return rc;
-    gt_dense_bwd_kernel<F><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.fit(), Q, K, V, attn_edge, grad_out, dQ, dK, dV,
+    gt_dense_bwd_kernel<F><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.desc(), Q, K, V, attn_edge, grad_out, dQ, dK, dV,
                                                                   heads_from, walk, keep, tail);
     return launch_status();
   });

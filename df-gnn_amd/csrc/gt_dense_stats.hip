@@ -32,7 +32,7 @@
 namespace dfgnn {
 
 template <int F>
-__global__ __launch_bounds__(kDenseThreads) void gt_dense_fwd_stats_kernel(Csr g, const int *__restrict__ fit,
+__global__ __launch_bounds__(kDenseThreads) void gt_dense_fwd_stats_kernel(Csr g, const PlanDesc *__restrict__ desc,
                                                                            const float *__restrict__ Q,
                                                                            const float *__restrict__ K,
                                                                            const float *__restrict__ V,
@@ -40,8 +40,8 @@ __global__ __launch_bounds__(kDenseThreads) void gt_dense_fwd_stats_kernel(Csr g
                                                                            float *__restrict__ stat_max,
                                                                            float *__restrict__ stat_sum, int lds_bytes) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int n0 = fit[2 * blockIdx.x], n1 = fit[2 * blockIdx.x + 1] & kPlanRangeMask;
-  const int n = n1 - n0;
+  const PlanDesc d = desc[blockIdx.x];  // (one scalar load: dfgnn_launch.hpp)
+  const int n0 = d.n0, n = (d.n1f & kPlanRangeMask) - n0;
   if (g.h == 1) {
     if (n <= kDenseChunkRows)
       dense_fwd_body<F, false, 1, kDenseChunkRows, 1, false, false, true>(lds, lds_bytes, g, n0, n, 0, 0, 0, 1, Q, K, V, nullptr,
@@ -81,15 +81,15 @@ __global__ __launch_bounds__(kDenseThreads) void gt_dense_fwd_stats_kernel(Csr g
 // lie behind all the working ones: workgroups go to the XCDs round-robin by index, so the workers stay spread).
 template <int F>
 __global__ __launch_bounds__(kDenseThreads) void gt_dense_bwd_stats_kernel(
-    Csr g, const int *__restrict__ fit, const float *__restrict__ Q, const float *__restrict__ K,
+    Csr g, const PlanDesc *__restrict__ desc, const float *__restrict__ Q, const float *__restrict__ K,
     const float *__restrict__ V, const float *__restrict__ stat_max, const float *__restrict__ stat_sum,
     const float *__restrict__ dO, float *__restrict__ dQ, float *__restrict__ dK, float *__restrict__ dV, int heads2, int keep) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   int range = blockIdx.x;
   const int head = blockIdx.y;
   if (keep >= 0 && range >= keep) range = (int)gridDim.x - 1 - (range - keep);  // (launch_gt_dense_bwd, gt_dense.hip)
-  const int n0 = fit[2 * range], n1 = fit[2 * range + 1] & kPlanRangeMask;
-  const int n = n1 - n0;
+  const PlanDesc d = desc[range];  // (one scalar load: dfgnn_launch.hpp)
+  const int n0 = d.n0, n = (d.n1f & kPlanRangeMask) - n0;
   if constexpr (F == 16 || F == 32 || F == 64) {
     if (heads2 && n <= kDenseWideRows) {  // (heads2: the launcher's choice, uniform over the grid)
       if (head != 0) return;
@@ -131,13 +131,13 @@ int launch_gt_dense_fwd_stats(const Csr &g_in, const Plan &p, const float *Q, co
     if constexpr (F == 64 || F == 128) {
       if (lean) {
         if (int rc = set_max_lds_cached(gt_dense_fwd_lean_kernel<F, false, true>)) return rc;
-        gt_dense_fwd_lean_kernel<F, false, true><<<grid, kLeanThreads, kLeanLdsBytes, s>>>(g, p.fit(), Q, K, V, nullptr, out, stat_max,
+        gt_dense_fwd_lean_kernel<F, false, true><<<grid, kLeanThreads, kLeanLdsBytes, s>>>(g, p.desc(), Q, K, V, nullptr, out, stat_max,
                                                                                           stat_sum);
         return launch_status();
       }
     }
     if (int rc = set_max_lds_cached(gt_dense_fwd_stats_kernel<F>)) return rc;
-    gt_dense_fwd_stats_kernel<F><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.fit(), Q, K, V, out, stat_max, stat_sum, kLdsBytes);
+    gt_dense_fwd_stats_kernel<F><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.desc(), Q, K, V, out, stat_max, stat_sum, kLdsBytes);
     return launch_status();
   });
 }
@@ -157,7 +157,7 @@ int launch_gt_dense_bwd_stats(const Csr &g_in, const Plan &p, const float *Q, co
   return dispatch_dense(g.f, [&](auto fc) {
     constexpr int F = decltype(fc)::value;
     if (int rc = set_max_lds_cached(gt_dense_bwd_stats_kernel<F>)) return rc;
-    gt_dense_bwd_stats_kernel<F><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.fit(), Q, K, V, stat_max, stat_sum, grad_out, dQ, dK,
+    gt_dense_bwd_stats_kernel<F><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.desc(), Q, K, V, stat_max, stat_sum, grad_out, dQ, dK,
                                                                         dV, heads2, g.h == 1 ? bwd_reverse_keep(p.num_dense) : -1);  // (several heads: measured, no gain)
     return launch_status();
   });

@@ -27,7 +27,7 @@ namespace dfgnn {
 
 // grid (dense ranges, heads)
 template <int F>
-__global__ __launch_bounds__(kDenseThreads) void gt_dense_fwd_stats_w_kernel(Csr g, const int *__restrict__ fit,
+__global__ __launch_bounds__(kDenseThreads) void gt_dense_fwd_stats_w_kernel(Csr g, const PlanDesc *__restrict__ desc,
                                                                              const float *__restrict__ Q,
                                                                              const float *__restrict__ K,
                                                                              const float *__restrict__ V,
@@ -35,8 +35,8 @@ __global__ __launch_bounds__(kDenseThreads) void gt_dense_fwd_stats_w_kernel(Csr
                                                                              float *__restrict__ stat_max,
                                                                              float *__restrict__ stat_sum, int lds_bytes) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int n0 = fit[2 * blockIdx.x], n1 = fit[2 * blockIdx.x + 1] & kPlanRangeMask;
-  const int n = n1 - n0, head = blockIdx.y;
+  const PlanDesc d = desc[blockIdx.x];  // (one scalar load: dfgnn_launch.hpp)
+  const int n0 = d.n0, n = (d.n1f & kPlanRangeMask) - n0, head = blockIdx.y;
   if (n <= kDenseChunkRows)
     dense_fwd_body<F, false, 1, kDenseChunkRows, 1, false, false, true, true>(lds, lds_bytes, g, n0, n, 0, 0, head, 1, Q, K, V,
                                                                               nullptr, out, 0.f, stat_max, stat_sum);
@@ -50,15 +50,15 @@ __global__ __launch_bounds__(kDenseThreads) void gt_dense_fwd_stats_w_kernel(Csr
 
 template <int F>
 __global__ __launch_bounds__(kDenseThreads) void gt_dense_bwd_stats_w_kernel(
-    Csr g, const int *__restrict__ fit, const float *__restrict__ Q, const float *__restrict__ K,
+    Csr g, const PlanDesc *__restrict__ desc, const float *__restrict__ Q, const float *__restrict__ K,
     const float *__restrict__ V, const float *__restrict__ stat_max, const float *__restrict__ stat_sum,
     const float *__restrict__ dO, float *__restrict__ dQ, float *__restrict__ dK, float *__restrict__ dV, int keep) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   int range = blockIdx.x;
   const int head = blockIdx.y;
   if (keep >= 0 && range >= keep) range = (int)gridDim.x - 1 - (range - keep);  // (launch_gt_dense_bwd, gt_dense.hip)
-  const int n0 = fit[2 * range], n1 = fit[2 * range + 1] & kPlanRangeMask;
-  const int n = n1 - n0;
+  const PlanDesc d = desc[range];  // (one scalar load: dfgnn_launch.hpp)
+  const int n0 = d.n0, n = (d.n1f & kPlanRangeMask) - n0;
   GatBwdArgs st{};
   st.edge_max = stat_max;
   st.edge_sum = stat_sum;
@@ -83,15 +83,16 @@ __global__ __launch_bounds__(kDenseThreads) void gt_dense_bwd_stats_w_kernel(
 #define DFGNN_RANKED_WRITE true  // (diagnostic builds: false = the same kernel without the attention values, for phase stamps)
 #endif
 template <int F>
-__global__ __launch_bounds__(kDenseThreads) void gt_dense_fwd_ranked_kernel(Csr g, const int *__restrict__ fit,
+__global__ __launch_bounds__(kDenseThreads) void gt_dense_fwd_ranked_kernel(Csr g, const PlanDesc *__restrict__ desc,
                                                                             const float *__restrict__ Q,
                                                                             const float *__restrict__ K,
                                                                             const float *__restrict__ V,
                                                                             float *__restrict__ attn_ranked,
                                                                             float *__restrict__ out, int lds_bytes) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int n0 = fit[2 * blockIdx.x], n1 = fit[2 * blockIdx.x + 1] & kPlanRangeMask;
-  const int n = n1 - n0, e0 = g.row_ptr[n0], ne = g.row_ptr[n1] - e0;
+  DFGNN_STAMP_ENTRY
+  const PlanDesc d = desc[blockIdx.x];  // (one scalar load: dfgnn_launch.hpp)
+  const int n0 = d.n0, n = (d.n1f & kPlanRangeMask) - n0, e0 = d.e0, ne = d.ne;
   // (the three classes as non-inlined functions -- each then keeps its own register allocation, 170 / 192 / 236 VGPRs and no
   // spills instead of 256 and 19 for the merged body -- ran 84 -> 102 us: behind a call the LDS pointers are generic and
   // every ds_ access becomes a flat one)
@@ -103,20 +104,21 @@ __global__ __launch_bounds__(kDenseThreads) void gt_dense_fwd_ranked_kernel(Csr 
   else
     dense_fwd_body<F, DFGNN_RANKED_WRITE, 2, kDenseChunkRows, 2, false, false, true>(lds, lds_bytes, g, n0, n, e0, ne, 0, 1, Q, K, V, attn_ranked, out);
 #endif
+  DFGNN_STAMP_EXIT
 }
 
 // ... several heads: every head of the range in this workgroup, like gt_dense_fwd_kernel (a kernel of its own: its widest
 // body must not set the register budget of the one-head kernel above)
 template <int F>
-__global__ __launch_bounds__(kDenseThreads) void gt_dense_fwd_ranked_heads_kernel(Csr g, const int *__restrict__ fit,
+__global__ __launch_bounds__(kDenseThreads) void gt_dense_fwd_ranked_heads_kernel(Csr g, const PlanDesc *__restrict__ desc,
                                                                                   const float *__restrict__ Q,
                                                                                   const float *__restrict__ K,
                                                                                   const float *__restrict__ V,
                                                                                   float *__restrict__ attn_ranked,
                                                                                   float *__restrict__ out, int lds_bytes) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int n0 = fit[2 * blockIdx.x], n1 = fit[2 * blockIdx.x + 1] & kPlanRangeMask;
-  const int n = n1 - n0, e0 = g.row_ptr[n0], ne = g.row_ptr[n1] - e0;
+  const PlanDesc d = desc[blockIdx.x];  // (one scalar load: dfgnn_launch.hpp)
+  const int n0 = d.n0, n = (d.n1f & kPlanRangeMask) - n0, e0 = d.e0, ne = d.ne;
   if constexpr (F == 16 || F == 32 || F == 64) {
     if (dense_heads_ok(F, g.h) && n <= kDenseWideRows) {  // heads in groups of 64 columns (dfgnn_dense_heads.hpp)
       if (n <= kDenseChunkRows)
@@ -141,7 +143,7 @@ int launch_gt_dense_fwd_stats_w(const Csr &g, const Plan &p, const float *Q, con
   return dispatch_dense(g.f, [&](auto fc) {
     constexpr int F = decltype(fc)::value;
     if (int rc = set_max_lds_cached(gt_dense_fwd_stats_w_kernel<F>)) return rc;
-    gt_dense_fwd_stats_w_kernel<F><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.fit(), Q, K, V, out, stat_max, stat_sum, kLdsBytes);
+    gt_dense_fwd_stats_w_kernel<F><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.desc(), Q, K, V, out, stat_max, stat_sum, kLdsBytes);
     return launch_status();
   });
 }
@@ -153,7 +155,7 @@ int launch_gt_dense_bwd_stats_w(const Csr &g, const Plan &p, const float *Q, con
   return dispatch_dense(g.f, [&](auto fc) {
     constexpr int F = decltype(fc)::value;
     if (int rc = set_max_lds_cached(gt_dense_bwd_stats_w_kernel<F>)) return rc;
-    gt_dense_bwd_stats_w_kernel<F><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.fit(), Q, K, V, stat_max, stat_sum, grad_out, dQ,
+    gt_dense_bwd_stats_w_kernel<F><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.desc(), Q, K, V, stat_max, stat_sum, grad_out, dQ,
                                                                           dK, dV, g.h == 1 ? bwd_reverse_keep(p.num_dense) : -1);  // (several heads: measured, no gain)
     return launch_status();
   });
@@ -172,17 +174,17 @@ int launch_gt_dense_fwd_ranked(const Csr &g_in, const Plan &p, const float *Q, c
     if constexpr (F == 64 || F == 128) {
       if (lean) {
         if (int rc = set_max_lds_cached(gt_dense_fwd_lean_kernel<F, true, true>)) return rc;
-        gt_dense_fwd_lean_kernel<F, true, true><<<grid, kLeanThreads, kLeanLdsBytes, s>>>(g, p.fit(), Q, K, V, attn_ranked, out, nullptr,
+        gt_dense_fwd_lean_kernel<F, true, true><<<grid, kLeanThreads, kLeanLdsBytes, s>>>(g, p.desc(), Q, K, V, attn_ranked, out, nullptr,
                                                                                          nullptr);
         return launch_status();
       }
     }
     if (g.h == 1) {
       if (int rc = set_max_lds_cached(gt_dense_fwd_ranked_kernel<F>)) return rc;
-      gt_dense_fwd_ranked_kernel<F><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.fit(), Q, K, V, attn_ranked, out, kLdsBytes);
+      gt_dense_fwd_ranked_kernel<F><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.desc(), Q, K, V, attn_ranked, out, kLdsBytes);
     } else {
       if (int rc = set_max_lds_cached(gt_dense_fwd_ranked_heads_kernel<F>)) return rc;
-      gt_dense_fwd_ranked_heads_kernel<F><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.fit(), Q, K, V, attn_ranked, out, kLdsBytes);
+      gt_dense_fwd_ranked_heads_kernel<F><<<grid, kDenseThreads, kLdsBytes, s>>>(g, p.desc(), Q, K, V, attn_ranked, out, kLdsBytes);
     }
     return launch_status();
   });

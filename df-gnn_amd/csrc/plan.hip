@@ -17,7 +17,12 @@
 //   [12 .. 12+2m)       fit ranges   (n0, n1 | kPlanEdgeGlobal | kPlanDense) pairs: dense ones first, each group
 //                                    largest first
 //   [12+2m .. 12+4m)    spill chunks (r0, r1) pairs, r1 - r0 <= kHyperRows
-//   [12+4m .. )         scratch: pairs[m] (cover, bad) as int2, bounds[m+1], count, rocPRIM temporary storage
+//   [12+4m .. )         scratch: pairs[m] (cover, bad) as int2, bounds[m+1], count, rocPRIM temporary storage -- dead once
+//                       plan_cut_kernel is through; plan_coords_kernel then writes over its front:
+//   [12+4m .. )         desc: one 16-byte PlanDesc per dense range k < num_dense, in the order of the fit list:
+//                       (n0, n1 | flags, row_ptr[n0], row_ptr[n1] - row_ptr[n0]) -- everything a matrix-core kernel must know
+//                       before its first vector load, in one scalar load (dfgnn_launch.hpp: plan_desc_off, PlanDesc, and
+//                       why num_dense of them fit in front of the coordinates)
 //   [.. behind coords)  mask[8 m], maskT[8 m]: edge bitmaps of the dense ranges, 8 words per node (plan_coords_kernel;
 //                       offset: dfgnn_launch.hpp:plan_mask_off) -- for the kernels that need the edge SET only
 //   [hdr[11] .. )       coords: uint16[nnz], for every edge e of a dense range (i - n0) << 8 | (j - n0) -- its row and
@@ -386,7 +391,8 @@ __global__ __launch_bounds__(256) void plan_coords_kernel(const int *__restrict_
                                                           const int *__restrict__ col_ind, const int *plan,
                                                           unsigned short *__restrict__ coords,
                                                           unsigned *__restrict__ mask, unsigned *__restrict__ maskT,
-                                                          unsigned short *__restrict__ ranked) {
+                                                          unsigned short *__restrict__ ranked,
+                                                          PlanDesc *__restrict__ desc, int desc_cap) {
   __shared__ unsigned s_mask[2][256 * kPlanMaskWords];
   const int ndense = plan[9];
   const int *fit = plan + kPlanHeader;
@@ -394,6 +400,7 @@ __global__ __launch_bounds__(256) void plan_coords_kernel(const int *__restrict_
   for (int k = blockIdx.x; k < ndense; k += gridDim.x) {
     const int n0 = fit[2 * k], n1 = fit[2 * k + 1] & kPlanRangeMask;
     const int words = (n1 - n0) * kPlanMaskWords;
+    if (threadIdx.x == 0 && k < desc_cap) desc[k] = PlanDesc{n0, fit[2 * k + 1], row_ptr[n0], row_ptr[n1] - row_ptr[n0]};
     for (int t = threadIdx.x; t < words; t += 256) s_mask[0][t] = s_mask[1][t] = 0u;
     __syncthreads();
     for (int i = n0 + grp; i < n1; i += 256 / kExtentLanes) {
@@ -463,6 +470,11 @@ size_t dfgnn_plan_ints(int m, int nnz) {
   if (m < 0 || nnz < 0) return 0;
   return plan_mask_off(plan_coords_off(m), nnz) + 2 * (size_t)kPlanMaskWords * (size_t)m + ((size_t)nnz + 1) / 2 + 4;
 }
+int dfgnn_plan_desc_off(int m, int nnz) {
+  if (m < 0 || nnz < 0) return kErrBadArg;
+  const size_t off = plan_desc_off(m);  // (behind the spill list, whatever nnz: the buffer keeps its size)
+  return off > 0x7fffffffu ? kErrUnsupported : (int)off;
+}
 
 int dfgnn_plan_build(int m, int nnz, int f, const int *row_ptr, const int *col_ind, int *plan, int *meta_host,
                      dfgnn_stream_t stream) {
@@ -505,11 +517,16 @@ int dfgnn_plan_build(int m, int nnz, int f, const int *row_ptr, const int *col_i
     plan_coords_kernel<<<(unsigned)min(m, 2048), 256, 0, s>>>(row_ptr, col_ind, plan,
                                                              reinterpret_cast<unsigned short *>(plan + coords_off), mask,
                                                              mask + (size_t)kPlanMaskWords * m,
-                                                             reinterpret_cast<unsigned short *>(mask + 2 * (size_t)kPlanMaskWords * m));
+                                                             reinterpret_cast<unsigned short *>(mask + 2 * (size_t)kPlanMaskWords * m),
+                                                             reinterpret_cast<PlanDesc *>(plan + plan_desc_off(m)),
+                                                             (int)min(plan_desc_capacity(m, coords_off), (size_t)0x7fffffff));
     if (int rc = launch_status()) return rc;
   }
   if (hipError_t rc = hipMemcpyAsync(meta_host, plan, kPlanHeader * sizeof(int), hipMemcpyDeviceToHost, s)) return (int)rc;
-  return (int)hipStreamSynchronize(s);
+  if (hipError_t rc = hipStreamSynchronize(s)) return (int)rc;
+  // (cannot happen by the merge rule -- dfgnn_launch.hpp: plan_desc_capacity -- and must not pass silently if it ever does)
+  if ((size_t)meta_host[9] > plan_desc_capacity(m, coords_off)) return kErrUnsupported;
+  return 0;
 }
 
 // Dense edge values for the WEIGHTED statistics pair (dfgnn.h): weights[256 m] floats, zero off the edges.

@@ -1030,6 +1030,8 @@ PYBIND11_MODULE(_dfgnn_ext, m) {
   // the library with itself): dfgnn_native.ext() takes the extension only if both equal the library's
   m.def("abi_version", [] { return (int)DFGNN_ABI_VERSION; });
   m.def("build_id", [] { return std::string(DFGNN_SRC_HASH); });
+  m.def("plan_desc_off", [](int64_t m_, int64_t nnz) { return (int64_t)dfgnn_plan_desc_off((int)m_, (int)nnz); },
+        "int32 offset of the dense ranges' descriptors in a plan buffer");
   m.def("gt_hyper_fwd", &gt_hyper_fwd, "fused GT conv 'hyper' forward (inference / training)");
   m.def("gt_bwd", &gt_bwd, "fused GT conv backward");
   m.def("gt_hyper_fwd_stats", &gt_hyper_fwd_stats, "fused GT conv 'hyper' training forward, row statistics instead of attn_edge");

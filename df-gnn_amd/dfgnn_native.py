@@ -19,6 +19,7 @@ _vp, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 # symbol -> argtypes; mirrors include/dfgnn.h one to one (checked by tests/test_capi_symbols.py)
 SIGNATURES = {
     "dfgnn_plan_build": [_i, _i, _i] + [_vp] * 5,
+    "dfgnn_plan_desc_off": [_i, _i],  # (answers an int32 offset, or a negative status)
     "dfgnn_preprocess_hyper": [_i, _i, _vp, _vp, _i] + [_vp] * 8 + [ctypes.c_size_t, _vp],
     "dfgnn_preprocess_ws_bytes_rect": [_i, _i, _i, _vp],
     "dfgnn_preprocess_hyper_rect": [_i, _i, _i, _vp, _vp, _i] + [_vp] * 8 + [ctypes.c_size_t, _vp],

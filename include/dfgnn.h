@@ -62,13 +62,17 @@ const char *dfgnn_build_id(void);
  * ~3 x 2^-24 relative error per product, that of an fp32 FMA chain).
  *   plan       device buffer of dfgnn_plan_ints(m, nnz) int32 (lists of ranges, build scratch and, for the
  *              matrix-core kernels, 2 bytes per edge -- its row and column within its dense range -- and two edge
- *              bitmaps of 32 bytes per node: the out- and the in-neighbours of a node within its dense range)
+ *              bitmaps of 32 bytes per node: the out- and the in-neighbours of a node within its dense range; over
+ *              the build scratch, from int32 offset dfgnn_plan_desc_off(m, nnz), one 16-byte descriptor per dense range in the order
+ *              of the range list: n0, n1 | flags, row_ptr[n0], row_ptr[n1] - row_ptr[n0] -- what a matrix-core kernel
+ *              reads of its range before anything else)
  *   meta_host  host buffer of 12 int32 filled on return: num_fit, num_spill, max_fit_nodes,
  *              max_fit_edges, m, nnz, f, lds_budget, num_edge_global, num_dense, num_dense_wide (dense ranges of
  *              more than 128 nodes), coords_offset (int32 offset of the per-edge coordinates in `plan`)
  * dfgnn_plan_build synchronises `stream` (it copies the 12 header words back); nothing else in this
  * library does. */
 size_t dfgnn_plan_ints(int m, int nnz);
+int dfgnn_plan_desc_off(int m, int nnz);
 /* 1 if the entry points below would use a plan with this host header for (m, nnz, h, f), else 0 (they then take the
  * general kernels, same results): the header must have been built for the same m, nnz, f; graphs with fewer than 8 edges
  * per row on average and feature matrices of 4 GiB or more (m h f 4 >= 2^32: the plan kernels address a feature row
