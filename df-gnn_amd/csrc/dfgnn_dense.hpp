@@ -28,6 +28,7 @@
 //   * the O^T accumulator holds 4 consecutive features of one output row per lane -> float4 stores.
 #pragma once
 #include "dfgnn_block.hpp"
+#include "dfgnn_lds_layout.hpp"
 
 namespace dfgnn {
 
@@ -246,9 +247,13 @@ __device__ __forceinline__ float wg_max_read(const float *slot) {
 // and the wait for the data to the previous barrier, measured 2 % slower.)
 // fr: real feature count (<= F, a multiple of 8): the image columns at or past it are stored as zeros.
 // scale: the image's power-of-two scale (pow2_scale of its largest magnitude).
+// kswap (a literal at every call site): the K image of a dQ product, whose rows are stored where image_row() puts them
+// (dfgnn_lds_layout.hpp) and read through image_k_off(); ROWS must then be a multiple of 16.
 template <int F, int ROWS, int USED = ROWS>
-__device__ __forceinline__ void dense_stage_store(DenseStageRegs<F, ROWS> &r, h16 *hi, h16 *lo, float scale, int fr = F) {
+__device__ __forceinline__ void dense_stage_store(DenseStageRegs<F, ROWS> &r, h16 *hi, h16 *lo, float scale, int fr = F,
+                                                  bool kswap = false) {
   constexpr int C8 = F / 8, RS = DenseCfg<F>::RS;
+  static_assert(RS == image_rs(F), "the image layout of dfgnn_lds_layout.hpp");
   const int tid = opaque_tid();
 #pragma unroll
   for (int k = 0; k < DenseStageRegs<F, USED>::PER; ++k) {
@@ -259,10 +264,11 @@ __device__ __forceinline__ void dense_stage_store(DenseStageRegs<F, ROWS> &r, h1
       const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
       hx8 h, l;
       split_hx8(valid ? r.a[k] : z, valid ? r.b[k] : z, scale, h, l);
-      DFGNN_LDS_AT(hi + row * RS + 8 * c8, 16u);
-      DFGNN_LDS_AT(lo + row * RS + 8 * c8, 16u);
-      *reinterpret_cast<hx8 *>(hi + row * RS + 8 * c8) = h;
-      *reinterpret_cast<hx8 *>(lo + row * RS + 8 * c8) = l;
+      const int irow = image_row(row, kswap);  // (image_at() of either plane, written so that the other images compile as before)
+      DFGNN_LDS_AT(hi + irow * RS + 8 * c8, 16u);
+      DFGNN_LDS_AT(lo + irow * RS + 8 * c8, 16u);
+      *reinterpret_cast<hx8 *>(hi + irow * RS + 8 * c8) = h;
+      *reinterpret_cast<hx8 *>(lo + irow * RS + 8 * c8) = l;
     }
   }
   asm volatile("" ::: "memory");
@@ -324,6 +330,51 @@ __device__ __forceinline__ hx8 dense_tr_pair(const h16 *p, int second_offset) {
   const hx4 a = __builtin_bit_cast(hx4, __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_hx4_ptr)(p)));
   const hx4 b = __builtin_bit_cast(hx4, __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_hx4_ptr)(p + second_offset)));
   return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// ---- the backward's P / dS tile (layout and bank rules: dfgnn_lds_layout.hpp) ------------------------------------------
+// Element offsets of this lane's piece of the hi half for each way the tile is accessed; the lo half lies TS further on.
+// They are taken at (row & 15, column & 15) -- the layout is periodic in both -- so that everything else is a constant.
+// A strip's own values (the accumulator layout: row 16 strip + mi, columns 16 u + 4 mq ..): + 16 u for tile u
+template <int TS>
+__device__ __forceinline__ int tile_strip_off(int strip, const LaneIds &L) {
+  return tile_at(TS, L.mi, 4 * L.mq, 0) + strip * 16 * 2 * TS;
+}
+// Transposed operand reads of a column product (rows 32 ib + 4 mq + tq and + 16, columns 16 cs + 4 tp ..): + 32 ib 2 TS
+template <int TS>
+__device__ __forceinline__ int tile_tr_off(int cs, const LaneIds &L) {
+  return tile_at(TS, 4 * L.mq + L.tq, 4 * L.tp, 0) + 16 * cs;
+}
+// Natural-order operand reads of a row product (row 16 strip + mi, columns 32 jb + 8 mq .. + 7): the two 4-column
+// chunks are addressed one by one, `part` = 0, 1; + 32 jb for k-block jb
+template <int TS>
+__device__ __forceinline__ int tile_row_off(int strip, int part, const LaneIds &L) {
+  return tile_at(TS, L.mi, 8 * L.mq + 4 * part, 0) + strip * 16 * 2 * TS;
+}
+__device__ __forceinline__ hx8 tile_row8(const h16 *a, const h16 *b) {
+  DFGNN_LDS_AT(a, 8u);
+  DFGNN_LDS_AT(b, 8u);
+  return __builtin_shufflevector(*reinterpret_cast<const hx4 *>(a), *reinterpret_cast<const hx4 *>(b), 0, 1, 2, 3, 4, 5, 6, 7);
+}
+// P of one edge -> its hi | lo halves (scale 2^14)
+template <int TS>
+__device__ __forceinline__ void tile_put_p(h16 *Tb, int i, int j, float p) {
+  const int at = tile_at(TS, i, j, 0);
+  const h16 hh = (h16)(p * kUnitScale);
+  DFGNN_LDS_AT(Tb + at + TS, 2u);
+  Tb[at] = hh;
+  Tb[at + TS] = (h16)fmaf(p, kUnitScale, -(float)hh);
+}
+// The K image of the dQ product (stored with kswap, see dense_stage_store): this lane's transposed reads of k-rows
+// 32 jb + 8 mq + tq (at `first`) and + 4 (at first + second), features 4 tp ..: + 32 jb RS, + 16 ft
+struct KImageOff {
+  int first, second;
+};
+template <int RS>
+__device__ __forceinline__ KImageOff image_k_off(const LaneIds &L) {
+  const int r = 8 * (L.mq & 3) + L.tq;
+  const int a = image_at(RS, 0, r, 4 * L.tp, 0, true);
+  return KImageOff{a, image_at(RS, 0, r + 4, 4 * L.tp, 0, true) - a};
 }
 
 // 8 fp32 values x scale -> fp16 hi / lo operand fragments

@@ -18,7 +18,7 @@ struct DenseBwdGeom {
   static constexpr int RB = (CW == kDenseWideRows) ? 80 : 128;  // rows per row block
   static constexpr int RBP = (RB + 31) & ~31;                  // ... padded to the 32-deep k-blocks of the products
   static constexpr int U = CW / 16;                            // 16-column tiles per column block
-  static constexpr int TS = CW + 8;                            // floats per tile row == 2 x TS fp16 (hi | lo)
+  static constexpr int TS = tile_ts(CW);                       // floats per tile row == 2 x TS fp16 (hi | lo, dfgnn_lds_layout.hpp)
 };
 
 // GAT training backward (GAT = true; Q = attn_row [m, h], K = attn_col [m, h], V = X, dV = grad_feat; attn_edge, dQ, dK
@@ -52,7 +52,7 @@ __device__ __forceinline__ void dense_bwd_body(float *lds, const Csr &g, int n0,
   using D = DenseCfg<F>;
   using G = DenseBwdGeom<CW, NBLK>;
   constexpr int RS = D::RS, KT = D::KT, FT = D::FT, RB = G::RB, RBP = G::RBP, U = G::U, TS = G::TS;
-  constexpr int TB = 2 * TS;  // fp16 elements per interleaved tile row: hi at +0, lo at +TS
+  constexpr int TB = 2 * TS;  // fp16 elements per tile row: hi at +0, lo at +TS, 4-column chunks swizzled (dfgnn_lds_layout.hpp)
   // edges fetched ahead per thread (GAT: each edge also carries its dropout random, so fewer fit the registers)
   constexpr int PRE = GAT ? 10 : kDensePre;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);  // = this wave's strip of a row block
@@ -106,9 +106,9 @@ __device__ __forceinline__ void dense_bwd_body(float *lds, const Csr &g, int n0,
     if (NBLK > 1) dense_stage_load<F, CW>(st, next_src, hf, next_row0, next_end, fr);
     wg_max_post(smax, dense_stage_absmax<F, CW>(st));
   };
-  auto image_store = [&]() {
+  auto image_store = [&](bool kswap = false) {  // kswap (a literal): the K image of the dQ product
     isc = pow2_scale(wg_max_read(smax));
-    dense_stage_store<F, CW>(st, ihi, ilo, isc.s, fr);
+    dense_stage_store<F, CW>(st, ihi, ilo, isc.s, fr, kswap);
   };
   // Edges of a row block (CSR order, contiguous) are fetched several per thread at a time -- loads first, then the
   // scatter into the fp32 tile -- so that a batch costs one memory round trip; the first batch of a range is
@@ -140,14 +140,10 @@ __device__ __forceinline__ void dense_bwd_body(float *lds, const Csr &g, int n0,
   // product wants -- and the strips read their rows back from it (hi + lo = P to 2^-24); no fp32 copy, no conversion
   // pass, one barrier less.  (Two column blocks / GAT: P is scattered as fp32 and converted in place by its strips.)
   constexpr bool kDirectP = !GAT && NBLK == 1 && !RECOMP;
-  auto put_p = [&](int i, int j, float p) {
-    const h16 hh = (h16)(p * kUnitScale);
-    Tb[i * TB + j] = hh;
-    Tb[i * TB + TS + j] = (h16)fmaf(p, kUnitScale, -(float)hh);
-  };
+  auto put_p = [&](int i, int j, float p) { tile_put_p<TS>(Tb, i, j, p); };
   auto tile_clear = [&]() {
     const int tid = opaque_tid();
-    for (int k = tid; k < RBP * TS / 4; k += kDenseThreads)
+    for (int k = tid; k < tile_elems(TS, RBP) / 8; k += kDenseThreads)
       reinterpret_cast<float4 *>(T)[k] = make_float4(0.f, 0.f, 0.f, 0.f);
     lds_barrier();
   };
@@ -199,7 +195,7 @@ __device__ __forceinline__ void dense_bwd_body(float *lds, const Csr &g, int n0,
   // hi | lo halves
   auto strip_to_tile = [&](const f32x4 (&X)[U], float tscale) {
     const LaneIds L = lane_ids();
-    h16 *trow = Tb + (wave * 16 + L.mi) * TB + 4 * L.mq;
+    h16 *trow = Tb + tile_strip_off<TS>(wave, L);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       hx4 h4, l4;
@@ -224,7 +220,7 @@ __device__ __forceinline__ void dense_bwd_body(float *lds, const Csr &g, int n0,
 #pragma unroll
     for (int ib = 0; ib < RBP / 32; ++ib) {
       if (32 * ib < ni) {
-        const int yoff = (32 * ib + 4 * L.mq + L.tq) * TB + 16 * cs + 4 * L.tp;
+        const int yoff = tile_tr_off<TS>(cs, L) + 32 * ib * TB;
         const hx8 yh = dense_tr_pair(Tb + yoff, 16 * TB);
         const hx8 yl = dense_tr_pair(Tb + yoff + TS, 16 * TB);
         dense_kblock_mma<F, (NBLK == 1 ? 8 : 4)>(acc, ihi, ilo, (32 * ib + 4 * L.mq + L.tq) * RS + 4 * L.tp, 16 * RS, yh, yl);
@@ -247,7 +243,7 @@ __device__ __forceinline__ void dense_bwd_body(float *lds, const Csr &g, int n0,
 #pragma unroll
     for (int ib = 0; ib < RBP / 32; ++ib) {
       if (32 * ib < ni) {
-        const int yoff = (32 * ib + 4 * L.mq + L.tq) * TB + 16 * cs + 4 * L.tp;
+        const int yoff = tile_tr_off<TS>(cs, L) + 32 * ib * TB;
         const hx8 yh = dense_tr_pair(Tb + yoff, 16 * TB);
         const hx8 yl = dense_tr_pair(Tb + yoff + TS, 16 * TB);
         const int xoff = (32 * ib + 4 * L.mq + L.tq) * RS + 4 * L.tp + 16 * ft;
@@ -274,7 +270,7 @@ __device__ __forceinline__ void dense_bwd_body(float *lds, const Csr &g, int n0,
 #pragma unroll
     for (int ib = 0; ib < RBP / 32; ++ib) {
       if (32 * ib < ni) {
-        const int yoff = (32 * ib + 4 * L.mq + L.tq) * TB + 16 * cs0 + 4 * L.tp;
+        const int yoff = tile_tr_off<TS>(cs0, L) + 32 * ib * TB;
         const hx8 yh0 = dense_tr_pair(Tb + yoff, 16 * TB), yl0 = dense_tr_pair(Tb + yoff + TS, 16 * TB);
         const hx8 yh1 = dense_tr_pair(Tb + yoff + 16, 16 * TB), yl1 = dense_tr_pair(Tb + yoff + 16 + TS, 16 * TB);
         dense_kblock_mma2<NFT>(acc0, acc1, ihi, ilo, (32 * ib + 4 * L.mq + L.tq) * RS + 4 * L.tp + 16 * ft0, 16 * RS, yh0,
@@ -446,7 +442,7 @@ __device__ __forceinline__ void dense_bwd_body(float *lds, const Csr &g, int n0,
         for (int u = 0; u < U; ++u) {
           if (16 * u < nj) {
             if constexpr (kDirectP) {
-              const h16 *trow = Tb + (wave * 16 + L.mi) * TB + 16 * u + 4 * L.mq;
+              const h16 *trow = Tb + tile_strip_off<TS>(wave, L) + 16 * u;
               const hx4 h4 = *reinterpret_cast<const hx4 *>(trow), l4 = *reinterpret_cast<const hx4 *>(trow + TS);
 #pragma unroll
               for (int r = 0; r < 4; ++r) Pr[jc][u][r] = ((float)h4[r] + (float)l4[r]) * kUnitScaleInv;
@@ -633,7 +629,7 @@ __device__ __forceinline__ void dense_bwd_body(float *lds, const Csr &g, int n0,
     for (int jc = 0; jc < NBLK; ++jc) {
       const int j0 = jc * CW, nj = min(n - j0, CW);
       if (row_wave) strip_to_tile(dS[jc], ts.s);
-      image_store();                        // K rows j0..
+      image_store(true);                    // K rows j0.., in the order the dQ product reads them without bank conflicts
       if (jc > 0) {                         // accumulated under the previous K block's scale
         const float ratio = kinv * isc.s;
 #pragma unroll
@@ -653,15 +649,16 @@ __device__ __forceinline__ void dense_bwd_body(float *lds, const Csr &g, int n0,
           f32x4 q0[NFT], q1[NFT];
 #pragma unroll
           for (int k = 0; k < NFT; ++k) q0[k] = q1[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-          const h16 *srow = Tb + (cs0 * 16 + L.mi) * TB + 8 * L.mq;
+          // natural k order (see below), 8 columns as two chunks: sa = columns 8 mq .. + 3, sb = columns 8 mq + 4 .. + 7
+          const h16 *sa = Tb + tile_row_off<TS>(cs0, 0, L), *sb = Tb + tile_row_off<TS>(cs0, 1, L);
+          const KImageOff ko = image_k_off<RS>(L);
 #pragma unroll
           for (int jb = 0; jb < CW / 32; ++jb) {
             if (32 * jb < nj) {
-              const hx8 sh0 = *reinterpret_cast<const hx8 *>(srow + 32 * jb), sl0 = *reinterpret_cast<const hx8 *>(srow + TS + 32 * jb);
-              const hx8 sh1 = *reinterpret_cast<const hx8 *>(srow + 16 * TB + 32 * jb),
-                        sl1 = *reinterpret_cast<const hx8 *>(srow + 16 * TB + TS + 32 * jb);
-              dense_kblock_mma2<NFT>(q0, q1, ihi, ilo, (32 * jb + 8 * L.mq + L.tq) * RS + 4 * L.tp + 16 * ft0, 4 * RS, sh0, sl0,
-                                     sh1, sl1);
+              const hx8 sh0 = tile_row8(sa + 32 * jb, sb + 32 * jb), sl0 = tile_row8(sa + TS + 32 * jb, sb + TS + 32 * jb);
+              const hx8 sh1 = tile_row8(sa + 16 * TB + 32 * jb, sb + 16 * TB + 32 * jb),
+                        sl1 = tile_row8(sa + 16 * TB + TS + 32 * jb, sb + 16 * TB + TS + 32 * jb);
+              dense_kblock_mma2<NFT>(q0, q1, ihi, ilo, ko.first + 32 * jb * RS + 16 * ft0, ko.second, sh0, sl0, sh1, sl1);
             }
           }
           dense_store_rows<NFT>(q0, kinv * ts.inv, dQb + 16 * ft0, (unsigned)hf, i0 + cs0 * 16 + L.mi, i0 + ni, L);
@@ -669,14 +666,15 @@ __device__ __forceinline__ void dense_bwd_body(float *lds, const Csr &g, int n0,
         }
       } else if (row_wave) {
         const LaneIds L = lane_ids();
-        const h16 *srow = Tb + (wave * 16 + L.mi) * TB + 8 * L.mq;
+        const h16 *sa = Tb + tile_row_off<TS>(wave, 0, L), *sb = Tb + tile_row_off<TS>(wave, 1, L);
+        const KImageOff ko = image_k_off<RS>(L);
 #pragma unroll
         for (int jb = 0; jb < CW / 32; ++jb) {
           if (32 * jb < nj) {
             // natural k order: element t of lane (mi, mq) is column 32 jb + 8 mq + t of dS / that row of K
-            const hx8 sh = *reinterpret_cast<const hx8 *>(srow + 32 * jb);
-            const hx8 sl = *reinterpret_cast<const hx8 *>(srow + TS + 32 * jb);
-            dense_kblock_mma<F, (NBLK == 1 ? 8 : 4)>(qacc, ihi, ilo, (32 * jb + 8 * L.mq + L.tq) * RS + 4 * L.tp, 4 * RS, sh, sl);
+            const hx8 sh = tile_row8(sa + 32 * jb, sb + 32 * jb);
+            const hx8 sl = tile_row8(sa + TS + 32 * jb, sb + TS + 32 * jb);
+            dense_kblock_mma<F, (NBLK == 1 ? 8 : 4)>(qacc, ihi, ilo, ko.first + 32 * jb * RS, ko.second, sh, sl);
           }
         }
         if (jc + 1 == NBLK) {  // dQ rows of this row block are complete: store them now, under the dK product

@@ -55,7 +55,7 @@ __device__ __forceinline__ void dense_bwd_wide_body(float *lds, const Csr &g, in
   constexpr int NH = F / FW;                // feature halves
   using D = DenseCfg<FW>;
   constexpr int RS = D::RS, KT = D::KT, FT = D::FT;
-  constexpr int U = NP / 16, TS = NP + 8, TB = 2 * TS, NS = (U + kDenseWaves - 1) / kDenseWaves, PRE = kDensePre;
+  constexpr int U = NP / 16, TS = tile_ts(NP), TB = 2 * TS, NS = (U + kDenseWaves - 1) / kDenseWaves, PRE = kDensePre;
   constexpr int QB = RECOMP ? NH : 0;  // images ahead of dO.0 (RECOMP: K.0 [K.1], for S)
   constexpr int NQ = 4 * NH + QB;      // images in all: dO.0 V.0 [dO.1 V.1] K.0 Q.0 [K.1 Q.1]
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
@@ -101,9 +101,10 @@ __device__ __forceinline__ void dense_bwd_wide_body(float *lds, const Csr &g, in
     if (q < NQ) dense_stage_load<FW, NP>(st[q % R], image_src(q), hf, 0, n, fr, once);
   };
   auto image_post = [&](int q) { wg_max_post(smax, dense_stage_absmax<FW, NP>(st[q % R])); };
-  auto image_store = [&](int q) {  // ... and the register set is refilled with the image R phases on
+  // kswap (a literal): a K image of the dQ product
+  auto image_store = [&](int q, bool kswap = false) {  // ... and the register set is refilled with the image R phases on
     isc = pow2_scale(wg_max_read(smax));
-    dense_stage_store<FW, NP>(st[q % R], ihi, ilo, isc.s, fr);
+    dense_stage_store<FW, NP>(st[q % R], ihi, ilo, isc.s, fr, kswap);
     if (q == 1) { DFGNN_WSTAMP(13) }
     image_fetch(q + R);
   };
@@ -191,7 +192,7 @@ __device__ __forceinline__ void dense_bwd_wide_body(float *lds, const Csr &g, in
       const int strip = wave + kDenseWaves * s;
       if (strip < U) {  // every row of the tile is written: zeros past the range
         const LaneIds L = lane_ids();
-        h16 *trow = Tb + (strip * 16 + L.mi) * TB + 4 * L.mq;
+        h16 *trow = Tb + tile_strip_off<TS>(strip, L);
         const float b = smx[s];
         // normalised by their own row sum (see dense_bwd_rc2_body): sum_j P_ij = 1 for the P that is differentiated
         float lsum = 0.f;
@@ -228,14 +229,9 @@ __device__ __forceinline__ void dense_bwd_wide_body(float *lds, const Csr &g, in
     }
   } else {  // tile := 0, then P of every edge as fp16 hi | lo (scale 2^14)
     const int tid = opaque_tid();
-    for (int k = tid; k < NP * TS / 4; k += kDenseThreads) reinterpret_cast<float4 *>(T)[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int k = tid; k < tile_elems(TS, NP) / 8; k += kDenseThreads) reinterpret_cast<float4 *>(T)[k] = make_float4(0.f, 0.f, 0.f, 0.f);
     lds_barrier();
-    auto put = [&](unsigned c, float p) {
-      const int at = (int)(c >> 8) * TB + (int)(c & 0xFF);
-      const h16 hh = (h16)(p * kUnitScale);
-      Tb[at] = hh;
-      Tb[at + TS] = (h16)fmaf(p, kUnitScale, -(float)hh);
-    };
+    auto put = [&](unsigned c, float p) { tile_put_p<TS>(Tb, (int)(c >> 8), (int)(c & 0xFF), p); };
 #pragma unroll
     for (int k = 0; k < PRE; ++k)
       if (tid + k * kDenseThreads < ne) put(pc[k], pa[k]);
@@ -272,7 +268,7 @@ __device__ __forceinline__ void dense_bwd_wide_body(float *lds, const Csr &g, in
 #pragma unroll
       for (int ib = 0; ib < NP / 32; ++ib) {
         if (32 * ib < n) {
-          const int yoff = (32 * ib + 4 * L.mq + L.tq) * TB + 16 * cs + 4 * L.tp;
+          const int yoff = tile_tr_off<TS>(cs, L) + 32 * ib * TB;
           const hx8 yh = dense_tr_pair(Tb + yoff, 16 * TB);
           const hx8 yl = dense_tr_pair(Tb + yoff + TS, 16 * TB);
           dense_kblock_mma<FW, (FW > 64 ? 8 : 4)>(acc, ihi, ilo, (32 * ib + 4 * L.mq + L.tq) * RS + 4 * L.tp, 16 * RS, yh, yl);
@@ -285,7 +281,7 @@ __device__ __forceinline__ void dense_bwd_wide_body(float *lds, const Csr &g, in
 #pragma unroll
       for (int ib = 0; ib < NP / 32; ++ib) {
         if (32 * ib < n) {
-          const int yoff = (32 * ib + 4 * L.mq + L.tq) * TB + 16 * cs + 4 * L.tp;
+          const int yoff = tile_tr_off<TS>(cs, L) + 32 * ib * TB;
           const hx8 yh = dense_tr_pair(Tb + yoff, 16 * TB);
           const hx8 yl = dense_tr_pair(Tb + yoff + TS, 16 * TB);
           const int xoff = (32 * ib + 4 * L.mq + L.tq) * RS + 4 * L.tp + 16 * ft;
@@ -371,7 +367,7 @@ __device__ __forceinline__ void dense_bwd_wide_body(float *lds, const Csr &g, in
     const int strip = wave + kDenseWaves * s;
     if (strip < nstrip) {
       const LaneIds L = lane_ids();
-      const h16 *prow = Tb + (strip * 16 + L.mi) * TB + 4 * L.mq;
+      const h16 *prow = Tb + tile_strip_off<TS>(strip, L);
       float t = 0.f;
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -407,7 +403,7 @@ __device__ __forceinline__ void dense_bwd_wide_body(float *lds, const Csr &g, in
     const int strip = wave + kDenseWaves * s;
     if (strip < nstrip) {
       const LaneIds L = lane_ids();
-      h16 *trow = Tb + (strip * 16 + L.mi) * TB + 4 * L.mq;
+      h16 *trow = Tb + tile_strip_off<TS>(strip, L);
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         hx4 h4, l4;
@@ -422,7 +418,7 @@ __device__ __forceinline__ void dense_bwd_wide_body(float *lds, const Csr &g, in
       }
     }
   }
-  image_store(QB + 2 * NH);  // K, half 0
+  image_store(QB + 2 * NH, true);  // K, half 0
   lds_barrier();
   DFGNN_WSTAMP(7)
 
@@ -438,13 +434,15 @@ __device__ __forceinline__ void dense_bwd_wide_body(float *lds, const Csr &g, in
         f32x4 qacc[FT];
 #pragma unroll
         for (int t = 0; t < FT; ++t) qacc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const h16 *srow = Tb + (strip * 16 + L.mi) * TB + 8 * L.mq;
+        // natural k order: columns 32 jb + 8 mq .. + 7 of dS as two 4-column chunks, against those rows of K
+        const h16 *sa = Tb + tile_row_off<TS>(strip, 0, L), *sb = Tb + tile_row_off<TS>(strip, 1, L);
+        const KImageOff ko = image_k_off<RS>(L);
 #pragma unroll
         for (int jb = 0; jb < NP / 32; ++jb) {
           if (32 * jb < n) {
-            const hx8 sh = *reinterpret_cast<const hx8 *>(srow + 32 * jb);
-            const hx8 sl = *reinterpret_cast<const hx8 *>(srow + TS + 32 * jb);
-            dense_kblock_mma<FW, (FW > 64 ? 8 : 4)>(qacc, ihi, ilo, (32 * jb + 8 * L.mq + L.tq) * RS + 4 * L.tp, 4 * RS, sh, sl);
+            const hx8 sh = tile_row8(sa + 32 * jb, sb + 32 * jb);
+            const hx8 sl = tile_row8(sa + TS + 32 * jb, sb + TS + 32 * jb);
+            dense_kblock_mma<FW, (FW > 64 ? 8 : 4)>(qacc, ihi, ilo, ko.first + 32 * jb * RS, ko.second, sh, sl);
           }
         }
         const int i = strip * 16 + L.mi;
@@ -464,7 +462,7 @@ __device__ __forceinline__ void dense_bwd_wide_body(float *lds, const Csr &g, in
     if (h + 1 < NH) {
       image_post(QB + 2 * NH + 2 * h + 2);
       lds_barrier();  // the Q image is free
-      image_store(QB + 2 * NH + 2 * h + 2);  // K, half h + 1
+      image_store(QB + 2 * NH + 2 * h + 2, true);  // K, half h + 1
       lds_barrier();
     }
   }
@@ -498,7 +496,7 @@ __device__ __forceinline__ void dense_bwd_wide2_body(float *lds, const Csr &g, i
   constexpr int FW = 64, NH = FR / FW;  // image width, feature halves
   using D = DenseCfg<FW>;
   constexpr int RS = D::RS, KT = D::KT, FT = D::FT;
-  constexpr int NC = kDenseWide2Rows, RB = NC / 2, U = NC / 16, TS = NC + 8, TB = 2 * TS, PRE = kDensePre;
+  constexpr int NC = kDenseWide2Rows, RB = NC / 2, U = NC / 16, TS = tile_ts(NC), TB = 2 * TS, PRE = kDensePre;
   constexpr int NQ = 4 * NH;  // images of a row block: dO.0 V.0 [dO.1 V.1] K.0 Q.0 [K.1 Q.1]
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
   const int ncs = (n + 15) >> 4;  // column strips
@@ -528,12 +526,7 @@ __device__ __forceinline__ void dense_bwd_wide2_body(float *lds, const Csr &g, i
   // P of the row block's edges [ea, ea + cnt) -> the (cleared) tile, as fp16 hi | lo (scale 2^14); i0 = its first row
   auto scatter = [&](int i0, int ea, int cnt) {
     const int tid = opaque_tid();
-    auto put = [&](unsigned c, float p) {
-      const int at = ((int)(c >> 8) - i0) * TB + (int)(c & 0xFF);
-      const h16 hh = (h16)(p * kUnitScale);
-      Tb[at] = hh;
-      Tb[at + TS] = (h16)fmaf(p, kUnitScale, -(float)hh);
-    };
+    auto put = [&](unsigned c, float p) { tile_put_p<TS>(Tb, (int)(c >> 8) - i0, (int)(c & 0xFF), p); };
 #pragma unroll
     for (int k = 0; k < PRE; ++k)
       if (tid + k * kDenseThreads < cnt) put(pc[k], pa[k]);
@@ -572,10 +565,11 @@ __device__ __forceinline__ void dense_bwd_wide2_body(float *lds, const Csr &g, i
   auto image_post = [&](int gq) {
     wg_max_post(smax, image_rows(gq) ? dense_stage_absmax<FW, NC, RB>(st[gq % R]) : dense_stage_absmax<FW, NC>(st[gq % R]));
   };
-  auto image_store = [&](int gq) {  // ... and the register set is refilled with the image R phases on
+  // kswap (a literal): a K image of the dQ product
+  auto image_store = [&](int gq, bool kswap = false) {  // ... and the register set is refilled with the image R phases on
     isc = pow2_scale(wg_max_read(smax));
     if (image_rows(gq)) dense_stage_store<FW, NC, RB>(st[gq % R], ihi, ilo, isc.s);
-    else dense_stage_store<FW, NC>(st[gq % R], ihi, ilo, isc.s);
+    else dense_stage_store<FW, NC>(st[gq % R], ihi, ilo, isc.s, FW, kswap);
     image_fetch(gq + R);
   };
 
@@ -607,7 +601,7 @@ __device__ __forceinline__ void dense_bwd_wide2_body(float *lds, const Csr &g, i
 #pragma unroll
       for (int ib = 0; ib < RB / 32; ++ib) {
         if (32 * ib < ni) {
-          const int yoff = (32 * ib + 4 * L.mq + L.tq) * TB + 16 * cs + 4 * L.tp;
+          const int yoff = tile_tr_off<TS>(cs, L) + 32 * ib * TB;
           const hx8 yh = dense_tr_pair(Tb + yoff, 16 * TB);
           const hx8 yl = dense_tr_pair(Tb + yoff + TS, 16 * TB);
           dense_kblock_mma<FW, 4>(acc, ihi, ilo, (32 * ib + 4 * L.mq + L.tq) * RS + 4 * L.tp, 16 * RS, yh, yl);
@@ -619,7 +613,7 @@ __device__ __forceinline__ void dense_bwd_wide2_body(float *lds, const Csr &g, i
 #pragma unroll
       for (int ib = 0; ib < RB / 32; ++ib) {
         if (32 * ib < ni) {
-          const int yoff = (32 * ib + 4 * L.mq + L.tq) * TB + 16 * cs + 4 * L.tp;
+          const int yoff = tile_tr_off<TS>(cs, L) + 32 * ib * TB;
           const hx8 yh = dense_tr_pair(Tb + yoff, 16 * TB);
           const hx8 yl = dense_tr_pair(Tb + yoff + TS, 16 * TB);
           const int xoff = (32 * ib + 4 * L.mq + L.tq) * RS + 4 * L.tp + 16 * ft;
@@ -664,7 +658,7 @@ __device__ __forceinline__ void dense_bwd_wide2_body(float *lds, const Csr &g, i
     if (rb > 0) lds_barrier();  // the previous row block's dS tile and Q image are free
     {
       const int tid = opaque_tid();
-      for (int k = tid; k < RB * TS / 4; k += kDenseThreads) reinterpret_cast<float4 *>(T)[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int k = tid; k < tile_elems(TS, RB) / 8; k += kDenseThreads) reinterpret_cast<float4 *>(T)[k] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
     lds_barrier();
     if (rb == 0) scatter(0, e0, e1 - e0);
@@ -717,7 +711,7 @@ __device__ __forceinline__ void dense_bwd_wide2_body(float *lds, const Csr &g, i
     float tmax = 0.f;
     if (row_wave) {
       const LaneIds L = lane_ids();
-      const h16 *prow = Tb + (wave * 16 + L.mi) * TB + 4 * L.mq;
+      const h16 *prow = Tb + tile_strip_off<TS>(wave, L);
       float t = 0.f;
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -742,7 +736,7 @@ __device__ __forceinline__ void dense_bwd_wide2_body(float *lds, const Csr &g, i
     const Pow2Scale ts = pow2_scale(wg_max_read(smax + kDenseWaves));
     if (row_wave) {
       const LaneIds L = lane_ids();
-      h16 *trow = Tb + (wave * 16 + L.mi) * TB + 4 * L.mq;
+      h16 *trow = Tb + tile_strip_off<TS>(wave, L);
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         hx4 h4, l4;
@@ -756,7 +750,7 @@ __device__ __forceinline__ void dense_bwd_wide2_body(float *lds, const Csr &g, i
         *reinterpret_cast<hx4 *>(trow + TS + 16 * u) = l4;
       }
     }
-    image_store(q0 + 2 * NH);  // K, half 0
+    image_store(q0 + 2 * NH, true);  // K, half 0
     lds_barrier();
 
     // ---- dQ.h = dS K.h ; dK.h (+)= dS^T Q.h -------------------------------------------------------------------------------
@@ -767,13 +761,14 @@ __device__ __forceinline__ void dense_bwd_wide2_body(float *lds, const Csr &g, i
         f32x4 qacc[FT];
 #pragma unroll
         for (int t = 0; t < FT; ++t) qacc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const h16 *srow = Tb + (wave * 16 + L.mi) * TB + 8 * L.mq;
+        const h16 *sa = Tb + tile_row_off<TS>(wave, 0, L), *sb = Tb + tile_row_off<TS>(wave, 1, L);
+        const KImageOff ko = image_k_off<RS>(L);
 #pragma unroll
         for (int jb = 0; jb < NC / 32; ++jb) {
           if (32 * jb < n) {
-            const hx8 sh = *reinterpret_cast<const hx8 *>(srow + 32 * jb);
-            const hx8 sl = *reinterpret_cast<const hx8 *>(srow + TS + 32 * jb);
-            dense_kblock_mma<FW, 4>(qacc, ihi, ilo, (32 * jb + 8 * L.mq + L.tq) * RS + 4 * L.tp, 4 * RS, sh, sl);
+            const hx8 sh = tile_row8(sa + 32 * jb, sb + 32 * jb);
+            const hx8 sl = tile_row8(sa + TS + 32 * jb, sb + TS + 32 * jb);
+            dense_kblock_mma<FW, 4>(qacc, ihi, ilo, ko.first + 32 * jb * RS, ko.second, sh, sl);
           }
         }
         dense_store_rows<FT>(qacc, isc.inv * ts.inv, dQb + h * FW, hf, i0 + wave * 16 + L.mi, i0 + ni, L);
@@ -788,7 +783,7 @@ __device__ __forceinline__ void dense_bwd_wide2_body(float *lds, const Csr &g, i
       if (h + 1 < NH) {
         image_post(q0 + 2 * NH + 2 * h + 2);
         lds_barrier();  // the Q image is free
-        image_store(q0 + 2 * NH + 2 * h + 2);  // K, half h + 1
+        image_store(q0 + 2 * NH + 2 * h + 2, true);  // K, half h + 1
         lds_barrier();
       }
     }
