@@ -21,6 +21,7 @@ from .GAT_DOT import DOTGATConv_csr, DOTGATConv_forward, DOTGATConv_hyper, DOTGA
 from .GAT import (GATConv_dgNN, GATConv_hyper, GATConv_hyper_ablation, GATConv_hyper_recompute, GATConv_hyper_v2,
                   GATConv_softmax, GATConv_softmax_gm, GATConv_tiling)
 from .GATv2 import GATv2Conv_edge_timing, GATv2Conv_forward, GATv2Conv_tiling
+from .GatedGCN import GatedGCNConv_plain_timing, GatedGCNConv_timing
 from .GT import (SparseMHA_bias_timing, SparseMHA_CSR, SparseMHA_CSR_GM, SparseMHA_edge_timing, SparseMHA_forward_timing,
                  SparseMHA_gate_timing, SparseMHA_hyper, SparseMHA_rowstats_timing, SparseMHA_softmax, SparseMHA_softmax_gm,
                  SparseMHA_tbias_timing, SparseMHA_tiling, SparseMHA_typed_timing)
@@ -150,6 +151,9 @@ _AGNN_LAYERS = {  # reference :424-442
 # vectors inside the LeakyReLU (seeded random here)
 _GATV2_LAYERS = {"tiling": GATv2Conv_tiling, "csr": GATv2Conv_tiling, "forward": GATv2Conv_forward,
                  "forward_edge": GATv2Conv_edge_timing}
+# this build's addition (the reference has no GatedGCN): "forward" is the Dwivedi / GraphGPS form on the fused pair (seeded
+# random edge term, normalised, with the edge output), "forward_plain" PyG's ResGatedGraphConv (no edge term, no normalisation)
+_GATEDGCN_LAYERS = {"forward": GatedGCNConv_timing, "forward_plain": GatedGCNConv_plain_timing}
 # "forward": this build's addition, the training layer on the fused AGNN pair in dot mode
 _DOTGAT_LAYERS = {"hyper": DOTGATConv_hyper, "csr": DOTGATConv_csr, "softmax": DOTGATConv_softmax, "forward": DOTGATConv_forward}
 # formats of the reference that are baselines on NVIDIA-only libraries or paper experiments
@@ -186,7 +190,13 @@ def load_layer_GATv2(args):
     return _pick(_GATV2_LAYERS, args, "GATv2conv")
 
 
+def load_layer_GatedGCN(args):
+    return _pick(_GATEDGCN_LAYERS, args, "GatedGCNconv")
+
+
 def load_graphconv_layer(args):
+    if args.conv == "gatedgcn":
+        return load_layer_GatedGCN(args)
     if args.conv == "dotgat":
         return load_layer_DOTGAT(args)
     if args.conv == "gatv2":
@@ -212,6 +222,6 @@ def load_prepfunc(args):
     if args.format in ("softmax", "softmax_gm"):
         return preprocess_softmax
     if args.format in ("forward", "forward_rowstats", "forward_bias", "forward_edge", "forward_gate", "forward_typed", "forward_tbias",
-                       "forward_beta"):
+                       "forward_beta", "forward_plain"):
         return preprocess_Hyper_fw_bw
     raise ValueError(f"Unsupported format {args.format}")

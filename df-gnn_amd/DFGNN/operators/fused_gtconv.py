@@ -137,6 +137,52 @@ def AGNNConvFuse(row_ptr, col_ind, col_ptr, row_ind, beta, X_row, X_col, cosine=
     return FusedAGNNFunction.apply(row_ptr, col_ind, col_ptr, row_ind, beta, X_row, X_col, cosine)
 
 
+# ---- GatedGCN: per-dimension sigmoid gates, optional edge term and edge output (this build's addition; fused_gtconv.gatedgcn_*)
+def GatedGCNConvFuse_inference(row_ptr, col_ind, X_row, X_col, V, E=None, normalize=True, eps=1e-6, edge_out=False):
+    """-> out[m, h, f] = sum_j sg_ij (.) V_j [/ (sum_j sg_ij + eps)] with sg_ij = sigmoid(X_row_i + X_col_j + E_ij), or
+    (out, Z) with edge_out: Z[nnz, h, f] = X_row_i + X_col_j + E_ij in CSR edge order.  E fp32[nnz, h, f] or None."""
+    return fused_gt.gatedgcn_inference(row_ptr, col_ind, X_row, X_col, V, E, normalize, eps, need_Z=edge_out)
+
+
+class FusedGatedGCNFunction(torch.autograd.Function):
+    """Training pair (include/dfgnn.h: dfgnn_gatedgcn_fwd / dfgnn_gatedgcn_bwd, csrc/gatedgcn_train.hip) -> (out, Z), or out
+    alone with edge_out=False.  Z is an OUTPUT the model trains through: its gradient G enters the backward next to grad_out
+    (None when Z was not used: then nothing of G is read).  Z is not saved -- the backward recomputes every edge from the rows
+    it gathers.  Saved between forward and backward: X_row, X_col, V, E (when given), the graph arrays and, with normalize,
+    out and den [m, h, f].  dE[nnz, h, f] is computed only when E requires a gradient."""
+
+    @staticmethod
+    def forward(ctx, row_ptr, col_ind, col_ptr, row_ind, val_idx, X_row, X_col, V, E, normalize, eps, edge_out):
+        out, den, Z = fused_gt.gatedgcn_forward(row_ptr, col_ind, X_row, X_col, V, E, normalize, eps, need_Z=edge_out)
+        keep = ((E,) if E is not None else ()) + ((out, den) if normalize else ())
+        ctx.save_for_backward(row_ptr, col_ind, col_ptr, row_ind, val_idx, X_row, X_col, V, *keep)
+        ctx.has_E, ctx.normalize, ctx.eps = E is not None, bool(normalize), float(eps)
+        ctx.set_materialize_grads(False)       # an unused Z arrives as None, not as zeros [nnz, h, f]
+        return (out, Z) if edge_out else out
+
+    @staticmethod
+    def backward(ctx, grad_out, grad_Z=None):
+        row_ptr, col_ind, col_ptr, row_ind, val_idx, X_row, X_col, V, *keep = ctx.saved_tensors
+        E = keep.pop(0) if ctx.has_E else None
+        out, den = keep if ctx.normalize else (None, None)
+        if grad_out is None:                   # only Z was used
+            grad_out = torch.zeros_like(X_row)
+        dX_row, dX_col, dV, dE = fused_gt.gatedgcn_backward(
+            row_ptr, col_ind, col_ptr, row_ind, val_idx, X_row, X_col, V, E, out, den, grad_out.contiguous(),
+            G=None if grad_Z is None else grad_Z.contiguous(), normalize=ctx.normalize, eps=ctx.eps,
+            need_dE=ctx.has_E and ctx.needs_input_grad[8])
+        # (one tensor passed as both X_row and X_col: autograd adds the two gradients)
+        return (None,) * 5 + (dX_row, dX_col, dV, dE, None, None, None)
+
+
+def GatedGCNConvFuse(row_ptr, col_ind, col_ptr, row_ind, val_idx, X_row, X_col, V, E=None, normalize=True, eps=1e-6,
+                     edge_out=True):
+    """Differentiable GatedGCN conv of any graph, square or m x n_cols -> (out, Z) with the edge output Z[nnz, h, f] =
+    X_row_i + X_col_j + E_ij, or out alone with edge_out=False; the gradient goes to X_row, X_col, V and E."""
+    return FusedGatedGCNFunction.apply(row_ptr, col_ind, col_ptr, row_ind, val_idx, X_row, X_col, V, E, normalize, eps,
+                                       edge_out)
+
+
 class FusedGTFunction_bias(torch.autograd.Function):
     """FusedGTFunction_rowstats with a per-edge, per-head additive attention bias (include/dfgnn.h: dfgnn_gt_fwd_bias /
     dfgnn_gt_bwd_bias, csrc/gt_bias_train.hip): s_e = val_e <Q_i, K_j> + bias[h, e], bias fp32[h, nnz] in CSR edge order,

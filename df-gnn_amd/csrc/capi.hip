@@ -675,6 +675,55 @@ int dfgnn_gatv2_bwd_edge(int m, int nnz, int h, int f, const int *row_ptr, const
                                    X_col, E, out, row_max, row_sum, grad_out, delta, ws, dX_row, dX_col, dattn, dE, stream);
 }
 
+// ---- GatedGCN (gatedgcn_train.hip): fused inference and training pair, any graph ------------------------------------------
+static bool gatedgcn_mode_ok(int normalize, float eps) {
+  return (normalize == 0 || normalize == 1) && eps >= 0.f && eps <= 3.0e38f;  // (a NaN fails both comparisons)
+}
+
+int dfgnn_gatedgcn_fwd_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind,
+                            const float *X_row, const float *X_col, const float *V, const float *E, int normalize, float eps,
+                            float *den, float *out, float *Z, dfgnn_stream_t stream) {
+  if (!gatedgcn_mode_ok(normalize, eps)) return kErrBadArg;
+  if (int c = check_rect(m, n_cols, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (m == 0) return 0;  // (no row: nothing to write)
+  if (!X_row || (n_cols > 0 && (!X_col || !V)) || !out) return kErrBadArg;
+  const Csr g = rect_csr(m, n_cols, nnz, h, f, row_ptr, col_ind, nullptr);
+  return launch_gatedgcn_fwd(g, GatedGcnGraph{nullptr, nullptr, nullptr, normalize == 1, eps}, X_row, X_col, V, E, den, out,
+                             Z, as_stream(stream));
+}
+
+int dfgnn_gatedgcn_fwd(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *X_row,
+                       const float *X_col, const float *V, const float *E, int normalize, float eps, float *den, float *out,
+                       float *Z, dfgnn_stream_t stream) {
+  return dfgnn_gatedgcn_fwd_rect(m, m, nnz, h, f, row_ptr, col_ind, X_row, X_col, V, E, normalize, eps, den, out, Z, stream);
+}
+
+int dfgnn_gatedgcn_bwd_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind,
+                            const int *col_ptr, const int *row_ind, const int *val_idx, const float *X_row,
+                            const float *X_col, const float *V, const float *E, int normalize, float eps, const float *out,
+                            const float *den, const float *grad_out, const float *G, float *dX_row, float *dX_col, float *dV,
+                            float *dE, float *ws, dfgnn_stream_t stream) {
+  if (!gatedgcn_mode_ok(normalize, eps)) return kErrBadArg;
+  if (int c = check_rect(m, n_cols, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (nnz > 0 && (!row_ind || !val_idx)) return kErrBadArg;  // (the CSC pass finds an entry's E and G rows through val_idx)
+  if (m > 0 && (!X_row || !grad_out || !dX_row)) return kErrBadArg;
+  if (m > 0 && normalize == 1 && (!out || !den || !ws)) return kErrBadArg;  // (normalize = 0 reads none of the three)
+  if (n_cols > 0 && (!X_col || !V || !dX_col || !dV || !col_ptr)) return kErrBadArg;
+  if ((dX_row && (dX_row == dX_col || dX_row == dV)) || (dX_col && dX_col == dV)) return kErrBadArg;  // (each written in full)
+  const Csr g = rect_csr(m, n_cols, nnz, h, f, row_ptr, col_ind, nullptr);
+  return launch_gatedgcn_bwd(g, GatedGcnGraph{col_ptr, row_ind, val_idx, normalize == 1, eps}, X_row, X_col, V, E, out, den,
+                             grad_out, G, dX_row, dX_col, dV, dE, ws, as_stream(stream));
+}
+
+int dfgnn_gatedgcn_bwd(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const int *col_ptr,
+                       const int *row_ind, const int *val_idx, const float *X_row, const float *X_col, const float *V,
+                       const float *E, int normalize, float eps, const float *out, const float *den, const float *grad_out,
+                       const float *G, float *dX_row, float *dX_col, float *dV, float *dE, float *ws,
+                       dfgnn_stream_t stream) {
+  return dfgnn_gatedgcn_bwd_rect(m, m, nnz, h, f, row_ptr, col_ind, col_ptr, row_ind, val_idx, X_row, X_col, V, E, normalize,
+                                 eps, out, den, grad_out, G, dX_row, dX_col, dV, dE, ws, stream);
+}
+
 int dfgnn_gt_tiling_fwd(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
                         const float *Q, const float *K, const float *V, float *out, dfgnn_stream_t stream) {
   if (int c = check_common(m, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;

@@ -345,6 +345,20 @@ int launch_agnn_fwd(const Csr &g, const AgnnGraph &v, const float *X_row, const 
 int launch_agnn_bwd(const Csr &g, const AgnnGraph &v, const float *X_row, const float *X_col, const float *out,
                     const float *row_max, const float *row_sum, const float *grad_out, float *delta, float *dX_row,
                     float *dX_col, float *dbeta_rows, hipStream_t s);
+// GatedGCN pair (gatedgcn_train.hip): any graph, no plan.  z_e = (X_row_i + X_col_j) + E_e, sg_e = sigmoid(z_e) per
+// dimension, out_i = sum sg_e (.) V_j [/ (den_i + eps)].  The forward writes den [m, h, f] (nullable: inference) and Z =
+// z [nnz, h, f] (nullable); the backward is the CSR pass (dX_row, dE, and with normalize s_i = dO_i / (den_i + eps) -> ws
+// [m, h, f]) then the CSC pass (dX_col, dV), on one stream.  E, G, Z, dE nullable; out, den, ws unused without normalize.
+struct GatedGcnGraph {
+  const int *col_ptr, *row_ind, *val_idx;  // CSC (backward only)
+  bool normalize;
+  float eps;
+};
+int launch_gatedgcn_fwd(const Csr &g, const GatedGcnGraph &v, const float *X_row, const float *X_col, const float *V,
+                        const float *E, float *den, float *out, float *Z, hipStream_t s);
+int launch_gatedgcn_bwd(const Csr &g, const GatedGcnGraph &v, const float *X_row, const float *X_col, const float *V,
+                        const float *E, const float *out, const float *den, const float *grad_out, const float *G,
+                        float *dX_row, float *dX_col, float *dV, float *dE, float *ws, hipStream_t s);
 // graphs with fewer than kBlockMinAvgDegree edges per row on average take the row-per-lane-group kernels.  The pairs that
 // take an m x n_cols graph ask per pass: (m, nnz) for the forward and the CSR pass, (n_cols, nnz) for the CSC pass
 inline bool low_degree(int m, int nnz) { return (long)nnz < (long)kBlockMinAvgDegree * m; }

@@ -948,6 +948,83 @@ std::vector<Tensor> gatv2_bwd_edge(double slope, const Tensor &row_ptr, const Te
   return res;
 }
 
+// ---- GatedGCN (include/dfgnn.h: dfgnn_gatedgcn_fwd / dfgnn_gatedgcn_bwd): any graph -----------------------------------------
+// What both entry points check: X_row fp32 [m, heads, feat], X_col and V fp32 [n_cols, heads, feat], the CSR arrays
+Dims gatedgcn_checks(const Tensor &row_ptr, const Tensor &col_ind, const Tensor &X_row, const Tensor &X_col, const Tensor &V) {
+  gatv2_edge_csr_dtype(row_ptr, col_ind);
+  check_i32(row_ptr, "row_ptr");
+  check_i32(col_ind, "col_ind");
+  check_feat3(X_row, X_row, "X_row");
+  check_cols_feat(X_col, "X_col", X_row, "X_row");
+  check_f32(V, "V");
+  TORCH_CHECK(V.sizes() == X_col.sizes(), "V must have shape ", shape_str(X_col), " like X_col, got ", shape_str(V));
+  TORCH_CHECK(row_ptr.dim() == 1 && col_ind.dim() == 1, "indptr / indices must be 1-D");
+  TORCH_CHECK(row_ptr.size(0) - 1 == X_row.size(0), "indptr describes ", row_ptr.size(0) - 1, " rows but features have ",
+              X_row.size(0), " nodes");
+  check_same_device(X_row, {&row_ptr, &col_ind, &X_col, &V});
+  return Dims{(int)X_row.size(0), (int)col_ind.size(0), (int)X_row.size(1), (int)X_row.size(2), (int)X_col.size(0)};
+}
+// E, G: fp32 [nnz, h, f] in CSR edge order; worded as the ctypes transport does (_binding_util._family)
+void gatedgcn_edge_checks(const Dims &d, const Tensor &ref, const Tensor &T, const char *name) {
+  check_cuda_contig(T, name);
+  TORCH_CHECK(T.scalar_type() == torch::kFloat32, name, " must have dtype torch.float32, got ", py_dtype(T));
+  TORCH_CHECK(T.dim() == 3 && T.size(0) == d.nnz && T.size(1) == d.h && T.size(2) == d.f, name, " must have shape (", d.nnz,
+              ", ", d.h, ", ", d.f, "), got ", shape_str(T));
+  check_same_device(ref, {&T});
+}
+
+// -> {out}, then den with save_den (training), then Z with need_Z
+std::vector<Tensor> gatedgcn_fwd(const Tensor &row_ptr, const Tensor &col_ind, const Tensor &X_row, const Tensor &X_col,
+                                 const Tensor &V, const c10::optional<Tensor> &E, bool normalize, double eps, bool save_den,
+                                 bool need_Z) {
+  const Dims d = gatedgcn_checks(row_ptr, col_ind, X_row, X_col, V);
+  if (E) gatedgcn_edge_checks(d, X_row, *E, "E");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(X_row.device());
+  Tensor out = torch::empty_like(X_row), den, Z;
+  if (save_den) den = torch::empty_like(X_row);
+  if (need_Z) Z = torch::empty({d.nnz, d.h, d.f}, X_row.options());
+  check_rc(dfgnn_gatedgcn_fwd_rect(d.m, d.n_cols, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), f32(X_row), f32(X_col), f32(V),
+                                   f32(E), normalize ? 1 : 0, (float)eps, f32(den), f32(out), f32(Z), cur_stream()),
+           save_den ? "gatedgcn_forward" : "gatedgcn_inference");
+  std::vector<Tensor> res = {out};
+  if (save_den) res.push_back(den);
+  if (need_Z) res.push_back(Z);
+  return res;
+}
+
+// out, den: the forward's (read with normalize only).  G: the gradient of Z, or nothing (zero).
+// -> {dX_row, dX_col, dV, dE}, or {dX_row, dX_col, dV} without need_dE
+std::vector<Tensor> gatedgcn_bwd(const Tensor &row_ptr, const Tensor &col_ind, const Tensor &col_ptr, const Tensor &row_ind,
+                                 const Tensor &val_idx, const Tensor &X_row, const Tensor &X_col, const Tensor &V,
+                                 const c10::optional<Tensor> &E, bool normalize, double eps, const c10::optional<Tensor> &out,
+                                 const c10::optional<Tensor> &den, const Tensor &grad, const c10::optional<Tensor> &G,
+                                 bool need_dE) {
+  const Dims d = gatedgcn_checks(row_ptr, col_ind, X_row, X_col, V);
+  if (E) gatedgcn_edge_checks(d, X_row, *E, "E");
+  if (G) gatedgcn_edge_checks(d, X_row, *G, "G");
+  csc_rect_checks(d, X_row, col_ptr, row_ind, &val_idx, "X_col");
+  check_feat3(grad, X_row, "grad");
+  check_same_device(X_row, {&grad});
+  TORCH_CHECK(!normalize || (out && den), "out and den of the forward are required with normalize");
+  if (normalize) {
+    check_feat3(*out, X_row, "out");
+    check_feat3(*den, X_row, "den");
+    check_same_device(X_row, {&*out, &*den});
+  }
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(X_row.device());
+  Tensor dX_row = torch::empty_like(X_row), dX_col = torch::empty_like(X_col), dV = torch::empty_like(V);
+  Tensor dE, ws;
+  if (need_dE) dE = torch::empty({d.nnz, d.h, d.f}, X_row.options());
+  if (normalize) ws = torch::empty_like(X_row);  // s_i = dO_i / (den_i + eps), CSR pass -> CSC pass
+  check_rc(dfgnn_gatedgcn_bwd_rect(d.m, d.n_cols, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), i32(col_ptr), i32(row_ind),
+                                   i32(val_idx), f32(X_row), f32(X_col), f32(V), f32(E), normalize ? 1 : 0, (float)eps,
+                                   normalize ? f32(out) : nullptr, normalize ? f32(den) : nullptr, f32(grad), f32(G),
+                                   f32(dX_row), f32(dX_col), f32(dV), f32(dE), f32(ws), cur_stream()),
+           "gatedgcn_backward");
+  if (!need_dE) return {dX_row, dX_col, dV};
+  return {dX_row, dX_col, dV, dE};
+}
+
 // fused_gtconv.cpp:244-276 (tiling), :174-242 (csr, csr_gm), :316-389 (softmax, softmax_gm): the GT inference variants that
 // take CSR (+ the COO rows for the two-kernel forms).  which: 0 tiling, 1 csr, 2 csr_gm, 3 softmax, 4 softmax_gm
 Tensor gt_variant_fwd(int64_t which, const Tensor &indptr, const Tensor &indices, const c10::optional<Tensor> &rows, const Tensor &val,
@@ -1062,6 +1139,8 @@ PYBIND11_MODULE(_dfgnn_ext, m) {
   m.def("agnn_bwd", &agnn_bwd, "fused AGNN / dot-product conv backward of any graph from the forward's output and row statistics");
   m.def("gatv2_fwd_edge", &gatv2_fwd_edge, "fused GATv2 conv forward of any graph with a per-edge feature vector inside the LeakyReLU");
   m.def("gatv2_bwd_edge", &gatv2_bwd_edge, "fused GATv2 conv backward of any graph with a per-edge feature vector inside the LeakyReLU");
+  m.def("gatedgcn_fwd", &gatedgcn_fwd, "fused GatedGCN conv forward of any graph (inference, or training with den; optional edge output)");
+  m.def("gatedgcn_bwd", &gatedgcn_bwd, "fused GatedGCN conv backward of any graph from the forward's out and den");
   m.def("gt_variant_fwd", &gt_variant_fwd, "fused GT conv inference: tiling / csr / csr_gm / softmax / softmax_gm");
   m.def("plan_build", &plan_build, "block plan of a CSR structure (dfgnn_plan_build)");
   m.def("preprocess_hyper", &preprocess_hyper, "COO -> CSR / COO rows / CSC on the GPU (dfgnn_preprocess_hyper)");

@@ -71,6 +71,10 @@ SIGNATURES = {
     "dfgnn_agnn_bwd": [_i] * 4 + [_vp] * 5 + [_i] + [_vp] * 11,
     "dfgnn_agnn_fwd_rect": [_i] * 5 + [_vp] * 3 + [_i] + [_vp] * 6,
     "dfgnn_agnn_bwd_rect": [_i] * 5 + [_vp] * 5 + [_i] + [_vp] * 11,
+    "dfgnn_gatedgcn_fwd": [_i] * 4 + [_vp] * 6 + [_i, _f] + [_vp] * 4,
+    "dfgnn_gatedgcn_bwd": [_i] * 4 + [_vp] * 9 + [_i, _f] + [_vp] * 10,
+    "dfgnn_gatedgcn_fwd_rect": [_i] * 5 + [_vp] * 6 + [_i, _f] + [_vp] * 4,
+    "dfgnn_gatedgcn_bwd_rect": [_i] * 5 + [_vp] * 9 + [_i, _f] + [_vp] * 10,
     "dfgnn_gt_bwd_rows": [_i, _i, _i, _i] + [_vp] * 11,
     "dfgnn_gt_bwd_cols": [_i, _i, _i, _i] + [_vp] * 11,
     "dfgnn_gt_tiling_fwd": [_i, _i, _i, _i] + [_vp] * 8,

@@ -701,6 +701,79 @@ def agnn_backward(row_ptr, col_ind, col_ptr, row_ind, beta, X_row, X_col, out, r
     return [dX_row, dX_col, dbeta_rows.sum(0) if need_dbeta else None]
 
 
+# ---- GatedGCN (include/dfgnn.h: dfgnn_gatedgcn_fwd / dfgnn_gatedgcn_bwd) -----------------------------------------------
+# Not part of the reference's module.  z_e = X_row_i + X_col_j + E_e, sg_e = sigmoid(z_e) per dimension, out_i = sum sg_e (.)
+# V_j [/ (sum sg_e + eps)], edge output Z = z (csrc/gatedgcn_train.hip): E, Z, the gradient G of Z and dE are fp32[nnz, h, f]
+# in CSR edge order.  Any graph, square or m x n_cols, no plan, any f.  DFGNN.operators.fused_gtconv.GatedGCNConvFuse takes it.
+
+
+def _check_gatedgcn(row_ptr, col_ind, X_row, X_col, V, E=None, G=None, **like_X):
+    """X_row (and `like_X`: grad, out, den) fp32 [m, heads, feat], X_col and V fp32 [n_cols, heads, feat], the CSR arrays of
+    the m rows, E and G (each optional) fp32 [nnz, heads, feat] -> (m, n_cols, nnz, h, f)."""
+    m, h, f = check_feats(X_row=X_row, **like_X)
+    n_cols = check_cols("X_row", X_row, X_col=X_col, V=V)
+    nnz = check_csr(X_row, m, row_ptr, col_ind)
+    if E is not None:
+        check_3d(X_row, nnz, h, f, E=E)
+    if G is not None:
+        check_3d(X_row, nnz, h, f, G=G)
+    return m, n_cols, nnz, h, f
+
+
+def _gatedgcn_fwd(what, save_den, need_Z, row_ptr, col_ind, X_row, X_col, V, E, normalize, eps):
+    ext = _n.ext()
+    if ext is not None:
+        return ext.gatedgcn_fwd(row_ptr, col_ind, X_row, X_col, V, E, bool(normalize), float(eps), save_den, bool(need_Z))
+    m, n_cols, nnz, h, f = _check_gatedgcn(row_ptr, col_ind, X_row, X_col, V, E)
+    out = torch.empty_like(X_row)
+    den = torch.empty_like(X_row) if save_den else None
+    Z = _empty(X_row, nnz, h, f) if need_Z else None
+    call("dfgnn_gatedgcn_fwd_rect", what, X_row.device, m, n_cols, nnz, h, f, row_ptr, col_ind, X_row, X_col, V, E,
+         int(bool(normalize)), float(eps), den, out, Z)
+    return [out] + ([den] if save_den else []) + ([Z] if need_Z else [])
+
+
+def gatedgcn_inference(row_ptr, col_ind, X_row, X_col, V, E=None, normalize=True, eps=1e-6, need_Z=False):
+    """-> out[m, h, f], or (out, Z[nnz, h, f]) with need_Z.  E fp32[nnz, h, f] in CSR edge order or None (no edge term);
+    X_row and X_col may be the same tensor.  normalize=False: the plain gated sum (PyG's ResGatedGraphConv)."""
+    res = _gatedgcn_fwd("gatedgcn_inference", False, need_Z, row_ptr, col_ind, X_row, X_col, V, E, normalize, eps)
+    return tuple(res) if need_Z else res[0]
+
+
+def gatedgcn_forward(row_ptr, col_ind, X_row, X_col, V, E=None, normalize=True, eps=1e-6, need_Z=False):
+    """-> (out, den[m, h, f], Z): the training forward; the same `out` and Z as gatedgcn_inference.  Z is None without
+    need_Z (then nothing of size nnz h f is allocated or written).  An empty row has out = 0, den = 0."""
+    res = _gatedgcn_fwd("gatedgcn_forward", True, need_Z, row_ptr, col_ind, X_row, X_col, V, E, normalize, eps)
+    return tuple(res) if need_Z else (res[0], res[1], None)
+
+
+def gatedgcn_backward(row_ptr, col_ind, col_ptr, row_ind, val_idx, X_row, X_col, V, E, out, den, grad, G=None,
+                      normalize=True, eps=1e-6, need_dE=True):
+    """-> (dX_row, dX_col, dV, dE[nnz, h, f]) from the forward's out and den (each edge is recomputed), the gradient `grad`
+    of out and the gradient G[nnz, h, f] of Z (None: zero, nothing of it is read); dE is None without need_dE (then nothing
+    of size nnz h f is allocated or written; the other three are the same bits).  normalize=False reads neither out nor den:
+    None is accepted for both."""
+    val_idx = as_int32(val_idx)
+    if not normalize:
+        out = den = None
+    ext = _n.ext()
+    if ext is not None:
+        res = ext.gatedgcn_bwd(row_ptr, col_ind, col_ptr, row_ind, val_idx, X_row, X_col, V, E, bool(normalize), float(eps),
+                               out, den, grad, G, bool(need_dE))
+        return tuple(res) if need_dE else tuple(res) + (None,)
+    if normalize and (out is None or den is None):
+        raise RuntimeError("out and den of the forward are required with normalize")
+    saved = {"out": out, "den": den} if normalize else {}
+    m, n_cols, nnz, h, f = _check_gatedgcn(row_ptr, col_ind, X_row, X_col, V, E, G, grad=grad, **saved)
+    check_csc_rect(X_row, n_cols, nnz, col_ptr, "X_col", row_ind=row_ind, val_idx=val_idx)
+    dX_row, dX_col, dV = torch.empty_like(X_row), torch.empty_like(X_col), torch.empty_like(V)
+    dE = _empty(X_row, nnz, h, f) if need_dE else None
+    ws = torch.empty_like(X_row) if normalize else None   # s_i = dO_i / (den_i + eps), CSR pass -> CSC pass
+    call("dfgnn_gatedgcn_bwd_rect", "gatedgcn_backward", X_row.device, m, n_cols, nnz, h, f, row_ptr, col_ind, col_ptr, row_ind,
+         val_idx, X_row, X_col, V, E, int(bool(normalize)), float(eps), out, den, grad, G, dX_row, dX_col, dV, dE, ws)
+    return dX_row, dX_col, dV, dE
+
+
 # ---- the CSR-taking inference variants ----------------------------------------------------------------------------------
 _VARIANTS = ("gt_tiling", "gt_csr", "gt_csr_gm", "gt_softmax", "gt_softmax_gm")   # by `which` of torch_ext.cpp: gt_variant_fwd
 

@@ -557,6 +557,56 @@ int dfgnn_agnn_bwd_rect(int m, int n_cols, int nnz, int h, int f, const int *row
                         const float *out, const float *row_max, const float *row_sum, const float *grad_out, float *delta,
                         float *dX_row, float *dX_col, float *dbeta_rows, dfgnn_stream_t stream);
 
+/* Residual gated graph convolution, GatedGCN (csrc/gatedgcn_train.hip): fused inference and training pair for ANY graph,
+ * no plan, no degree limit, any f.  The attention is per dimension: a sigmoid gate in place of a softmax over a logit.
+ * For edge e = (i, j), per head:
+ *   z_e   = (X_row[i] + X_col[j]) + E_e                     elementwise, [f]
+ *   sg_e  = 1 / (1 + exp(-z_e))                             finite for every finite z
+ *   den_i = sum_{e of row i} sg_e
+ *   out_i = sum_{e of row i} sg_e (.) V_j / (den_i + eps)   normalize = 1 (Dwivedi et al., GraphGPS; eps = 1e-6 there)
+ *   out_i = sum_{e of row i} sg_e (.) V_j                   normalize = 0 (PyG's ResGatedGraphConv)
+ *   Z_e   = z_e                                             the edge output: the next layer's edge features (optional)
+ * and, with dO = d loss / d out and G = d loss / d Z (optional, NULL = zero),
+ *   s_i   = dO_i / (den_i + eps)   (normalize = 0: dO_i)
+ *   dsg_e = s_i (.) (V_j - out_i)  (normalize = 0: s_i (.) V_j)
+ *   g_e   = dsg_e (.) sg_e (.) (1 - sg_e) + G_e
+ *   dX_row_i = sum_{e of row i} g_e    dX_col_j = sum_{e into j} g_e    dV_j = sum_{e into j} sg_e (.) s_i    dE_e = g_e
+ * Saved between forward and backward: out and den, fp32[m, h, f]; nothing of size nnz.  Both backward passes rebuild z_e
+ * and sg_e with the forward's expression and routine: the bits are the forward's.
+ *   X_row    fp32[m, h, f]; X_col, V fp32[n_cols, h, f] (square entries: n_cols = m).  X_row and X_col may be one pointer
+ *   E        fp32[nnz, h, f] in CSR edge order (the row of (edge e, head) starts at (e h + head) f), or NULL: no edge
+ *            term, the bits of E = zeros and nothing of it is read
+ *   den      fp32[m, h, f], or NULL in the forward: not wanted (inference).  Written in either mode
+ *   Z        fp32[nnz, h, f], every slot written by plain stores, or NULL: not wanted.  `out` and `den` are the same bits
+ *   G        fp32[nnz, h, f] or NULL: zero (the bits of G = zeros; nothing of it is read)
+ *   dE       fp32[nnz, h, f], every slot written, or NULL: not wanted.  Every other output is the same bits
+ *   out, den of the backward: the forward's.  normalize = 0 reads neither and accepts NULL for both
+ *   ws       caller scratch fp32[m, h, f] (16-byte aligned for the float4 path): the CSR pass leaves s_i there for the CSC
+ *            pass.  Required when normalize = 1 and m > 0; not touched when normalize = 0
+ *   val_idx  int32[nnz], the CSR position of each CSC entry; required by the backward when nnz > 0
+ * An empty row: out = 0, den = 0, dX_row = 0; an empty column: dX_col = dV = 0.  No edge values.  No atomics: every output
+ * is written in full by plain stores, the summation order is fixed, two calls give the same bits.  Nothing allocates or
+ * synchronises.  Return codes: DFGNN_E_BADARG for a negative size, a missing pointer, a normalize other than 0 / 1, a
+ * negative or non-finite eps, two of dX_row / dX_col / dV being one buffer; DFGNN_E_UNSUPPORTED for h > 65535 or f outside
+ * the compiled range; m == 0 or nnz == 0 reads no edge.  The square entries are the n_cols = m case of the *_rect ones
+ * (col_ptr int32[n_cols+1]; see dfgnn_gt_fwd_rowstats_rect): same kernels, same bits. */
+int dfgnn_gatedgcn_fwd(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *X_row,
+                       const float *X_col, const float *V, const float *E, int normalize, float eps, float *den, float *out,
+                       float *Z, dfgnn_stream_t stream);
+int dfgnn_gatedgcn_bwd(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const int *col_ptr,
+                       const int *row_ind, const int *val_idx, const float *X_row, const float *X_col, const float *V,
+                       const float *E, int normalize, float eps, const float *out, const float *den, const float *grad_out,
+                       const float *G, float *dX_row, float *dX_col, float *dV, float *dE, float *ws,
+                       dfgnn_stream_t stream);
+int dfgnn_gatedgcn_fwd_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind,
+                            const float *X_row, const float *X_col, const float *V, const float *E, int normalize, float eps,
+                            float *den, float *out, float *Z, dfgnn_stream_t stream);
+int dfgnn_gatedgcn_bwd_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind,
+                            const int *col_ptr, const int *row_ind, const int *val_idx, const float *X_row,
+                            const float *X_col, const float *V, const float *E, int normalize, float eps, const float *out,
+                            const float *den, const float *grad_out, const float *G, float *dX_row, float *dX_col, float *dV,
+                            float *dE, float *ws, dfgnn_stream_t stream);
+
 /* weights[256 i + c] = val[e] for the edge e from node i to the c-th node of i's range of the plan, 0 elsewhere:
  * dfgnn_plan_dense_weights_floats(m) = 256 m floats (device, 16-byte aligned), written by one memset + one kernel on
  * `stream`.  val: fp32[nnz] in CSR order.  Only the dense ranges of the plan are filled (dfgnn_gt_stats_applies == 1:
