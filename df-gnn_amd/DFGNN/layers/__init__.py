@@ -1,4 +1,5 @@
 from .AGNN import AGNNConv_beta, AGNNConv_forward  # noqa: F401
+from .GAT import GATConv_edge, GATConv_forward, index_ops_gat_edge  # noqa: F401
 from .GAT_DOT import DOTGATConv_forward  # noqa: F401
 from .GatedGCN import GatedGCNConv, index_ops_gatedgcn  # noqa: F401
 from .GATv2 import GATv2Conv_edge, GATv2Conv_forward, GATv2Conv_tiling, GATv2ConvDGL  # noqa: F401

@@ -18,7 +18,7 @@ from DFGNN.utils import sparse as dglsp
 from .AGNN import (AGNNConv_beta, AGNNConv_csr, AGNNConv_csr_gm, AGNNConv_hyper, AGNNConv_softmax, AGNNConv_softmax_gm,
                    AGNNConv_tiling)
 from .GAT_DOT import DOTGATConv_csr, DOTGATConv_forward, DOTGATConv_hyper, DOTGATConv_softmax
-from .GAT import (GATConv_dgNN, GATConv_hyper, GATConv_hyper_ablation, GATConv_hyper_recompute, GATConv_hyper_v2,
+from .GAT import (GATConv_dgNN, GATConv_edge_timing, GATConv_forward, GATConv_hyper, GATConv_hyper_ablation, GATConv_hyper_recompute, GATConv_hyper_v2,
                   GATConv_softmax, GATConv_softmax_gm, GATConv_tiling)
 from .GATv2 import GATv2Conv_edge_timing, GATv2Conv_forward, GATv2Conv_tiling
 from .GatedGCN import GatedGCNConv_plain_timing, GatedGCNConv_timing
@@ -140,6 +140,8 @@ _GAT_LAYERS = {
     "csr": GATConv_dgNN, "tiling": GATConv_tiling, "hyper": GATConv_hyper, "nofuse": GATConv_hyper,
     "softmax": GATConv_softmax, "softmax_gm": GATConv_softmax_gm,
     "hyper_v2": GATConv_hyper_v2, "hyper_recompute": GATConv_hyper_recompute, "hyper_ablation": GATConv_hyper_ablation,
+    "forward": GATConv_forward,  # this build's addition: the training layer on the any-graph fused pair
+    "forward_edge": GATConv_edge_timing,  # this build's addition: a per-edge attention term inside the LeakyReLU (seeded random here)
 }
 _AGNN_LAYERS = {  # reference :424-442
     "hyper": AGNNConv_hyper, "csr": AGNNConv_csr, "softmax": AGNNConv_softmax, "csr_gm": AGNNConv_csr_gm,

@@ -146,3 +146,46 @@ def GATv2ConvFuse_edge(attn, row_ptr, col_ind, col_ptr, row_ind, val_idx, negati
     """Differentiable GATv2 conv of any graph with the edge features fp32[nnz, h, f] (CSR edge order) inside the LeakyReLU;
     the argument list of GATv2ConvFuse plus `val_idx` (the CSR position of each CSC entry) and `E`."""
     return FusedGATv2Function_edge.apply(attn, row_ptr, col_ind, col_ptr, row_ind, val_idx, negative_slope, X_row, X_col, E)
+
+
+# ---- GAT of any graph with an optional per-edge attention term (fused_gatconv.gat_*_edge) ---------------------------------
+# logits LeakyReLU(attn_row[i] + attn_col[j] + score[h, e]) on an m x n_cols graph: in_feat fp32[n_cols, h, f] are the sources
+def GATConvFuse_inference_edge(attn_row, attn_col, row_ptr, col_ind, negative_slope, in_feat, score=None):
+    """-> out[m, h, f]; attn_row [m, heads], attn_col [n_cols, heads], score fp32[heads, nnz] in CSR edge order or None
+    (PyG's GATConv(edge_dim): the term is inside the LeakyReLU and not part of the message).  No dropout."""
+    return fused_gat.gat_inference_edge(attn_row, attn_col, row_ptr, col_ind, negative_slope, in_feat, score)
+
+
+class FusedGATFunction_edge(torch.autograd.Function):
+    """Training pair (include/dfgnn.h: dfgnn_gat_fwd_edge / dfgnn_gat_bwd_edge, csrc/gat_edge_train.hip): FusedGATFunction
+    for any graph, square or m x n_cols, with the optional edge term.  Saved between forward and backward: the inputs,
+    two floats per (row, head) and -- with dropout only -- the randoms [nnz, heads].  grad_score [heads, nnz] is computed only
+    when score requires a gradient; otherwise the backward allocates and writes nothing of that size."""
+
+    @staticmethod
+    def forward(ctx, attn_row, attn_col, row_ptr, col_ind, col_ptr, row_ind, val_idx, negative_slope, in_feat, attn_drop,
+                score):
+        out, edge_max, edge_sum, edge_mask = fused_gat.gat_forward_edge(attn_row, attn_col, row_ptr, col_ind, negative_slope,
+                                                                        in_feat, score, attn_drop)
+        ctx.save_for_backward(row_ptr, col_ind, col_ptr, row_ind, val_idx, attn_row, attn_col, in_feat, edge_max, edge_sum,
+                              score, edge_mask)
+        ctx.negative_slope, ctx.attn_drop = negative_slope, attn_drop
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (row_ptr, col_ind, col_ptr, row_ind, val_idx, attn_row, attn_col, in_feat, edge_max, edge_sum, score,
+         edge_mask) = ctx.saved_tensors
+        grad_feat, grad_attn_row, grad_attn_col, grad_score = fused_gat.gat_backward_edge(
+            ctx.negative_slope, ctx.attn_drop, row_ptr, col_ind, col_ptr, row_ind, val_idx, attn_row, attn_col, in_feat,
+            edge_max, edge_sum, grad_out.contiguous(), score=score, edge_mask=edge_mask,
+            want_grad_score=score is not None and ctx.needs_input_grad[10])
+        return grad_attn_row, grad_attn_col, None, None, None, None, None, None, grad_feat, None, grad_score
+
+
+def GATConvFuse_edge(attn_row, attn_col, row_ptr, col_ind, col_ptr, row_ind, val_idx, negative_slope, in_feat, attn_drop=0.0,
+                     score=None):
+    """Differentiable GAT conv of any graph; the argument list of GATConvFuse with `val_idx` (the CSR position of each CSC
+    entry; GATConvFuse calls it permute) and the optional edge term `score` fp32[heads, nnz] in CSR edge order."""
+    return FusedGATFunction_edge.apply(attn_row, attn_col, row_ptr, col_ind, col_ptr, row_ind, val_idx, negative_slope,
+                                       in_feat, attn_drop, score)

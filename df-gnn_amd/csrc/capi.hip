@@ -724,6 +724,56 @@ int dfgnn_gatedgcn_bwd(int m, int nnz, int h, int f, const int *row_ptr, const i
                                  eps, out, den, grad_out, G, dX_row, dX_col, dV, dE, ws, stream);
 }
 
+// ---- GAT for any graph with an optional per-edge attention term (gat_edge_train.hip) --------------------------------------
+int dfgnn_gat_fwd_edge_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind,
+                            const float *attn_row, const float *attn_col, float negative_slope, const float *score,
+                            const float *X, const float *edge_mask, float attn_drop, float *edge_max, float *edge_sum,
+                            float *out, dfgnn_stream_t stream) {
+  if (edge_mask && !(attn_drop >= 0.f && attn_drop < 1.f)) return kErrBadArg;
+  if (int c = check_rect(m, n_cols, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (m == 0) return 0;  // (no row: nothing to write)
+  if (!attn_row || !out || (n_cols > 0 && (!attn_col || !X)) || (!edge_max != !edge_sum)) return kErrBadArg;  // (both statistics or neither: inference)
+  const Csr g = rect_csr(m, n_cols, nnz, h, f, row_ptr, col_ind, nullptr);
+  return launch_gat_edge_fwd(g, GatEdgeTerms{attn_row, attn_col, negative_slope, score, edge_mask, attn_drop}, X, edge_max,
+                             edge_sum, out, as_stream(stream));
+}
+
+int dfgnn_gat_fwd_edge(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *attn_row,
+                       const float *attn_col, float negative_slope, const float *score, const float *X,
+                       const float *edge_mask, float attn_drop, float *edge_max, float *edge_sum, float *out,
+                       dfgnn_stream_t stream) {
+  return dfgnn_gat_fwd_edge_rect(m, m, nnz, h, f, row_ptr, col_ind, attn_row, attn_col, negative_slope, score, X, edge_mask,
+                                 attn_drop, edge_max, edge_sum, out, stream);
+}
+
+int dfgnn_gat_bwd_edge_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind,
+                            const int *col_ptr, const int *row_ind, const int *val_idx, const float *attn_row,
+                            const float *attn_col, float negative_slope, const float *score, const float *X,
+                            const float *edge_mask, float attn_drop, const float *edge_max, const float *edge_sum,
+                            const float *grad_out, float *delta, float *grad_feat, float *grad_attn_row,
+                            float *grad_attn_col, float *grad_score, dfgnn_stream_t stream) {
+  if (edge_mask && !(attn_drop >= 0.f && attn_drop < 1.f)) return kErrBadArg;
+  if (int c = check_rect(m, n_cols, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;
+  if (m > 0 && (!attn_row || !edge_max || !edge_sum || !grad_out || !delta || !grad_attn_row)) return kErrBadArg;
+  if (n_cols > 0 && (!attn_col || !X || !grad_feat || !grad_attn_col || !col_ptr)) return kErrBadArg;
+  if (nnz > 0 && !row_ind) return kErrBadArg;
+  if (nnz > 0 && (score || edge_mask) && !val_idx) return kErrBadArg;  // (the CSC pass finds an entry's score and random through val_idx)
+  const Csr g = rect_csr(m, n_cols, nnz, h, f, row_ptr, col_ind, nullptr);
+  return launch_gat_edge_bwd(g, GatEdgeTerms{attn_row, attn_col, negative_slope, score, edge_mask, attn_drop}, col_ptr,
+                             row_ind, val_idx, X, edge_max, edge_sum, grad_out, delta, grad_feat, grad_attn_row,
+                             grad_attn_col, grad_score, as_stream(stream));
+}
+
+int dfgnn_gat_bwd_edge(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const int *col_ptr,
+                       const int *row_ind, const int *val_idx, const float *attn_row, const float *attn_col,
+                       float negative_slope, const float *score, const float *X, const float *edge_mask, float attn_drop,
+                       const float *edge_max, const float *edge_sum, const float *grad_out, float *delta, float *grad_feat,
+                       float *grad_attn_row, float *grad_attn_col, float *grad_score, dfgnn_stream_t stream) {
+  return dfgnn_gat_bwd_edge_rect(m, m, nnz, h, f, row_ptr, col_ind, col_ptr, row_ind, val_idx, attn_row, attn_col,
+                                 negative_slope, score, X, edge_mask, attn_drop, edge_max, edge_sum, grad_out, delta,
+                                 grad_feat, grad_attn_row, grad_attn_col, grad_score, stream);
+}
+
 int dfgnn_gt_tiling_fwd(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *val,
                         const float *Q, const float *K, const float *V, float *out, dfgnn_stream_t stream) {
   if (int c = check_common(m, nnz, h, f, row_ptr, col_ind)) return c < 0 ? c : 0;

@@ -359,6 +359,24 @@ int launch_gatedgcn_fwd(const Csr &g, const GatedGcnGraph &v, const float *X_row
 int launch_gatedgcn_bwd(const Csr &g, const GatedGcnGraph &v, const float *X_row, const float *X_col, const float *V,
                         const float *E, const float *out, const float *den, const float *grad_out, const float *G,
                         float *dX_row, float *dX_col, float *dV, float *dE, float *ws, hipStream_t s);
+// GAT pair for any graph with an optional per-edge attention term (gat_edge_train.hip): no plan.  pre_e = (attn_row_i +
+// attn_col_j) + score[h, e], score [h, nnz] in CSR order (nullable: + 0.f); mask [nnz, h] uniform randoms (nullable: no
+// dropout).  The forward saves edge_max / edge_sum [m, h] (both nullable: inference); the backward is the CSR pass (delta
+// [m, h] summed over the edges -- the forward's out is not read --, grad_attn_row and, when it is not null, grad_score [h, nnz] in full) then the CSC pass (grad_feat, grad_attn_col),
+// on one stream.  The CSC pass reads val_idx only when score or mask is given.  Nothing of size nnz is handed over.
+struct GatEdgeTerms {
+  const float *attn_row, *attn_col;  // [m, h] / [n_cols, h]
+  float slope;
+  const float *score;                // [h, nnz]
+  const float *mask;                 // [nnz, h]
+  float attn_drop;
+};
+int launch_gat_edge_fwd(const Csr &g, const GatEdgeTerms &t, const float *X, float *edge_max, float *edge_sum, float *out,
+                        hipStream_t s);
+int launch_gat_edge_bwd(const Csr &g, const GatEdgeTerms &t, const int *col_ptr, const int *row_ind, const int *val_idx,
+                        const float *X, const float *edge_max, const float *edge_sum, const float *grad_out, float *delta,
+                        float *grad_feat, float *grad_attn_row, float *grad_attn_col,
+                        float *grad_score, hipStream_t s);
 // graphs with fewer than kBlockMinAvgDegree edges per row on average take the row-per-lane-group kernels.  The pairs that
 // take an m x n_cols graph ask per pass: (m, nnz) for the forward and the CSR pass, (n_cols, nnz) for the CSC pass
 inline bool low_degree(int m, int nnz) { return (long)nnz < (long)kBlockMinAvgDegree * m; }

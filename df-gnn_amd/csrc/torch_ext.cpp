@@ -1025,6 +1025,87 @@ std::vector<Tensor> gatedgcn_bwd(const Tensor &row_ptr, const Tensor &col_ind, c
   return {dX_row, dX_col, dV, dE};
 }
 
+// ---- GAT for any graph with an optional per-edge attention term (include/dfgnn.h: dfgnn_gat_fwd_edge / dfgnn_gat_bwd_edge) ----
+// an fp32 array of shape (a, b) or (a, b, c), with the text of the ctypes transport's check (_binding_util._family)
+void check_shape_f32(const Tensor &t, const char *name, std::initializer_list<int64_t> shape) {
+  check_cuda_contig(t, name);
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32, name, " must have dtype torch.float32, got ", py_dtype(t));
+  if (t.sizes() == c10::IntArrayRef(shape.begin(), shape.size())) return;
+  std::string want = "(";
+  for (auto it = shape.begin(); it != shape.end(); ++it) want += (it != shape.begin() ? ", " : "") + std::to_string(*it);
+  TORCH_CHECK(false, name, " must have shape ", want, "), got ", shape_str(t));
+}
+// What both entry points check: X fp32 [n_cols, heads, feat] (the sources), the CSR arrays of the m rows, the per-node scores
+// attn_row [m, h] / attn_col [n_cols, h], the optional score [h, nnz] and the dropout rate with its optional randoms
+Dims gat_edge_checks(const Tensor &attn_row, const Tensor &attn_col, const Tensor &row_ptr, const Tensor &col_ind,
+                     const c10::optional<Tensor> &score, const Tensor &X, double attn_drop,
+                     const c10::optional<Tensor> &edge_mask) {
+  check_f32(X, "X");
+  TORCH_CHECK(X.dim() == 3, "X must have shape [nodes, heads, feat], got ", shape_str(X));
+  check_i32(row_ptr, "indptr");
+  check_i32(col_ind, "indices");
+  TORCH_CHECK(row_ptr.dim() == 1 && col_ind.dim() == 1, "indptr / indices must be 1-D");
+  TORCH_CHECK(row_ptr.size(0) >= 1, "indptr must have at least one entry");
+  const Dims d{(int)(row_ptr.size(0) - 1), (int)col_ind.size(0), (int)X.size(1), (int)X.size(2), (int)X.size(0)};
+  check_shape_f32(attn_row, "attn_row", {d.m, d.h});
+  check_shape_f32(attn_col, "attn_col", {d.n_cols, d.h});
+  if (score) check_shape_f32(*score, "score", {d.h, d.nnz});
+  check_same_device(X, {&row_ptr, &col_ind, &attn_row, &attn_col, opt(score)});
+  TORCH_CHECK(attn_drop >= 0.0 && attn_drop < 1.0, "attn_drop must be in [0, 1), got ", attn_drop);
+  if (edge_mask) {
+    check_shape_f32(*edge_mask, "edge_mask", {d.nnz, d.h});
+    check_same_device(X, {&*edge_mask});
+  }
+  return d;
+}
+
+// save_stats = false: inference -> {out}; else the training forward -> {out, edge_max, edge_sum}
+std::vector<Tensor> gat_fwd_edge(const Tensor &attn_row, const Tensor &attn_col, const Tensor &row_ptr, const Tensor &col_ind,
+                                 double slope, const c10::optional<Tensor> &score, const Tensor &X,
+                                 const c10::optional<Tensor> &edge_mask, double attn_drop, bool save_stats) {
+  const Dims d = gat_edge_checks(attn_row, attn_col, row_ptr, col_ind, score, X, attn_drop, edge_mask);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
+  Tensor out = torch::empty({d.m, d.h, d.f}, X.options());
+  Tensor edge_max, edge_sum;
+  if (save_stats) {
+    edge_max = torch::empty({d.m, d.h}, X.options());
+    edge_sum = torch::empty({d.m, d.h}, X.options());
+  }
+  check_rc(dfgnn_gat_fwd_edge_rect(d.m, d.n_cols, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), f32(attn_row), f32(attn_col),
+                                   (float)slope, f32(score), f32(X), f32(edge_mask), (float)attn_drop, f32(edge_max),
+                                   f32(edge_sum), f32(out), cur_stream()),
+           save_stats ? "gat_forward_edge" : "gat_inference_edge");
+  if (!save_stats) return {out};
+  return {out, edge_max, edge_sum};
+}
+
+// -> {grad_feat, grad_attn_row, grad_attn_col, grad_score}, or the first three without want_grad_score
+std::vector<Tensor> gat_bwd_edge(double slope, double attn_drop, const Tensor &row_ptr, const Tensor &col_ind,
+                                 const Tensor &col_ptr, const Tensor &row_ind, const Tensor &val_idx, const Tensor &attn_row,
+                                 const Tensor &attn_col, const c10::optional<Tensor> &score, const Tensor &X,
+                                 const c10::optional<Tensor> &edge_mask, const Tensor &edge_max, const Tensor &edge_sum,
+                                 const Tensor &grad, bool want_grad_score) {
+  const Dims d = gat_edge_checks(attn_row, attn_col, row_ptr, col_ind, score, X, attn_drop, edge_mask);
+  csc_rect_checks(d, X, col_ptr, row_ind, &val_idx, "X");
+  check_shape_f32(grad, "grad", {d.m, d.h, d.f});
+  check_shape_f32(edge_max, "edge_max", {d.m, d.h});
+  check_shape_f32(edge_sum, "edge_sum", {d.m, d.h});
+  check_same_device(X, {&grad, &edge_max, &edge_sum});
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
+  Tensor delta = torch::empty({d.m, d.h}, X.options());
+  Tensor grad_feat = torch::empty_like(X);
+  Tensor grad_row = torch::empty({d.m, d.h}, X.options()), grad_col = torch::empty({d.n_cols, d.h}, X.options());
+  Tensor grad_score;
+  if (want_grad_score) grad_score = torch::empty({d.h, d.nnz}, X.options());
+  check_rc(dfgnn_gat_bwd_edge_rect(d.m, d.n_cols, d.nnz, d.h, d.f, i32(row_ptr), i32(col_ind), i32(col_ptr), i32(row_ind),
+                                   i32(val_idx), f32(attn_row), f32(attn_col), (float)slope, f32(score), f32(X), f32(edge_mask),
+                                   (float)attn_drop, f32(edge_max), f32(edge_sum), f32(grad), f32(delta),
+                                   f32(grad_feat), f32(grad_row), f32(grad_col), f32(grad_score), cur_stream()),
+           "gat_backward_edge");
+  if (!want_grad_score) return {grad_feat, grad_row, grad_col};
+  return {grad_feat, grad_row, grad_col, grad_score};
+}
+
 // fused_gtconv.cpp:244-276 (tiling), :174-242 (csr, csr_gm), :316-389 (softmax, softmax_gm): the GT inference variants that
 // take CSR (+ the COO rows for the two-kernel forms).  which: 0 tiling, 1 csr, 2 csr_gm, 3 softmax, 4 softmax_gm
 Tensor gt_variant_fwd(int64_t which, const Tensor &indptr, const Tensor &indices, const c10::optional<Tensor> &rows, const Tensor &val,
@@ -1139,6 +1220,8 @@ PYBIND11_MODULE(_dfgnn_ext, m) {
   m.def("agnn_bwd", &agnn_bwd, "fused AGNN / dot-product conv backward of any graph from the forward's output and row statistics");
   m.def("gatv2_fwd_edge", &gatv2_fwd_edge, "fused GATv2 conv forward of any graph with a per-edge feature vector inside the LeakyReLU");
   m.def("gatv2_bwd_edge", &gatv2_bwd_edge, "fused GATv2 conv backward of any graph with a per-edge feature vector inside the LeakyReLU");
+  m.def("gat_fwd_edge", &gat_fwd_edge, "fused GAT forward of any graph with an optional per-edge attention term (inference, or training with statistics)");
+  m.def("gat_bwd_edge", &gat_bwd_edge, "fused GAT backward of any graph from the forward's row statistics");
   m.def("gatedgcn_fwd", &gatedgcn_fwd, "fused GatedGCN conv forward of any graph (inference, or training with den; optional edge output)");
   m.def("gatedgcn_bwd", &gatedgcn_bwd, "fused GatedGCN conv backward of any graph from the forward's out and den");
   m.def("gt_variant_fwd", &gt_variant_fwd, "fused GT conv inference: tiling / csr / csr_gm / softmax / softmax_gm");

@@ -75,6 +75,10 @@ SIGNATURES = {
     "dfgnn_gatedgcn_bwd": [_i] * 4 + [_vp] * 9 + [_i, _f] + [_vp] * 10,
     "dfgnn_gatedgcn_fwd_rect": [_i] * 5 + [_vp] * 6 + [_i, _f] + [_vp] * 4,
     "dfgnn_gatedgcn_bwd_rect": [_i] * 5 + [_vp] * 9 + [_i, _f] + [_vp] * 10,
+    "dfgnn_gat_fwd_edge": [_i] * 4 + [_vp] * 4 + [_f] + [_vp] * 3 + [_f] + [_vp] * 4,
+    "dfgnn_gat_bwd_edge": [_i] * 4 + [_vp] * 7 + [_f] + [_vp] * 3 + [_f] + [_vp] * 9,
+    "dfgnn_gat_fwd_edge_rect": [_i] * 5 + [_vp] * 4 + [_f] + [_vp] * 3 + [_f] + [_vp] * 4,
+    "dfgnn_gat_bwd_edge_rect": [_i] * 5 + [_vp] * 7 + [_f] + [_vp] * 3 + [_f] + [_vp] * 9,
     "dfgnn_gt_bwd_rows": [_i, _i, _i, _i] + [_vp] * 11,
     "dfgnn_gt_bwd_cols": [_i, _i, _i, _i] + [_vp] * 11,
     "dfgnn_gt_tiling_fwd": [_i, _i, _i, _i] + [_vp] * 8,

@@ -390,3 +390,101 @@ def gatv2_backward_edge(negative_slope, row_ptr, col_ind, col_ptr, row_ind, val_
     call("dfgnn_gatv2_bwd_edge_rect", "gatv2_backward_edge", X_row.device, m, n_cols, nnz, h, f, row_ptr, col_ind, col_ptr, row_ind,
          val_idx, attn, float(negative_slope), X_row, X_col, E, out, row_max, row_sum, grad, delta, ws, dX_row, dX_col, dattn, dE)
     return [dX_row, dX_col, dattn, dE]
+
+
+# ---- GAT for any graph with an optional per-edge attention term (include/dfgnn.h: dfgnn_gat_fwd_edge / dfgnn_gat_bwd_edge) ------
+# Not part of the reference's module.  The logit of edge (i, j) is LeakyReLU(attn_row[i] + attn_col[j] + score[h, e]): the
+# rank-one GAT of gat_forward / gat_backward on an m x n_cols graph (csrc/gat_edge_train.hip), with what PyG's
+# GATConv(edge_dim) adds inside the LeakyReLU.  in_feat holds the SOURCES, fp32[n_cols, h, f]; attn_row is [m, h], attn_col
+# [n_cols, h]; score is fp32[h, nnz] in CSR edge order or None.  No plan, any f; nothing of size nnz is allocated beyond the
+# dropout randoms and, when wanted, grad_score.  DFGNN.operators.fused_gatconv.GATConvFuse_edge takes it.
+
+
+def _check_edge(attn_row, attn_col, row_ptr, col_ind, score, in_feat):
+    """What every operator of the pair checks -> (m, n_cols, nnz, h, f)."""
+    n_cols, h, f = check_feats(X=in_feat)
+    check_family(in_feat, torch.int32, indptr=row_ptr, indices=col_ind)
+    if row_ptr.dim() != 1 or col_ind.dim() != 1:
+        raise RuntimeError("indptr / indices must be 1-D")
+    if row_ptr.size(0) < 1:
+        raise RuntimeError("indptr must have at least one entry")
+    m, nnz = row_ptr.size(0) - 1, col_ind.size(0)
+    check_2d(in_feat, m, h, attn_row=attn_row)
+    check_2d(in_feat, n_cols, h, attn_col=attn_col)
+    if score is not None:
+        check_2d(in_feat, h, nnz, score=score)
+    return m, n_cols, nnz, h, f
+
+
+def _edge_mask(in_feat, nnz, h, attn_drop, edge_mask):
+    """The dropout randoms [nnz, h]: the caller's, or drawn here -- only when something is dropped."""
+    if edge_mask is None and attn_drop > 0.0:
+        edge_mask = torch.rand((nnz, h), dtype=torch.float32, device=in_feat.device)
+    return edge_mask
+
+
+def _gat_fwd_edge(what, save_stats, attn_row, attn_col, row_ptr, col_ind, negative_slope, in_feat, score, attn_drop, edge_mask):
+    ext = _n.ext()
+    if ext is not None and in_feat.dim() == 3 and in_feat.is_cuda and col_ind.dim() == 1:
+        attn_drop = float(attn_drop)
+        if 0.0 <= attn_drop < 1.0:   # (else: the extension's error, before any randoms are drawn)
+            edge_mask = _edge_mask(in_feat, col_ind.size(0), in_feat.size(1), attn_drop, edge_mask)
+        return ext.gat_fwd_edge(attn_row, attn_col, row_ptr, col_ind, float(negative_slope), score, in_feat, edge_mask,
+                                attn_drop, save_stats) + [edge_mask]
+    m, n_cols, nnz, h, f = _check_edge(attn_row, attn_col, row_ptr, col_ind, score, in_feat)
+    attn_drop = _drop(attn_drop)
+    edge_mask = _edge_mask(in_feat, nnz, h, attn_drop, edge_mask)
+    if edge_mask is not None:
+        check_2d(in_feat, nnz, h, edge_mask=edge_mask)
+    out = _empty(in_feat, m, h, f)
+    edge_max, edge_sum = (_empty(in_feat, m, h), _empty(in_feat, m, h)) if save_stats else (None, None)
+    call("dfgnn_gat_fwd_edge_rect", what, in_feat.device, m, n_cols, nnz, h, f, row_ptr, col_ind, attn_row, attn_col,
+         float(negative_slope), score, in_feat, edge_mask, attn_drop, edge_max, edge_sum, out)
+    return ([out, edge_max, edge_sum] if save_stats else [out]) + [edge_mask]
+
+
+def gat_inference_edge(attn_row, attn_col, row_ptr, col_ind, negative_slope, in_feat, score=None, attn_drop=0.0,
+                       edge_mask=None):
+    """-> out[m, h, f].  attn_drop > 0 drops edges here too (randoms from torch.rand unless edge_mask is given): the
+    training forward's `out`, bit for bit, without saving the statistics."""
+    return _gat_fwd_edge("gat_inference_edge", False, attn_row, attn_col, row_ptr, col_ind, negative_slope, in_feat, score,
+                         attn_drop, edge_mask)[0]
+
+
+def gat_forward_edge(attn_row, attn_col, row_ptr, col_ind, negative_slope, in_feat, score=None, attn_drop=0.0, edge_mask=None):
+    """-> [out[m, h, f], edge_max[m, h], edge_sum[m, h], edge_mask]: the training forward.  edge_mask holds the uniform
+    randoms [nnz, h] of the attention dropout -- the caller's, or drawn with torch.rand when attn_drop > 0 -- and is None
+    when there are none: no dropout, nothing of size nnz allocated.  A given edge_mask with attn_drop = 0 keeps every edge."""
+    return _gat_fwd_edge("gat_forward_edge", True, attn_row, attn_col, row_ptr, col_ind, negative_slope, in_feat, score,
+                         attn_drop, edge_mask)
+
+
+def gat_backward_edge(negative_slope, attn_drop, row_ptr, col_ind, col_ptr, row_ind, val_idx, attn_row, attn_col, in_feat,
+                      edge_max, edge_sum, grad, score=None, edge_mask=None, want_grad_score=True):
+    """-> [grad_feat[n_cols, h, f], grad_attn_row[m, h], grad_attn_col[n_cols, h], grad_score[h, nnz]] from the forward's
+    row statistics alone (each edge is recomputed; the forward's `out` is not needed); grad_score is None without want_grad_score (then nothing of size
+    nnz is allocated or written).  val_idx: the CSR position of each CSC entry, through which the column pass finds an
+    entry's score and random."""
+    if val_idx is None:
+        raise RuntimeError("gat_backward_edge: val_idx is required (the column pass finds an entry's score and random through it)")
+    val_idx = as_int32(val_idx)
+    want_grad_score = bool(want_grad_score)
+    ext = _n.ext()
+    if ext is not None and in_feat.dim() == 3 and in_feat.is_cuda:
+        res = ext.gat_bwd_edge(float(negative_slope), float(attn_drop), row_ptr, col_ind, col_ptr, row_ind, val_idx, attn_row,
+                               attn_col, score, in_feat, edge_mask, edge_max, edge_sum, grad, want_grad_score)
+        return res if want_grad_score else res + [None]
+    m, n_cols, nnz, h, f = _check_edge(attn_row, attn_col, row_ptr, col_ind, score, in_feat)
+    attn_drop = _drop(attn_drop)
+    if edge_mask is not None:
+        check_2d(in_feat, nnz, h, edge_mask=edge_mask)
+    check_csc_rect(in_feat, n_cols, nnz, col_ptr, "X", row_ind=row_ind, val_idx=val_idx)
+    check_3d(in_feat, m, h, f, grad=grad)
+    check_2d(in_feat, m, h, edge_max=edge_max, edge_sum=edge_sum)
+    delta, grad_feat = _empty(in_feat, m, h), torch.empty_like(in_feat)
+    grad_attn_row, grad_attn_col = _empty(in_feat, m, h), _empty(in_feat, n_cols, h)
+    grad_score = _empty(in_feat, h, nnz) if want_grad_score else None
+    call("dfgnn_gat_bwd_edge_rect", "gat_backward_edge", in_feat.device, m, n_cols, nnz, h, f, row_ptr, col_ind, col_ptr,
+         row_ind, val_idx, attn_row, attn_col, float(negative_slope), score, in_feat, edge_mask, attn_drop, edge_max, edge_sum,
+         grad, delta, grad_feat, grad_attn_row, grad_attn_col, grad_score)
+    return [grad_feat, grad_attn_row, grad_attn_col, grad_score]

@@ -607,6 +607,61 @@ int dfgnn_gatedgcn_bwd_rect(int m, int n_cols, int nnz, int h, int f, const int 
                             const float *den, const float *grad_out, const float *G, float *dX_row, float *dX_col, float *dV,
                             float *dE, float *ws, dfgnn_stream_t stream);
 
+/* GAT (v1) for ANY graph with an optional per-edge attention term (csrc/gat_edge_train.hip): fused inference and training
+ * pair, no plan, no degree limit, any f, square or m x n_cols.  Opt-in: dfgnn_gat_fwd_train / dfgnn_gat_bwd stay what the
+ * GAT layers use on dense batches.  For edge e = (row i, column j), per head (rows are the outputs, columns the sources):
+ *   pre_e = (attn_row[i] + attn_col[j]) + score[head, e]
+ *   s_e   = pre_e > 0 ? pre_e : negative_slope pre_e
+ *   P_e   = exp(s_e - edge_max_i) / edge_sum_i              statistics over ALL edges of the row, dropped or not
+ *   k_e   = edge_mask ? (edge_mask[e, head] > attn_drop) / (1 - attn_drop) : 1
+ *   out_i = sum_{e of row i} k_e P_e X[j]
+ * and, with dO = d loss / d out,
+ *   delta_i = <dO_i, out_i>     dS_e = P_e (k_e <dO_i, X[j]> - delta_i)     G_e = dS_e (pre_e > 0 ? 1 : negative_slope)
+ *   grad_attn_row[i] = sum_{e of row i} G_e    grad_attn_col[j] = sum_{e into j} G_e    grad_score[head, e] = G_e
+ *   grad_feat[j]     = sum_{e into j} k_e P_e dO_i
+ * Saved between forward and backward: edge_max, edge_sum (and the caller's edge_mask).  The CSR pass sums delta_i = sum_e k_e
+ * P_e <dO_i, X[j]> over the edges it walks anyway -- the forward's `out` is not an argument of the backward; summed this way
+ * delta carries the rounding of the dot products alone, which keeps rows of a few edges at fp32 level -- and hands only
+ * delta to the CSC pass, which recomputes <dO_i, X[j]> from the rows it gathers anyway.  Nothing else of size nnz exists.
+ *   attn_row, edge_max, edge_sum, delta, grad_attn_row   fp32[m, h]
+ *   attn_col, grad_attn_col                              fp32[n_cols, h]  (square entries: n_cols = m)
+ *   X, grad_feat                                         fp32[n_cols, h, f]: the message is the source's; no row-side features
+ *   out, grad_out                                        fp32[m, h, f]
+ *   score       fp32[h, nnz] in CSR edge order (the layout of bias in dfgnn_gt_fwd_bias), or NULL: no edge term, the bits of
+ *               score = zeros.  -inf masks an edge: P_e = 0, G_e = 0.  A (row, head) whose edges are all masked is an empty
+ *               row.  +inf and NaN are the caller's error
+ *   grad_score  fp32[h, nnz], every slot written by plain stores, or NULL: not wanted, every other output keeps its bits
+ *   edge_mask   fp32[nnz, h] uniform randoms with attn_drop in [0, 1) exactly as in dfgnn_gat_fwd_train, or NULL: no dropout
+ *               (attn_drop is then ignored).  A row whose edges are all dropped has out = 0 and finite gradients
+ *   edge_max, edge_sum of the forward: both NULL = inference
+ *   delta       caller scratch fp32[m, h], written by the backward
+ *   val_idx     int32[nnz], the CSR position of each CSC entry; required when nnz > 0 and score or edge_mask is given
+ * An empty row: out = 0, edge_max = -1e38, edge_sum = 0, grad_attn_row = 0, delta = 0; an empty column: grad_feat = 0,
+ * grad_attn_col = 0.  No atomics: every output is written in full by plain stores, the summation order is fixed, two calls
+ * give the same bits.  Nothing allocates or synchronises.  X / out (forward), X / grad_out / grad_feat (backward) 16-byte aligned with f % 4 == 0
+ * take the float4 path, anything else the scalar one (f <= 256).  Degenerate extents and return codes as for
+ * dfgnn_gt_fwd_rowstats_rect; DFGNN_E_BADARG also for an edge_mask with attn_drop outside [0, 1).  The square entries are
+ * the n_cols = m case of the *_rect ones: same kernels, same bits. */
+int dfgnn_gat_fwd_edge(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const float *attn_row,
+                       const float *attn_col, float negative_slope, const float *score, const float *X,
+                       const float *edge_mask, float attn_drop, float *edge_max, float *edge_sum, float *out,
+                       dfgnn_stream_t stream);
+int dfgnn_gat_bwd_edge(int m, int nnz, int h, int f, const int *row_ptr, const int *col_ind, const int *col_ptr,
+                       const int *row_ind, const int *val_idx, const float *attn_row, const float *attn_col,
+                       float negative_slope, const float *score, const float *X, const float *edge_mask, float attn_drop,
+                       const float *edge_max, const float *edge_sum, const float *grad_out, float *delta, float *grad_feat,
+                       float *grad_attn_row, float *grad_attn_col, float *grad_score, dfgnn_stream_t stream);
+int dfgnn_gat_fwd_edge_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind,
+                            const float *attn_row, const float *attn_col, float negative_slope, const float *score,
+                            const float *X, const float *edge_mask, float attn_drop, float *edge_max, float *edge_sum,
+                            float *out, dfgnn_stream_t stream);
+int dfgnn_gat_bwd_edge_rect(int m, int n_cols, int nnz, int h, int f, const int *row_ptr, const int *col_ind,
+                            const int *col_ptr, const int *row_ind, const int *val_idx, const float *attn_row,
+                            const float *attn_col, float negative_slope, const float *score, const float *X,
+                            const float *edge_mask, float attn_drop, const float *edge_max, const float *edge_sum,
+                            const float *grad_out, float *delta, float *grad_feat, float *grad_attn_row,
+                            float *grad_attn_col, float *grad_score, dfgnn_stream_t stream);
+
 /* weights[256 i + c] = val[e] for the edge e from node i to the c-th node of i's range of the plan, 0 elsewhere:
  * dfgnn_plan_dense_weights_floats(m) = 256 m floats (device, 16-byte aligned), written by one memset + one kernel on
  * `stream`.  val: fp32[nnz] in CSR order.  Only the dense ranges of the plan are filled (dfgnn_gt_stats_applies == 1:

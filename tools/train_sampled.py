@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Neighbour-sampled mini-batch training on the reddit-like stand-in: a 2-layer GT (--conv gatv2: GATv2) whose layers run
+"""Neighbour-sampled mini-batch training on the reddit-like stand-in: a 2-layer GT (--conv gatv2: GATv2, --conv gat: GAT on the any-graph pair) whose layers run
 on RECTANGULAR blocks (DFGNN.utils.graph.sample_block -> DFGNN.layers.preprocess_block -> the fused pairs that take an
 m x n_cols graph).  Each step: seeds, two sampled blocks, their preprocessing, forward, backward, Adam.  The same blocks
 go through the index-op branch of the layers every step (same weights, no gradient, outside the timed step); the last
@@ -12,7 +12,7 @@ Reported as separate JSON lines (medians over --repeats groups of --iters):
   conv_pairs      ms for forward + backward of the convolution operators alone on the two blocks of one step, three ways:
                   rect (this build's entries), padded_square (rows padded to n_cols, the square entry: the workaround
                   without rectangular support) and index_ops (torch index ops over the edge list)
-usage: python3 tools/train_sampled.py --scale 0.1 --fanout 10,25 --batch 1024 --heads 1 --dim 128 [--conv gatv2]"""
+usage: python3 tools/train_sampled.py --scale 0.1 --fanout 10,25 --batch 1024 --heads 1 --dim 128 [--conv gatv2|gat]"""
 import argparse
 import json
 import os
@@ -29,7 +29,7 @@ from torch import nn  # noqa: E402
 import dfgnn_preprocess  # noqa: E402
 import fused_gatconv  # noqa: E402
 import fused_gtconv  # noqa: E402
-from DFGNN.layers import GATv2Conv_forward, SparseMHA_rowstats, preprocess_block  # noqa: E402
+from DFGNN.layers import GATConv_forward, GATv2Conv_forward, SparseMHA_rowstats, index_ops_gat_edge, preprocess_block  # noqa: E402
 from DFGNN.layers.GT.gtconv_layer_bias import index_ops_mha_bias  # noqa: E402
 from DFGNN.utils import load_data_full_graph, sample_block  # noqa: E402
 
@@ -58,7 +58,8 @@ class Net(nn.Module):
     def __init__(self, conv, in_dim, dim, heads, classes):
         super().__init__()
         self.inproj = nn.Linear(in_dim, dim)
-        make = (lambda: GATv2Conv_forward(dim, dim // heads, heads)) if conv == "gatv2" else (lambda: _GTLayer(dim, dim, heads))
+        make = {"gatv2": lambda: GATv2Conv_forward(dim, dim // heads, heads), "gat": lambda: GATConv_forward(dim, dim // heads, heads),
+                "gt": lambda: _GTLayer(dim, dim, heads)}[conv]
         self.layers = nn.ModuleList(make() for _ in range(2))
         self.out = nn.Linear(dim, classes)
 
@@ -109,6 +110,22 @@ def block_jobs(conv, params, m, heads, f, gen):
     q_sq, dO_sq = pad(q), pad(dO)
     assert rp.numel() == m + 1 and rp_sq.numel() == n + 1 and int(rp[-1]) == nnz and int(ci.max()) < n and int(ri.max()) < m
     rows_l, ci_l = rows.long(), ci.long()
+    if conv == "gat":     # rect: the any-graph pair; padded_square: the existing (square) pair on the padded adjacency
+        ar, ac = r(m, heads), r(n, heads)
+        ar_sq = pad(ar)
+
+        def rect():
+            _, mx, sm, _ = fused_gatconv.gat_forward_edge(ar, ac, rp, ci, SLOPE, k)
+            fused_gatconv.gat_backward_edge(SLOPE, 0.0, rp, ci, cp, ri, vi, ar, ac, k, mx, sm, dO, want_grad_score=False)
+
+        def padded_square():
+            _, mx, sm, mask = fused_gatconv.gat_forward(ar_sq, ac, rp_sq, ci, SLOPE, k, 0.0)
+            fused_gatconv.gat_backward(SLOPE, 0.0, rp_sq, ci, cp, ri, vi, mx, sm, mask, k, ar_sq, ac, dO_sq)
+
+        def index_ops():
+            ar_, ac_, k_ = (t.clone().requires_grad_(True) for t in (ar, ac, k))
+            index_ops_gat_edge(rows, ci, ar_, ac_, SLOPE, k_).backward(dO)
+        return dict(rect=rect, padded_square=padded_square, index_ops=index_ops)
     if conv == "gatv2":
         attn = r(heads, f) * f ** -0.5
 
@@ -151,7 +168,7 @@ def conv_pairs(conv, blocks, heads, dim, iters, repeats):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=float, default=0.1)
-    ap.add_argument("--conv", default="gt", choices=["gt", "gatv2"])
+    ap.add_argument("--conv", default="gt", choices=["gt", "gatv2", "gat"])
     ap.add_argument("--fanout", default="10,25", help="per layer, input side first")
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--heads", type=int, default=1)
