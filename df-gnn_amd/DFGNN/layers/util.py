@@ -106,8 +106,15 @@ def preprocess_block(block, fused=True):
     """preprocess_Hyper_fw_bw for a rectangular graph (DFGNN.utils.graph.Block: num_rows x num_cols, edges() = (row, column)
     ids): the same 9-tuple, with A of shape (rows, cols), row_ptr of rows + 1 and col_ptr of cols + 1 entries -- what the
     layers on the pairs that take a rectangular graph (SparseMHA_rowstats / _bias / _edge, GATv2Conv_forward) expect next to
-    a pair of node features (h_cols, h_rows)."""
+    a pair of node features (h_cols, h_rows).  A DFGNN.utils.graph.SampledBlock (sample_block_fused) carries these arrays
+    already: they are handed on as they are, and A is built from its rows and col_ind."""
     shape = (block.num_rows(), block.num_cols())
+    if fused and getattr(block, "val_idx", None) is not None:
+        # a block of sample_block_fused carries the finished arrays: no kernel of the preprocessing and no sort
+        row, col = block.edges()      # rows / col_ind as int64
+        val = _unit_val(row.numel(), row.device)
+        return (dglsp.SparseMatrix(row, col, val, shape), block.rows, block.row_ptr, block.col_ind, val, block.col_ptr,
+                block.row_ind, block.val_idx, _round_up(128 * 8, WARP_SIZE))
     A, max_neigh = dglsp.spmatrix(torch.stack(block.edges()), shape=shape), 128
     if not fused:
         return A, None, None, None, None, None, None, None, None

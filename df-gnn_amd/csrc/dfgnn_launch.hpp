@@ -389,6 +389,13 @@ int launch_gat_tiling_fwd(const Csr &g, const float *attn_row, const float *attn
 int launch_gat_sddmm(const Csr &g, const float *attn_row, const float *attn_col, float slope, float *logits,
                      hipStream_t s);
 
+// the CSC half of the preprocessing on its own (preprocess.hip), for a caller that already holds the CSR list (sample.hip):
+// col_ptr [n_cols + 1], row_ind, val_idx [nnz] = a stable sort of the CSR list by column.  temp: rocPRIM storage of
+// csc_sort_temp_bytes(n_cols, nnz) bytes or more; sorted_cols: int[nnz] of scratch.  nnz > 0
+int csc_sort_temp_bytes(int n_cols, int nnz, size_t &bytes);
+int launch_csc_of_csr(int n_cols, int nnz, const int *col_ind, const int *rows, int *col_ptr, int *row_ind, int *val_idx,
+                      void *temp, size_t temp_bytes, int *sorted_cols, hipStream_t s);
+
 int launch_gat_attn_scores(int m, int h, int f, const float *a_l, const float *a_r, const float *X, float *attn_row,
                            float *attn_col, hipStream_t s);
 // GAT training pair (gat_train.hip).  rest != NULL: only the ranges of that plan which the matrix-core kernels do not

@@ -99,6 +99,28 @@ static int sort_temp_bytes(int m, int nnz, size_t &bytes) {
   return 0;
 }
 
+// The CSC half on its own, for a caller that already holds the CSR list (sample.hip): rocPRIM storage of the column sort of
+// nnz pairs with keys below n_cols
+int csc_sort_temp_bytes(int n_cols, int nnz, size_t &bytes) {
+  bytes = 0;
+  if (hipError_t rc = sort_pairs(nullptr, bytes, (const int *)nullptr, (int *)nullptr, rocprim::counting_iterator<int>(0),
+                                 (int *)nullptr, (unsigned)nnz, key_bits(n_cols), (hipStream_t) nullptr))
+    return (int)rc;
+  bytes = align256(bytes);
+  return 0;
+}
+
+// CSC: (column, CSR slot) sorted by column.  temp: temp_bytes of rocPRIM storage; sorted_cols: int[nnz] of scratch
+int launch_csc_of_csr(int n_cols, int nnz, const int *col_ind, const int *rows, int *col_ptr, int *row_ind, int *val_idx,
+                      void *temp, size_t temp_bytes, int *sorted_cols, hipStream_t s) {
+  if (hipError_t rc = sort_pairs(temp, temp_bytes, col_ind, sorted_cols, rocprim::counting_iterator<int>(0), val_idx,
+                                 (unsigned)nnz, key_bits(n_cols), s))
+    return (int)rc;
+  csr_pointers_kernel<<<n_cols / 256 + 1, 256, 0, s>>>(n_cols, nnz, sorted_cols, col_ptr);
+  gather_int_kernel<<<(nnz + 255) / 256, 256, 0, s>>>(nnz, rows, val_idx, row_ind);
+  return launch_status();
+}
+
 }  // namespace dfgnn
 
 using namespace dfgnn;
@@ -159,14 +181,7 @@ int dfgnn_preprocess_hyper_rect(int m, int n_cols, int nnz, const void *src, con
   if (int rc = launch_status()) return rc;
   if (!want_csc) return 0;
 
-  // CSC: (column, CSR slot) sorted by column
-  tb = temp;
-  if (hipError_t rc = sort_pairs(ws, tb, (const int *)col_ind, sorted_cols, rocprim::counting_iterator<int>(0), val_idx,
-                                 (unsigned)nnz, key_bits(n_cols), s))
-    return (int)rc;
-  csr_pointers_kernel<<<n_cols / 256 + 1, 256, 0, s>>>(n_cols, nnz, sorted_cols, col_ptr);
-  gather_int_kernel<<<eb, 256, 0, s>>>(nnz, rows, val_idx, row_ind);
-  return launch_status();
+  return launch_csc_of_csr(n_cols, nnz, col_ind, rows, col_ptr, row_ind, val_idx, ws, temp, sorted_cols, s);
 }
 
 int dfgnn_preprocess_hyper(int m, int nnz, const void *src, const void *dst, int idx64, int *row_ptr, int *col_ind,

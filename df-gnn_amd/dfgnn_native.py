@@ -97,6 +97,14 @@ SIGNATURES = {
     "dfgnn_gat_bwd": [_i, _i, _i, _i] + [_vp] * 8 + [_f] + [_vp] * 4 + [_f] + [_vp] * 8,
 }
 
+# the sampler's entries: include/dfgnn_sample.h one to one (checked by tests/test_sample_host.py); every one answers an int
+SAMPLE_SIGNATURES = {
+    "dfgnn_sample_abi_version": [],
+    "dfgnn_sample_ws_bytes": [_i, _i, _i, _vp],
+    "dfgnn_sample_select": [_i, _i, _i, ctypes.c_uint] + [_vp] * 6 + [ctypes.c_size_t, _vp],
+    "dfgnn_sample_emit": [_i] * 5 + [_vp] * 12 + [ctypes.c_size_t, _vp],
+}
+
 EXT_PATH = os.path.join(_HERE, "_dfgnn_ext.so")   # torch C++ extension over the same C ABI (csrc/torch_ext.cpp)
 
 _lib = None
@@ -149,7 +157,7 @@ def lib():
         # (no import order to respect: libdfgnn.so has no HIP dependency, libdfgnn_hip.so is opened by it at the first
         # call that needs the kernels -- csrc/gen_shim.py)
         L = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in SIGNATURES.items():
+        for name, argtypes in list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the library is stale
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int

@@ -1,18 +1,20 @@
 #!/usr/bin/env python3
 """Neighbour-sampled mini-batch training on the reddit-like stand-in: a 2-layer GT (--conv gatv2: GATv2, --conv gat: GAT on the any-graph pair) whose layers run
 on RECTANGULAR blocks (DFGNN.utils.graph.sample_block -> DFGNN.layers.preprocess_block -> the fused pairs that take an
-m x n_cols graph).  Each step: seeds, two sampled blocks, their preprocessing, forward, backward, Adam.  The same blocks
+m x n_cols graph; --sampler native: DFGNN.utils.graph.sample_block_fused, the native sampler of include/dfgnn_sample.h, whose
+blocks carry their CSR and CSC arrays, so that preprocess_block only hands them on).  Each step: seeds, two sampled blocks, their preprocessing, forward, backward, Adam.  The same blocks
 go through the index-op branch of the layers every step (same weights, no gradient, outside the timed step); the last
 step's two losses and the largest gap between the two over all steps are printed.
 
 Reported as separate JSON lines (medians over --repeats groups of --iters):
-  sampling        ms per step for the two sample_block calls
+  sampling        ms per step for the two sample_block (--sampler native: sample_block_fused) calls
   preprocessing   ms per step for the two preprocess_block calls
   step            ms per training step, fused, everything included
   conv_pairs      ms for forward + backward of the convolution operators alone on the two blocks of one step, three ways:
                   rect (this build's entries), padded_square (rows padded to n_cols, the square entry: the workaround
                   without rectangular support) and index_ops (torch index ops over the edge list)
-usage: python3 tools/train_sampled.py --scale 0.1 --fanout 10,25 --batch 1024 --heads 1 --dim 128 [--conv gatv2|gat]"""
+usage: python3 tools/train_sampled.py --scale 0.1 --fanout 10,25 --batch 1024 --heads 1 --dim 128 [--conv gatv2|gat]
+       [--sampler torch|native]"""
 import argparse
 import json
 import os
@@ -31,7 +33,7 @@ import fused_gatconv  # noqa: E402
 import fused_gtconv  # noqa: E402
 from DFGNN.layers import GATConv_forward, GATv2Conv_forward, SparseMHA_rowstats, index_ops_gat_edge, preprocess_block  # noqa: E402
 from DFGNN.layers.GT.gtconv_layer_bias import index_ops_mha_bias  # noqa: E402
-from DFGNN.utils import load_data_full_graph, sample_block  # noqa: E402
+from DFGNN.utils import load_data_full_graph, sample_block, sample_block_fused  # noqa: E402
 
 SLOPE = 0.2
 
@@ -70,11 +72,11 @@ class Net(nn.Module):
         return self.out(h)
 
 
-def sample(row_ptr, col_ind, seeds, fanouts, gen):
+def sample(row_ptr, col_ind, seeds, fanouts, gen, hop=sample_block):
     """-> [(block, rows)] outermost first, and the input nodes of the outermost block."""
     blocks, nodes = [], seeds
     for fanout in reversed(fanouts):
-        block, cols = sample_block(row_ptr, col_ind, nodes, fanout, gen)
+        block, cols = hop(row_ptr, col_ind, nodes, fanout, gen)
         blocks.insert(0, (block, nodes.numel()))
         nodes = cols
     return blocks, nodes
@@ -178,6 +180,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--sampler", default="torch", choices=["torch", "native"],
+                    help="torch: sample_block (torch ops, keys from the device generator); native: sample_block_fused")
     args = ap.parse_args()
     fanouts = [int(x) for x in args.fanout.split(",")]
     assert len(fanouts) == 2, "two layers: two fanouts"
@@ -193,7 +197,9 @@ def main():
     opt = torch.optim.Adam(model.parameters(), lr=1e-3)
     loss_fn = nn.CrossEntropyLoss()
     gen = torch.Generator(device=dev).manual_seed(2)
-    base = dict(tool="train_sampled", conv=args.conv, scale=args.scale, fanout=fanouts, batch=args.batch, heads=args.heads,
+    # the native sampler takes one 32-bit seed per hop: drawn on the CPU, no device work and no host read
+    hop, hop_gen = (sample_block_fused, torch.Generator().manual_seed(2)) if args.sampler == "native" else (sample_block, gen)
+    base = dict(tool="train_sampled", sampler=args.sampler, conv=args.conv, scale=args.scale, fanout=fanouts, batch=args.batch, heads=args.heads,
                 dim=args.dim, nodes=N, edges=g.num_edges())
     t_sample, t_prep, t_step, worst_gap = [], [], [], 0.0
 
@@ -204,7 +210,7 @@ def main():
     for step in range(args.warmup + args.steps):
         t0 = now()
         seeds = torch.randperm(N, device=dev, generator=gen)[:args.batch]
-        sampled, inputs = sample(row_ptr, col_ind, seeds, fanouts, gen)
+        sampled, inputs = sample(row_ptr, col_ind, seeds, fanouts, hop_gen, hop)
         t1 = now()
         blocks = [(preprocess_block(b), m) for b, m in sampled]
         t2 = now()
