@@ -1,0 +1,55 @@
+"""The global half of a GraphGPS-style layer: multi-head attention of every node over all nodes of its own graph in a
+batch (DFGNN/operators/fused_gtconv.py: SegmentMHAFuse, csrc/segment_mha.hip).  The nodes are ordered by graph; the only
+structure is the graphs' sizes."""
+import torch
+import torch.nn as nn
+
+import fused_gtconv as fused_gt
+from DFGNN.operators.fused_gtconv import SegmentMHAFuse
+
+
+def segment_offsets(segments, device):
+    """seg_ptr int32[n_seg + 1] on `device` from what a caller has: an int32 tensor on the device IS a seg_ptr (passed through
+    without a host read, so that the bounds cached on it are found again and the call can be captured); anything else is
+    the graphs' sizes (Graph.batch_num_nodes(): int64)."""
+    segments = torch.as_tensor(segments)
+    if segments.dtype == torch.int32 and segments.device == device:
+        return segments
+    sizes = segments.to(torch.int64)
+    seg_ptr = torch.zeros(sizes.numel() + 1, dtype=torch.int32)
+    seg_ptr[1:] = torch.cumsum(sizes.cpu(), 0)
+    return seg_ptr.to(device)
+
+
+class GlobalMHA(nn.Module):
+    """out = W_o concat_heads(softmax_graph(scale Q K^T) V), the softmax of a node running over its own graph's nodes."""
+
+    def __init__(self, in_size, out_size, num_heads):
+        super().__init__()
+        self.num_heads = num_heads
+        self.head_dim = out_size // num_heads
+        self.scaling = self.head_dim ** -0.5
+        self.q_proj = nn.Linear(in_size, out_size)
+        self.k_proj = nn.Linear(in_size, out_size)
+        self.v_proj = nn.Linear(in_size, out_size)
+        self.out_proj = nn.Linear(out_size, out_size)
+
+    def forward(self, h, seg_ptr, fuse=True):
+        """h [N, in]; seg_ptr: int32[n_seg + 1] offsets (a tensor kept across layers and steps is looked up, not rebuilt) or
+        the batch's graph sizes.  fuse=False, or a head shape the fused pair does not serve: plain torch, graph by graph."""
+        seg_ptr = segment_offsets(seg_ptr, h.device)
+        n = len(h)
+        q, k, v = (p(h).reshape(n, self.num_heads, self.head_dim) for p in (self.q_proj, self.k_proj, self.v_proj))
+        if fuse and h.is_cuda and fused_gt.segment_mha_applies(self.num_heads, self.head_dim):
+            out = SegmentMHAFuse(seg_ptr, q.contiguous(), k.contiguous(), v.contiguous(), self.scaling)
+        else:
+            out = self.forward_plain(seg_ptr, q, k, v)
+        return self.out_proj(out.reshape(n, -1))
+
+    def forward_plain(self, seg_ptr, q, k, v):
+        outs = []
+        ends = seg_ptr.tolist()
+        for lo, hi in zip(ends[:-1], ends[1:]):
+            s = torch.einsum("ihf,jhf->hij", q[lo:hi], k[lo:hi]) * self.scaling
+            outs.append(torch.einsum("hij,jhf->ihf", torch.softmax(s, dim=-1), v[lo:hi]))
+        return torch.cat(outs) if outs else torch.empty_like(q)

@@ -102,6 +102,34 @@ def GTConvFuse_rowstats(rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, 
         rows, row_ptr, col_ind, val, col_ptr, row_ind, val_idx, smem_consume, Q, K, V)
 
 
+# ---- global attention over batched graphs (include/dfgnn_segment.h; fused_gtconv.segment_mha_*) -------------------------
+class FusedSegmentMHAFunction(torch.autograd.Function):
+    """Multi-head attention of every node over the nodes of its own graph.  Saved between forward and backward: Q, K, V,
+    out and the row statistics [m, h] -- nothing of size n^2."""
+
+    @staticmethod
+    def forward(ctx, bounds, Q, K, V, scale):
+        out, row_max, row_sum = fused_gt.segment_mha_forward(bounds, Q, K, V, scale)
+        ctx.save_for_backward(bounds, Q, K, V, out, row_max, row_sum)
+        ctx.scale = scale
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        bounds, Q, K, V, out, row_max, row_sum = ctx.saved_tensors
+        dQ, dK, dV = fused_gt.segment_mha_backward(bounds, Q, K, V, out, row_max, row_sum, grad_out.contiguous(), ctx.scale)
+        return None, dQ, dK, dV, None
+
+
+def SegmentMHAFuse(seg_ptr, Q, K, V, scale=1.0):
+    """Differentiable global attention: Q, K, V fp32 [m, h, f] with the nodes ordered by graph, seg_ptr int32[n_seg + 1]
+    the graphs' offsets -> out [m, h, f].  Without a gradient to compute, the inference forward (no statistics)."""
+    bounds = fused_gt.segment_bounds(seg_ptr, Q.size(0))
+    if not (torch.is_grad_enabled() and (Q.requires_grad or K.requires_grad or V.requires_grad)):
+        return fused_gt.segment_mha_inference(bounds, Q, K, V, scale)
+    return FusedSegmentMHAFunction.apply(bounds, Q, K, V, scale)
+
+
 # ---- AGNN / dot-product attention with tied keys and values (this build's addition; fused_gtconv.agnn_*) -----------------
 def AGNNConvFuse_inference(row_ptr, col_ind, beta, X_row, X_col, cosine=True):
     """-> out[m, h, f] = softmax_j(beta[h] cos(X_row_i, X_col_j)) X_col_j (cosine=False: beta[h] <X_row_i, X_col_j>); beta

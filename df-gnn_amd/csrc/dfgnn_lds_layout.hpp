@@ -55,7 +55,19 @@ DFGNN_LAYOUT_FN int image_at(int rs, int rows, int row, int feat, int half, bool
   return half * rows * rs + image_row(row, kswap) * rs + feat;
 }
 
-static_assert(tile_at(136, 16 + 5, 32 + 12, 1) == tile_at(136, 5, 12, 1) + 16 * 272 + 32, "tile_at is periodic");
+// ---- segment attention (dfgnn_segment.hpp): height of a staged tile ---------------------------------------------------
+// A tile is two matrices (K and V, or Q and dO) of `rows` rows as hi / lo images, plus `row_words` dwords per row of
+// staged per-row values.  Bytes of one, and the tallest of 128 / 64 / 32 / 16 rows that fits `budget` bytes next to
+// `fixed` bytes and stays within rows * f <= cap_elems -- the register side of the choice: the staged tile travels
+// through rows * f / 256 VGPRs and its logits live in rows / 4 more, per product.
+DFGNN_LAYOUT_FN int segment_tile_bytes(int f, int rows, int row_words) { return rows * (4 * image_rs(f) * 2 + 4 * row_words); }
+DFGNN_LAYOUT_FN int segment_tile_rows(int f, int row_words, int fixed, int budget, int cap_elems) {
+  int rows = 128;
+  while (rows > 16 && (fixed + segment_tile_bytes(f, rows, row_words) > budget || rows * f > cap_elems)) rows /= 2;
+  return rows;
+}
+
+static_assert(tile_at(136, 16 + 5, 32 + 12, 1) ==tile_at(136, 5, 12, 1) + 16 * 272 + 32, "tile_at is periodic");
 static_assert(image_at(144, 128, 32 + 9, 20, 0, true) == image_at(144, 128, 9, 20, 0, true) + 32 * 144, "image_at is periodic");
 
 }  // namespace dfgnn

@@ -1,0 +1,427 @@
+// dfgnn_segment.hpp -- kernel bodies of the segment multi-head attention pair (segment_mha.hip, include/dfgnn_segment.h):
+// every node attends to all nodes of its own graph in a batch, the "global" half of a GraphGPS-style layer.
+//
+// Flash-style on the matrix cores, with the numerics and operand layouts of dfgnn_dense.hpp (power-of-two-scaled fp16
+// hi / lo halves, three MFMAs per product, fp32 accumulation).  The three kernels are ONE shape:
+//   * a work item is an aligned 128-row window of the node array and one head; wave w owns the 16-row strip w, whose rows
+//     of one or two matrices stay in registers as hi / lo operands for the whole item (SegRows);
+//   * the item walks the contiguous node range its rows can see -- lo of the first row to hi of the last -- in tiles of TR
+//     rows of two other matrices, staged as hi / lo images while the next tile's loads are in flight (seg_tile_loop);
+//   * per tile, D^T = Image . Rows^T leaves a row of the strip on 4 lanes (dense_rows_mma), the mask lo_i <= j < hi_i
+//     comes from two registers per row, and the result is the B operand of the second product (dense_cols_mma).
+//              strip rows   register rows   images      first products          second products
+//   forward    queries      Q               K, V        S^T = K Q^T             O^T  += V^T P^T
+//   dQ         queries      Q, dO           K, V        S^T, dP^T = V dO^T      dQ^T += K^T dS^T   (after a pass for t, below)
+//   dK / dV    keys         K, V            Q, dO       S = Q K^T, dP = dO V^T  dV^T += dO^T P,  dK^T += Q^T dS
+// The dK / dV kernel is the forward turned round: with the KEYS on the register side the accumulators of S and dP are
+// already the B operands of dO^T P and Q^T dS, so P and dS never leave the registers (no LDS tile, no third barrier) and
+// every key row is summed by one wave in a fixed order: no atomics.  It takes the row statistics, delta and the bounds
+// of a tile's query rows from LDS, staged with the images.
+//
+// Every image has its own power-of-two scale, and dS a per-wave one.  A second product therefore goes into a zeroed
+// accumulator and is added to the running one in fp32 under the product of the inverse scales: one rounding per tile
+// and element, an fp32 FMA chain.  (Rescaling the running accumulator to the new tile's units instead overflows when a
+// tile of dO or dS is all zero and its scale the largest normal one.)
+//
+// delta_i = sum_j P_ij dP_ij is formed from P and dP themselves, never from the stored `out` row; a
+// row's keys may straddle two tiles however small its graph is, so the dQ kernel walks the keys twice: the first pass
+// accumulates t_i in registers, the second forms dS = P (dP - t) and dQ.  See DESIGN.md 3.3k.
+#pragma once
+#include "dfgnn_dense.hpp"
+#include "dfgnn_launch.hpp"
+
+namespace dfgnn {
+
+constexpr int kSegWindow = kDenseWaves * 16;  // rows of a work item: one 16-row strip per wave
+constexpr int kSegFixedLds = 2 * kDenseWaves * 4;  // the two workgroup-maximum slots
+
+// FR: the real width (16 runs zero-padded on the 32-wide layout, as in dfgnn_dense_fwd.hpp); ROW_WORDS: staged dwords
+// per tile row (dK / dV: row_max, 1 / row_sum, delta, lo, hi); CAP: rows * f the registers allow (dfgnn_lds_layout.hpp);
+// MAXR: rows at most (dK / dV: 64 -- with 128 the narrow heads' S, dP and staged row values spill)
+template <int FR, int ROW_WORDS, int CAP, int MAXR = 128>
+struct SegCfg {
+  static constexpr int F = FR < 32 ? 32 : FR;
+  static constexpr int RS = DenseCfg<F>::RS, KT = DenseCfg<F>::KT, FT = DenseCfg<F>::FT;
+  static constexpr int TR0 = segment_tile_rows(F, ROW_WORDS, kSegFixedLds, kBlockLdsBudget, CAP), TR = TR0 < MAXR ? TR0 : MAXR;
+  static constexpr int NT = TR / 16, PLANE = TR * RS;
+  static constexpr int kLds = kSegFixedLds + segment_tile_bytes(F, TR, ROW_WORDS);
+  static_assert(TR % 32 == 0 && kLds <= kBlockLdsBudget, "a tile is whole 32-row k-blocks inside the LDS budget");
+};
+constexpr int kSegCapFwd = 8192, kSegCapBwd = 4096;
+template <int FR> using SegFwdCfg = SegCfg<FR, 0, kSegCapFwd>;
+template <int FR> using SegDqCfg = SegCfg<FR, 0, kSegCapBwd>;
+template <int FR> using SegDkvCfg = SegCfg<FR, 5, kSegCapBwd, 64>;
+
+struct SegImages {
+  const h16 *ahi, *alo, *bhi, *blo;
+  float ainv, binv;  // 1 / scale of the two resident images
+  float *rows;       // the staged per-row values, ROW_WORDS arrays of TR
+};
+
+// 16 rows of a matrix as the register operand of dense_rows_mma: lane (mi, mq) holds row `row`, features 32 t + 8 mq ..
+template <int FR>
+struct SegRows {
+  static constexpr int KT = (FR < 32 ? 32 : FR) / 32;
+  hx8 h[KT], l[KT];
+  float inv;
+};
+template <int FR>
+__device__ __forceinline__ void seg_rows_load(SegRows<FR> &x, const float *__restrict__ base, unsigned hf, int row, int m,
+                                              const LaneIds &L) {
+  constexpr int F = FR < 32 ? 32 : FR, KT = F / 32;
+  const unsigned off = (unsigned)min(row, m - 1) * hf;
+  float4 a[KT], b[KT];
+  float am = 0.f;
+#pragma unroll
+  for (int t = 0; t < KT; ++t) {
+    const bool in = FR == F || 32 * t + 8 * L.mq < FR;
+    const unsigned c = in ? 32u * t + 8u * L.mq : 0u;
+    a[t] = ld32_f4(base, off + c);
+    b[t] = ld32_f4(base, off + c + 4);
+    if (row >= m || !in) a[t] = b[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+    am = fmaxf(am, absmax8(a[t], b[t]));
+  }
+  const Pow2Scale s = pow2_scale(wave_max(am));
+  x.inv = s.inv;
+#pragma unroll
+  for (int t = 0; t < KT; ++t) split_hx8(a[t], b[t], s.s, x.h[t], x.l[t]);
+}
+
+// Rows [t0, t1) of A and B (row 0 at the pointers, row stride hf) in tiles of TR rows: fn(t, images) runs with rows
+// t .. t + TR - 1 resident (rows at or past t1 are zero).  xload(t) issues a tile's further loads, xstore(rows) puts them
+// into LDS next to the images.  Everything here is workgroup-uniform; fn may leave early per wave.
+template <class C, class XL, class XS, class Fn>
+__device__ __forceinline__ void seg_tile_loop(float *lds, const float *__restrict__ A, const float *__restrict__ B,
+                                              unsigned hf, int t0, int t1, int fr, XL &&xload, XS &&xstore, Fn &&fn) {
+  constexpr int F = C::F, TR = C::TR;
+  if (t0 >= t1) return;
+  float *smax = lds;
+  h16 *ahi = reinterpret_cast<h16 *>(lds + 2 * kDenseWaves), *alo = ahi + C::PLANE, *bhi = alo + C::PLANE, *blo = bhi + C::PLANE;
+  float *rows = reinterpret_cast<float *>(blo + C::PLANE);
+  DenseStageRegs<F, TR> sa, sb;
+  dense_stage_load<F, TR>(sa, A, hf, t0, t1, fr);
+  dense_stage_load<F, TR>(sb, B, hf, t0, t1, fr);
+  xload(t0);
+  for (int t = t0; t < t1; t += TR) {
+    wg_max_post(smax, dense_stage_absmax<F, TR>(sa));
+    wg_max_post(smax + kDenseWaves, dense_stage_absmax<F, TR>(sb));
+    lds_barrier();  // every wave is done with the previous tile
+    const Pow2Scale pa = pow2_scale(wg_max_read(smax)), pb = pow2_scale(wg_max_read(smax + kDenseWaves));
+    dense_stage_store<F, TR>(sa, ahi, alo, pa.s, fr);
+    dense_stage_store<F, TR>(sb, bhi, blo, pb.s, fr);
+    xstore(rows);
+    if (t + TR < t1) {
+      dense_stage_load<F, TR>(sa, A, hf, t + TR, t1, fr);
+      dense_stage_load<F, TR>(sb, B, hf, t + TR, t1, fr);
+      xload(t + TR);
+    }
+    lds_barrier();
+    fn(t, SegImages{ahi, alo, bhi, blo, pa.inv, pb.inv, rows});
+  }
+}
+
+// What a strip knows of itself: its rows, their bounds, and the node range any of them can see (wave-uniform).
+struct SegStrip {
+  int row, lo, hi;       // this lane's row (absolute) and its bounds; a row at or past m sees nothing
+  int vis_lo, vis_hi;    // lo of the strip's first row, hi of its last: uniform
+  bool live;             // the strip has a row below m: uniform
+  // rows [a, a + len) of a tile can be seen by some row of the strip
+  __device__ __forceinline__ bool sees(int a, int len) const { return live && a < vis_hi && a + len > vis_lo; }
+};
+__device__ __forceinline__ SegStrip seg_strip(const int *__restrict__ bounds, int m, int w0, const LaneIds &L) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int s0 = w0 + 16 * wave;
+  SegStrip s;
+  s.live = s0 < m;
+  s.row = s0 + L.mi;
+  const int rc = min(s.row, m - 1);
+  s.lo = s.row < m ? bounds[2 * rc] : 0;
+  s.hi = s.row < m ? bounds[2 * rc + 1] : 0;
+  s.vis_lo = __builtin_amdgcn_readfirstlane(bounds[2 * min(s0, m - 1)]);
+  s.vis_hi = __builtin_amdgcn_readfirstlane(bounds[2 * min(s0 + 15, m - 1) + 1]);
+  return s;
+}
+
+// accumulator tiles of a strip -> its global rows (whole lines; the padded width tile by tile)
+template <int FR, int FT>
+__device__ __forceinline__ void seg_store(const f32x4 (&acc)[FT], float scale, float *__restrict__ base, unsigned hf,
+                                          const SegStrip &s, int m, const LaneIds &L) {
+  if (!s.live) return;
+  if constexpr (FR >= 32) dense_store_rows<FT>(acc, scale, base, hf, s.row, m, L);
+  else if (s.row < m) dense_store_acc<FT, true>(acc, scale, base, (unsigned)s.row * hf + 4u * L.mq, false, 4 * L.mq, FR);
+}
+
+// dense_cols_mma for the NFT feature tiles from tile ft0 on
+template <int F, int NFT>
+__device__ __forceinline__ void seg_cols_mma(f32x4 (&acc)[NFT], const h16 *ihi, const h16 *ilo, int jb, int ft0, const f32x4 &y0,
+                                             const f32x4 &y1, float yscale, const LaneIds &L) {
+  constexpr int RS = DenseCfg<F>::RS;
+  hx8 yh, yl;
+  dense_split8(y0, y1, yscale, yh, yl);
+  dense_kblock_mma<16 * NFT>(acc, ihi, ilo, (32 * jb + 4 * L.mq + L.tq) * RS + 4 * L.tp + 16 * ft0, 16 * RS, yh, yl);
+}
+
+// ---- forward ----------------------------------------------------------------------------------------------------------
+template <int FR>
+__device__ __forceinline__ void segment_fwd_body(float *lds, int m, int h, float scale, const int *__restrict__ bounds,
+                                                 const float *__restrict__ Q, const float *__restrict__ K,
+                                                 const float *__restrict__ V, float *__restrict__ out,
+                                                 float *__restrict__ row_max, float *__restrict__ row_sum) {
+  using C = SegFwdCfg<FR>;
+  constexpr int F = C::F, FT = C::FT, NT = C::NT, TR = C::TR;
+  const int head = blockIdx.y, w0 = blockIdx.x * kSegWindow;
+  const unsigned hf = (unsigned)h * FR, hoff = (unsigned)head * FR;
+  const int t0 = bounds[2 * w0], t1 = bounds[2 * min(w0 + kSegWindow - 1, m - 1) + 1];
+  const LaneIds L = lane_ids();
+  const SegStrip st = seg_strip(bounds, m, w0, L);
+  SegRows<FR> q;
+  seg_rows_load<FR>(q, Q + hoff, hf, st.row, m, L);
+  float mrun = -INFINITY, lrun = 0.f;
+  f32x4 o[FT];
+#pragma unroll
+  for (int ft = 0; ft < FT; ++ft) o[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  seg_tile_loop<C>(lds, K + hoff, V + hoff, hf, t0, t1, FR, [](int) {}, [](float *) {}, [&](int t, const SegImages &im) {
+    if (!st.sees(t, TR)) return;  // (wave-uniform: staging and barriers stay with seg_tile_loop)
+    const LaneIds L = lane_ids();
+    f32x4 S[NT];
+    const float c = im.ainv * q.inv * scale;
+    float mx = -INFINITY;
+#pragma unroll
+    for (int jt = 0; jt < NT; ++jt) {
+      const bool seen = st.sees(t + 16 * jt, 16);
+      S[jt] = seen ? dense_rows_mma<F>(im.ahi, im.alo, jt, q.h, q.l, L) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int j = t + 16 * jt + 4 * L.mq + r;
+        const float x = (seen && j >= st.lo && j < st.hi) ? S[jt][r] * c : -INFINITY;
+        S[jt][r] = x;
+        mx = fmaxf(mx, x);
+      }
+    }
+    // online softmax: the running maximum and sum of the row, the accumulators rescaled only when the maximum moved
+    const float mnew = fmaxf(mrun, xor16_32_max(mx));
+    const float base = (mnew == -INFINITY) ? 0.f : mnew;
+    const float alpha = fast_exp(mrun - base);
+    float sum = 0.f;
+#pragma unroll
+    for (int jt = 0; jt < NT; ++jt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float p = fast_exp(S[jt][r] - base);  // exp(-inf) = 0 for the masked pairs
+        S[jt][r] = p;
+        sum += p;
+      }
+    lrun = lrun * alpha + xor16_32_sum(sum);
+    mrun = mnew;
+    if (__builtin_amdgcn_ballot_w64(alpha != 1.f)) {
+#pragma unroll
+      for (int ft = 0; ft < FT; ++ft) o[ft] *= alpha;
+    }
+    f32x4 tile[FT];
+#pragma unroll
+    for (int ft = 0; ft < FT; ++ft) tile[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int jb = 0; jb < TR / 32; ++jb)
+      if (st.sees(t + 32 * jb, 32)) dense_cols_mma<F>(tile, im.bhi, im.blo, jb, S[2 * jb], S[2 * jb + 1], kUnitScale, L);
+    const float u = im.binv * kUnitScaleInv;
+#pragma unroll
+    for (int ft = 0; ft < FT; ++ft) o[ft] += tile[ft] * u;
+  });
+
+  seg_store<FR, FT>(o, lrun > 0.f ? 1.f / lrun : 0.f, out + hoff, hf, st, m, L);
+  if (row_max && st.row < m && L.mq == 0) {
+    row_max[(size_t)st.row * h + head] = (mrun == -INFINITY) ? -1e38f : mrun;
+    row_sum[(size_t)st.row * h + head] = lrun;
+  }
+}
+
+// P of this strip against the resident K tile, from the rows' saved statistics; masked pairs are 0
+template <class C, int FR>
+__device__ __forceinline__ void seg_recompute_p(f32x4 (&S)[C::NT], f32x4 (&dP)[C::NT], const SegImages &im, int t,
+                                                const SegStrip &st, const SegRows<FR> &q, const SegRows<FR> &g, float scale,
+                                                float mx, float il, const LaneIds &L) {
+  const float c = im.ainv * q.inv * scale, cd = im.binv * g.inv;
+#pragma unroll
+  for (int jt = 0; jt < C::NT; ++jt) {
+    const bool seen = st.sees(t + 16 * jt, 16);
+    S[jt] = seen ? dense_rows_mma<C::F>(im.ahi, im.alo, jt, q.h, q.l, L) : f32x4{0.f, 0.f, 0.f, 0.f};
+    dP[jt] = seen ? dense_rows_mma<C::F>(im.bhi, im.blo, jt, g.h, g.l, L) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int j = t + 16 * jt + 4 * L.mq + r;
+      const float e = fast_exp(S[jt][r] * c - mx) * il;
+      S[jt][r] = (seen && j >= st.lo && j < st.hi) ? e : 0.f;
+      dP[jt][r] *= cd;
+    }
+  }
+}
+
+// ---- dQ (and delta) ---------------------------------------------------------------------------------------------------
+template <int FR>
+__device__ __forceinline__ void segment_dq_body(float *lds, int m, int h, float scale, const int *__restrict__ bounds,
+                                                const float *__restrict__ Q, const float *__restrict__ K,
+                                                const float *__restrict__ V, const float *__restrict__ row_max,
+                                                const float *__restrict__ row_sum, const float *__restrict__ dO,
+                                                float *__restrict__ dQ, float *__restrict__ delta) {
+  using C = SegDqCfg<FR>;
+  constexpr int F = C::F, FT = C::FT, NT = C::NT, TR = C::TR;
+  const int head = blockIdx.y, w0 = blockIdx.x * kSegWindow;
+  const unsigned hf = (unsigned)h * FR, hoff = (unsigned)head * FR;
+  const int t0 = bounds[2 * w0], t1 = bounds[2 * min(w0 + kSegWindow - 1, m - 1) + 1];
+  const LaneIds L = lane_ids();
+  const SegStrip st = seg_strip(bounds, m, w0, L);
+  SegRows<FR> q, g;
+  seg_rows_load<FR>(q, Q + hoff, hf, st.row, m, L);
+  seg_rows_load<FR>(g, dO + hoff, hf, st.row, m, L);
+  const size_t si = (size_t)min(st.row, m - 1) * h + head;
+  const float mx = row_max[si], rs = row_sum[si], il = rs > 0.f ? 1.f / rs : 0.f;
+
+  float tsum = 0.f;  // pass 1: t_i = sum_j P_ij dP_ij
+  seg_tile_loop<C>(lds, K + hoff, V + hoff, hf, t0, t1, FR, [](int) {}, [](float *) {}, [&](int t, const SegImages &im) {
+    if (!st.sees(t, TR)) return;
+    const LaneIds L = lane_ids();
+    f32x4 S[NT], dP[NT];
+    seg_recompute_p<C, FR>(S, dP, im, t, st, q, g, scale, mx, il, L);
+#pragma unroll
+    for (int jt = 0; jt < NT; ++jt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) tsum = fmaf(S[jt][r], dP[jt][r], tsum);
+  });
+  const float dl = xor16_32_sum(tsum);
+  if (st.row < m && L.mq == 0) delta[si] = dl;
+
+  f32x4 dq[FT];  // pass 2: dS = P (dP - t), dQ += dS K
+#pragma unroll
+  for (int ft = 0; ft < FT; ++ft) dq[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
+  seg_tile_loop<C>(lds, K + hoff, V + hoff, hf, t0, t1, FR, [](int) {}, [](float *) {}, [&](int t, const SegImages &im) {
+    if (!st.sees(t, TR)) return;
+    const LaneIds L = lane_ids();
+    f32x4 S[NT], dP[NT];
+    seg_recompute_p<C, FR>(S, dP, im, t, st, q, g, scale, mx, il, L);
+    float am = 0.f;
+#pragma unroll
+    for (int jt = 0; jt < NT; ++jt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        S[jt][r] *= dP[jt][r] - dl;
+        am = fmaxf(am, fabsf(S[jt][r]));
+      }
+    const Pow2Scale ds = pow2_scale(wave_max(am));
+    f32x4 tile[FT];
+#pragma unroll
+    for (int ft = 0; ft < FT; ++ft) tile[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int jb = 0; jb < TR / 32; ++jb)
+      if (st.sees(t + 32 * jb, 32)) dense_cols_mma<F>(tile, im.ahi, im.alo, jb, S[2 * jb], S[2 * jb + 1], ds.s, L);
+    const float u = im.ainv * ds.inv;
+#pragma unroll
+    for (int ft = 0; ft < FT; ++ft) dq[ft] += tile[ft] * u;
+  });
+  seg_store<FR, FT>(dq, scale, dQ + hoff, hf, st, m, L);
+}
+
+// ---- dK, dV -----------------------------------------------------------------------------------------------------------
+template <int FR>
+__device__ __forceinline__ void segment_dkv_body(float *lds, int m, int h, float scale, const int *__restrict__ bounds,
+                                                 const float *__restrict__ Q, const float *__restrict__ K,
+                                                 const float *__restrict__ V, const float *__restrict__ row_max,
+                                                 const float *__restrict__ row_sum, const float *__restrict__ dO,
+                                                 const float *__restrict__ delta, float *__restrict__ dK,
+                                                 float *__restrict__ dV) {
+  using C = SegDkvCfg<FR>;
+  constexpr int F = C::F, FT = C::FT, NT = C::NT, TR = C::TR;
+  const int head = blockIdx.y, w0 = blockIdx.x * kSegWindow;
+  const unsigned hf = (unsigned)h * FR, hoff = (unsigned)head * FR;
+  // the queries that see this window's keys: the graphs of its first and last key (a node's bounds are its graph)
+  const int t0 = bounds[2 * w0], t1 = bounds[2 * min(w0 + kSegWindow - 1, m - 1) + 1];
+  const LaneIds L = lane_ids();
+  const SegStrip st = seg_strip(bounds, m, w0, L);  // (strip rows are keys here)
+  SegRows<FR> k, v;
+  seg_rows_load<FR>(k, K + hoff, hf, st.row, m, L);
+  seg_rows_load<FR>(v, V + hoff, hf, st.row, m, L);
+  f32x4 dk[FT], dv[FT];
+#pragma unroll
+  for (int ft = 0; ft < FT; ++ft) dk[ft] = dv[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  float xm = 0.f, xs = 0.f, xd = 0.f;  // a tile row's statistics, delta and bounds on their way to LDS (threads < TR)
+  int xlo = 0, xhi = 0;
+  auto xload = [&](int t) {
+    const int tid = opaque_tid();
+    if (tid < TR) {
+      const int i = min(t + tid, t1 - 1);
+      const size_t si = (size_t)i * h + head;
+      xm = row_max[si];
+      xs = row_sum[si];
+      xd = delta[si];
+      xlo = t + tid < t1 ? bounds[2 * i] : 0;  // a row past the range sees nothing
+      xhi = t + tid < t1 ? bounds[2 * i + 1] : 0;
+    }
+  };
+  auto xstore = [&](float *rows) {
+    const int tid = opaque_tid();
+    if (tid < TR) {
+      rows[tid] = xm;
+      rows[TR + tid] = xs > 0.f ? 1.f / xs : 0.f;
+      rows[2 * TR + tid] = xd;
+      reinterpret_cast<int *>(rows)[3 * TR + tid] = xlo;
+      reinterpret_cast<int *>(rows)[4 * TR + tid] = xhi;
+    }
+  };
+  seg_tile_loop<C>(lds, Q + hoff, dO + hoff, hf, t0, t1, FR, xload, xstore, [&](int t, const SegImages &im) {
+    if (!st.sees(t, TR)) return;
+    const LaneIds L = lane_ids();
+    f32x4 S[NT], dP[NT];
+    const float c = im.ainv * k.inv * scale, cd = im.binv * v.inv;
+    const int j = st.row;  // this lane's key; its values of tile u belong to the queries t + 16 u + 4 mq + r
+    float am = 0.f;
+#pragma unroll
+    for (int u = 0; u < NT; ++u) {
+      const bool seen = st.sees(t + 16 * u, 16);
+      S[u] = seen ? dense_rows_mma<F>(im.ahi, im.alo, u, k.h, k.l, L) : f32x4{0.f, 0.f, 0.f, 0.f};
+      dP[u] = seen ? dense_rows_mma<F>(im.bhi, im.blo, u, v.h, v.l, L) : f32x4{0.f, 0.f, 0.f, 0.f};
+      const int at = 16 * u + 4 * L.mq;
+      const float4 mx = *reinterpret_cast<const float4 *>(im.rows + at), il = *reinterpret_cast<const float4 *>(im.rows + TR + at),
+                   dl = *reinterpret_cast<const float4 *>(im.rows + 2 * TR + at);
+      const int4 lo = *reinterpret_cast<const int4 *>(im.rows + 3 * TR + at), hi = *reinterpret_cast<const int4 *>(im.rows + 4 * TR + at);
+      const float mxr[4] = {mx.x, mx.y, mx.z, mx.w}, ilr[4] = {il.x, il.y, il.z, il.w}, dlr[4] = {dl.x, dl.y, dl.z, dl.w};
+      const int lor[4] = {lo.x, lo.y, lo.z, lo.w}, hir[4] = {hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float e = fast_exp(S[u][r] * c - mxr[r]) * ilr[r];
+        const float p = (seen && j >= lor[r] && j < hir[r]) ? e : 0.f;
+        const float ds = p * (dP[u][r] * cd - dlr[r]);
+        S[u][r] = p;
+        dP[u][r] = ds;
+        am = fmaxf(am, fabsf(ds));
+      }
+    }
+    const Pow2Scale dsc = pow2_scale(wave_max(am));
+    const float uv = im.binv * kUnitScaleInv, uk = im.ainv * dsc.inv;
+    // the widest head takes the feature tiles in two halves: dk, dv and a whole tile[] next to the K and V operands do not fit
+    constexpr int PARTS = F == 128 ? 2 : 1, PT = FT / PARTS;
+#pragma unroll
+    for (int part = 0; part < PARTS; ++part) {
+      f32x4 tile[PT];
+#pragma unroll
+      for (int k = 0; k < PT; ++k) tile[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ib = 0; ib < TR / 32; ++ib)
+        if (st.sees(t + 32 * ib, 32)) seg_cols_mma<F, PT>(tile, im.bhi, im.blo, ib, part * PT, S[2 * ib], S[2 * ib + 1], kUnitScale, L);
+#pragma unroll
+      for (int k = 0; k < PT; ++k) {
+        dv[part * PT + k] += tile[k] * uv;
+        tile[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+#pragma unroll
+      for (int ib = 0; ib < TR / 32; ++ib)
+        if (st.sees(t + 32 * ib, 32)) seg_cols_mma<F, PT>(tile, im.ahi, im.alo, ib, part * PT, dP[2 * ib], dP[2 * ib + 1], dsc.s, L);
+#pragma unroll
+      for (int k = 0; k < PT; ++k) dk[part * PT + k] += tile[k] * uk;
+    }
+  });
+  seg_store<FR, FT>(dv, 1.f, dV + hoff, hf, st, m, L);
+  seg_store<FR, FT>(dk, scale, dK + hoff, hf, st, m, L);
+}
+
+}  // namespace dfgnn

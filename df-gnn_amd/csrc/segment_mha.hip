@@ -1,0 +1,138 @@
+// segment_mha.hip -- multi-head attention of every node over the nodes of its own graph in a batch: the C entries of
+// include/dfgnn_segment.h.  The kernel bodies and the design are in dfgnn_segment.hpp.
+//
+// The whole structure of the problem is seg_ptr [n_seg + 1].  dfgnn_segment_bounds turns it into (lo, hi) per node once
+// per batch; every layer, head and direction reads that.  Grids follow from m alone -- ceil(m / 128) windows x h heads --
+// so nothing here reads the device from the host, allocates or synchronises: the calls can be captured in a HIP graph.
+#include <hip/hip_runtime.h>
+
+#include "../../include/dfgnn_segment.h"
+#include "dfgnn_segment.hpp"
+
+namespace dfgnn {
+
+// one thread per node: the last segment that starts at or before it (empty segments in front of it share that start and
+// are passed over), clamped into [0, m] so that no later kernel forms an address from an unchecked seg_ptr
+__global__ void segment_bounds_kernel(int m, int n_seg, const int *__restrict__ seg_ptr, int *__restrict__ bounds) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  int a = 0, b = n_seg - 1;  // seg_ptr[a] <= i (seg_ptr[0] = 0); the answer lies in [a, b]
+  while (a < b) {
+    const int mid = (a + b + 1) >> 1;
+    if (seg_ptr[mid] <= i) a = mid;
+    else b = mid - 1;
+  }
+  bounds[2 * i] = min(max(seg_ptr[a], 0), m);
+  bounds[2 * i + 1] = min(max(seg_ptr[a + 1], 0), m);
+}
+
+template <int FR>
+__global__ __launch_bounds__(kDenseThreads) void segment_mha_fwd_kernel(int m, int h, float scale, const int *__restrict__ bounds,
+                                                                        const float *__restrict__ Q, const float *__restrict__ K,
+                                                                        const float *__restrict__ V, float *__restrict__ out,
+                                                                        float *__restrict__ row_max, float *__restrict__ row_sum) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  segment_fwd_body<FR>(lds, m, h, scale, bounds, Q, K, V, out, row_max, row_sum);
+}
+
+template <int FR>
+__global__ __launch_bounds__(kDenseThreads) void segment_mha_dq_kernel(int m, int h, float scale, const int *__restrict__ bounds,
+                                                                       const float *__restrict__ Q, const float *__restrict__ K,
+                                                                       const float *__restrict__ V,
+                                                                       const float *__restrict__ row_max,
+                                                                       const float *__restrict__ row_sum,
+                                                                       const float *__restrict__ dO, float *__restrict__ dQ,
+                                                                       float *__restrict__ delta) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  segment_dq_body<FR>(lds, m, h, scale, bounds, Q, K, V, row_max, row_sum, dO, dQ, delta);
+}
+
+template <int FR>
+__global__ __launch_bounds__(kDenseThreads) void segment_mha_dkv_kernel(int m, int h, float scale, const int *__restrict__ bounds,
+                                                                        const float *__restrict__ Q, const float *__restrict__ K,
+                                                                        const float *__restrict__ V,
+                                                                        const float *__restrict__ row_max,
+                                                                        const float *__restrict__ row_sum,
+                                                                        const float *__restrict__ dO,
+                                                                        const float *__restrict__ delta, float *__restrict__ dK,
+                                                                        float *__restrict__ dV) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  segment_dkv_body<FR>(lds, m, h, scale, bounds, Q, K, V, row_max, row_sum, dO, delta, dK, dV);
+}
+
+static bool segment_width_ok(int f) { return f == 16 || f == 32 || f == 64 || f == 128; }
+
+// extents first, then the limits: the kernels address feature rows with 32-bit byte offsets, heads are the grid's y
+static int segment_check(int m, int h, int f) {
+  if (m < 0 || h < 1 || f < 1) return kErrBadArg;
+  if (!segment_width_ok(f) || h > 65535) return kErrUnsupported;
+  if ((unsigned long long)m * (unsigned)h * (unsigned)f * 4ull >= (1ull << 32)) return kErrUnsupported;
+  return 0;
+}
+
+template <class Fn>
+static int dispatch_segment(int f, Fn &&fn) {
+  if (f == 16) return fn(std::integral_constant<int, 16>{});
+  if (f == 32) return fn(std::integral_constant<int, 32>{});
+  if (f == 64) return fn(std::integral_constant<int, 64>{});
+  if (f == 128) return fn(std::integral_constant<int, 128>{});
+  return kErrUnsupported;
+}
+
+}  // namespace dfgnn
+
+using namespace dfgnn;
+
+extern "C" {
+
+int dfgnn_segment_abi_version(void) { return DFGNN_SEGMENT_ABI_VERSION; }
+
+int dfgnn_segment_mha_applies(int h, int f) { return (h >= 1 && h <= 65535 && segment_width_ok(f)) ? 1 : 0; }
+
+int dfgnn_segment_bounds(int m, int n_seg, const int *seg_ptr, int *bounds, dfgnn_stream_t stream) {
+  if (m < 0 || n_seg < 0 || (m > 0 && n_seg == 0)) return kErrBadArg;  // a node needs a segment
+  if (m >= (1 << 30)) return kErrUnsupported;                           // (2 m ints)
+  if (m == 0) return 0;
+  if (!seg_ptr || !bounds) return kErrBadArg;
+  segment_bounds_kernel<<<(m + 255) / 256, 256, 0, reinterpret_cast<hipStream_t>(stream)>>>(m, n_seg, seg_ptr, bounds);
+  return launch_status();
+}
+
+int dfgnn_segment_mha_fwd(int m, int h, int f, float scale, const int *bounds, const float *Q, const float *K, const float *V,
+                          float *out, float *row_max, float *row_sum, dfgnn_stream_t stream) {
+  if (int rc = segment_check(m, h, f)) return rc;
+  if ((row_max == nullptr) != (row_sum == nullptr)) return kErrBadArg;
+  if (m == 0) return 0;
+  if (!bounds || !Q || !K || !V || !out) return kErrBadArg;
+  const dim3 grid((m + kSegWindow - 1) / kSegWindow, h);
+  return dispatch_segment(f, [&](auto fc) {
+    constexpr int FR = decltype(fc)::value;
+    if (int rc = set_max_lds_cached(segment_mha_fwd_kernel<FR>)) return rc;
+    segment_mha_fwd_kernel<FR><<<grid, kDenseThreads, SegFwdCfg<FR>::kLds, reinterpret_cast<hipStream_t>(stream)>>>(
+        m, h, scale, bounds, Q, K, V, out, row_max, row_sum);
+    return launch_status();
+  });
+}
+
+int dfgnn_segment_mha_bwd(int m, int h, int f, float scale, const int *bounds, const float *Q, const float *K, const float *V,
+                          const float *out, const float *row_max, const float *row_sum, const float *dO, float *dQ, float *dK,
+                          float *dV, float *delta, dfgnn_stream_t stream) {
+  (void)out;  // (delta comes from P and dP, not from the stored rows: dfgnn_segment.hpp)
+  if (int rc = segment_check(m, h, f)) return rc;
+  if (m == 0) return 0;
+  if (!bounds || !Q || !K || !V || !row_max || !row_sum || !dO || !dQ || !dK || !dV || !delta) return kErrBadArg;
+  const dim3 grid((m + kSegWindow - 1) / kSegWindow, h);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  return dispatch_segment(f, [&](auto fc) {
+    constexpr int FR = decltype(fc)::value;
+    if (int rc = set_max_lds_cached(segment_mha_dq_kernel<FR>)) return rc;
+    if (int rc = set_max_lds_cached(segment_mha_dkv_kernel<FR>)) return rc;
+    segment_mha_dq_kernel<FR><<<grid, kDenseThreads, SegDqCfg<FR>::kLds, s>>>(m, h, scale, bounds, Q, K, V, row_max,
+                                                                                          row_sum, dO, dQ, delta);
+    segment_mha_dkv_kernel<FR><<<grid, kDenseThreads, SegDkvCfg<FR>::kLds, s>>>(m, h, scale, bounds, Q, K, V, row_max,
+                                                                                           row_sum, dO, delta, dK, dV);
+    return launch_status();
+  });
+}
+
+}  // extern "C"

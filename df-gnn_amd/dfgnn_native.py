@@ -105,6 +105,15 @@ SAMPLE_SIGNATURES = {
     "dfgnn_sample_emit": [_i] * 5 + [_vp] * 12 + [ctypes.c_size_t, _vp],
 }
 
+# the segment attention pair: include/dfgnn_segment.h one to one (checked by tests/test_segment_host.py); all answer an int
+SEGMENT_SIGNATURES = {
+    "dfgnn_segment_abi_version": [],
+    "dfgnn_segment_mha_applies": [_i, _i],
+    "dfgnn_segment_bounds": [_i, _i] + [_vp] * 3,
+    "dfgnn_segment_mha_fwd": [_i, _i, _i, _f] + [_vp] * 8,
+    "dfgnn_segment_mha_bwd": [_i, _i, _i, _f] + [_vp] * 13,
+}
+
 EXT_PATH = os.path.join(_HERE, "_dfgnn_ext.so")   # torch C++ extension over the same C ABI (csrc/torch_ext.cpp)
 
 _lib = None
@@ -157,7 +166,7 @@ def lib():
         # (no import order to respect: libdfgnn.so has no HIP dependency, libdfgnn_hip.so is opened by it at the first
         # call that needs the kernels -- csrc/gen_shim.py)
         L = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()):
+        for name, argtypes in list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(SEGMENT_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the library is stale
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int

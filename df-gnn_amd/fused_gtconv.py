@@ -15,7 +15,7 @@ import torch
 import dfgnn_native as _n
 import os
 
-from _binding_util import (as_int32, call, check_2d, check_3d, check_cols, check_csc, check_csc_rect, check_csr, check_edges,
+from _binding_util import (_family, _KeyedCache, as_int32, call, check_2d, check_3d, check_cols, check_csc, check_csc_rect, check_csr, check_edges,
                            check_family, check_feats, get_plan_obj, plan_dense_weights, plan_ptrs, val_ptr)
 
 # Set to False to force the general (plan-less) kernels; results are identical either way.
@@ -774,8 +774,67 @@ def gatedgcn_backward(row_ptr, col_ind, col_ptr, row_ind, val_idx, X_row, X_col,
     return dX_row, dX_col, dV, dE
 
 
+# ---- global attention over batched graphs (include/dfgnn_segment.h, csrc/segment_mha.hip) --------------------------------
+# Not part of the reference's module.  Every node attends to all nodes of its own graph; the structure is seg_ptr
+# int32[n_seg + 1] (the prefix sums of the batch's graph sizes), turned into per-node (lo, hi) once per batch.  ctypes
+# transport only.  DFGNN.operators.fused_gtconv.SegmentMHAFuse / DFGNN.layers.GlobalMHA take it.
+_bounds_cache = _KeyedCache()
+
+
+def segment_mha_applies(h, f):
+    """dfgnn_segment_mha_applies: the fused pair serves `h` heads of `f` features (host-only)."""
+    return bool(_n.lib().dfgnn_segment_mha_applies(int(h), int(f)))
+
+
+def segment_bounds(seg_ptr, m):
+    """-> bounds int32[2 m]: (lo, hi) of every node's segment, built once per seg_ptr tensor and cached."""
+    check_family(seg_ptr, torch.int32, seg_ptr=seg_ptr)
+    if seg_ptr.dim() != 1 or seg_ptr.numel() < 1:
+        raise RuntimeError(f"seg_ptr must have shape (n_seg + 1,), got {tuple(seg_ptr.shape)}")
+    key = _KeyedCache.key_of(seg_ptr, extra=(m,))
+    bounds = _bounds_cache.get(key)
+    if bounds is None:
+        bounds = torch.empty(2 * m, dtype=torch.int32, device=seg_ptr.device)
+        call("dfgnn_segment_bounds", "segment_bounds", seg_ptr.device, m, seg_ptr.numel() - 1, seg_ptr, bounds)
+        _bounds_cache.put(key, bounds, seg_ptr)
+    return bounds
+
+
+def _segment_checks(bounds, Q, K, V, **like_Q):
+    m, h, f = check_feats(Q=Q, K=K, V=V, **like_Q)
+    _family(Q, torch.int32, (2 * m,), {"bounds": bounds})
+    return m, h, f
+
+
+def segment_mha_inference(bounds, Q, K, V, scale=1.0):
+    """-> out [m, h, f]; no statistics are written."""
+    m, h, f = _segment_checks(bounds, Q, K, V)
+    out = torch.empty_like(Q)
+    call("dfgnn_segment_mha_fwd", "segment_mha_inference", Q.device, m, h, f, float(scale), bounds, Q, K, V, out, None, None)
+    return out
+
+
+def segment_mha_forward(bounds, Q, K, V, scale=1.0):
+    """-> [out, row_max[m, h], row_sum[m, h]]: the training forward."""
+    m, h, f = _segment_checks(bounds, Q, K, V)
+    out, row_max, row_sum = torch.empty_like(Q), _empty(Q, m, h), _empty(Q, m, h)
+    call("dfgnn_segment_mha_fwd", "segment_mha_forward", Q.device, m, h, f, float(scale), bounds, Q, K, V, out, row_max, row_sum)
+    return [out, row_max, row_sum]
+
+
+def segment_mha_backward(bounds, Q, K, V, out, row_max, row_sum, grad, scale=1.0):
+    """-> [dQ, dK, dV] from the forward's row statistics (P is recomputed tile by tile)."""
+    m, h, f = _segment_checks(bounds, Q, K, V, out=out, grad=grad)
+    check_2d(Q, m, h, row_max=row_max, row_sum=row_sum)
+    delta = _empty(Q, m, h)
+    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
+    call("dfgnn_segment_mha_bwd", "segment_mha_backward", Q.device, m, h, f, float(scale), bounds, Q, K, V, out, row_max, row_sum,
+         grad, dQ, dK, dV, delta)
+    return [dQ, dK, dV]
+
+
 # ---- the CSR-taking inference variants ----------------------------------------------------------------------------------
-_VARIANTS = ("gt_tiling", "gt_csr", "gt_csr_gm", "gt_softmax", "gt_softmax_gm")   # by `which` of torch_ext.cpp: gt_variant_fwd
+_VARIANTS =("gt_tiling", "gt_csr", "gt_csr_gm", "gt_softmax", "gt_softmax_gm")   # by `which` of torch_ext.cpp: gt_variant_fwd
 
 
 def _variant(which, indptr, indices, rows, val, Q, K, V):

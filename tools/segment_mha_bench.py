@@ -1,0 +1,110 @@
+#!/usr/bin/env python3
+"""Global attention over batched graphs (DFGNN.operators.fused_gtconv.SegmentMHAFuse; csrc/segment_mha.hip) against the two
+things a user could do before it, on identical inputs, forward + backward of one training step:
+  new    SegmentMHAFuse(seg_ptr, Q, K, V)
+  sdpa   torch scaled_dot_product_attention on the batch padded to [B, h, n_max, f] with a key-padding mask (the padding
+         and the gather back are NOT timed: the baseline at its best)
+  csr    GTConvFuse_rowstats on the complete-graph CSR (sum of n^2 edges), where that has at most --csr-max-edges edges
+Batches: graph sizes drawn around 23 (ZINC-like), 119 (PATTERN-like), 150 (Peptides-like) and 1000-2000 nodes.  Device events
+around each step, warm-up first, the forms alternating step by step; the median and the minimum go to one JSON line per
+(batch, shape), appended to profiles/segment_mha_bench.jsonl.
+usage: python3 tools/segment_mha_bench.py [--shapes 4x32,8x16,1x128] [--steps 30]   (DESIGN.md 3.3k holds the table)"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "df-gnn_amd")):
+    sys.path.insert(0, p)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+from torch.nn import functional as F  # noqa: E402
+
+from DFGNN.operators.fused_gtconv import GTConvFuse_rowstats, SegmentMHAFuse  # noqa: E402
+
+DEV = "cuda:0"
+BATCHES = {"zinc": (1024, 9, 37), "pattern": (256, 44, 188), "peptides": (128, 60, 240), "long": (16, 1000, 2000)}
+
+
+def complete_csr(sizes):
+    """The complete graph of every segment as the arrays GTConvFuse_rowstats takes (its CSC half is its own transpose)."""
+    n = torch.as_tensor(sizes, device=DEV)
+    lo = torch.cumsum(n, 0) - n
+    node_lo, node_n = torch.repeat_interleave(lo, n), torch.repeat_interleave(n, n)
+    row_ptr = torch.zeros(node_n.numel() + 1, dtype=torch.int64, device=DEV)
+    row_ptr[1:] = torch.cumsum(node_n, 0)
+    rows = torch.repeat_interleave(torch.arange(node_n.numel(), device=DEV), node_n)
+    col = torch.arange(int(row_ptr[-1]), device=DEV) - row_ptr[rows] + node_lo[rows]
+    val_idx = row_ptr[col] + rows - node_lo[rows]
+    i32 = lambda t: t.to(torch.int32)  # noqa: E731
+    val = torch.ones(col.numel(), device=DEV)
+    return i32(rows), i32(row_ptr), i32(col), val, i32(row_ptr), i32(col), i32(val_idx), 0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="4x32,8x16,1x128", help="heads x per-head width, comma-separated")
+    ap.add_argument("--batches", default=",".join(BATCHES))
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--csr-max-edges", type=int, default=40_000_000)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "segment_mha_bench.jsonl"))
+    args = ap.parse_args()
+    for name in args.batches.split(","):
+        count, a, b = BATCHES[name]
+        sizes = np.random.default_rng(7).integers(a, b + 1, size=count)
+        for shape in args.shapes.split(","):
+            h, f = (int(x) for x in shape.split("x"))
+            line = bench(args, name, sizes, h, f)
+            print(json.dumps(line), flush=True)
+            with open(args.out, "a") as fh:
+                fh.write(json.dumps(line) + "\n")
+
+
+def bench(args, name, sizes, h, f):
+    ends = np.concatenate([[0], np.cumsum(sizes)])
+    m, B, nmax, pairs = int(ends[-1]), len(sizes), int(sizes.max()), int((sizes.astype(np.int64) ** 2).sum())
+    seg_ptr = torch.tensor(ends, dtype=torch.int32, device=DEV)
+    gen = torch.Generator().manual_seed(5)
+    Q0, K0, V0, dO = (torch.randn(m, h, f, generator=gen).to(DEV) for _ in range(4))
+    scale = f ** -0.5
+    # padded form: node i of graph b at [b, :, i - lo_b]
+    seg = torch.repeat_interleave(torch.arange(B, device=DEV), torch.as_tensor(sizes, device=DEV))
+    pos = torch.arange(m, device=DEV) - seg_ptr[seg.long()].long()
+    pad = lambda x: torch.zeros(B, nmax, h, f, device=DEV).index_put_((seg, pos), x).transpose(1, 2).contiguous()  # noqa: E731
+    keep = (torch.arange(nmax, device=DEV)[None, :] < torch.as_tensor(sizes, device=DEV)[:, None])[:, None, None, :]
+    Qp, Kp, Vp, dOp = (pad(x) for x in (Q0, K0, V0, dO))
+    forms = {"new": (lambda q, k, v: SegmentMHAFuse(seg_ptr, q, k, v, scale), (Q0, K0, V0), dO),
+             "sdpa": (lambda q, k, v: F.scaled_dot_product_attention(q, k, v, attn_mask=keep, scale=scale), (Qp, Kp, Vp), dOp)}
+    if pairs <= args.csr_max_edges:
+        csr = complete_csr(sizes)
+        forms["csr"] = (lambda q, k, v: GTConvFuse_rowstats(*csr, q * scale, k, v), (Q0, K0, V0), dO)
+    times = {k: [] for k in forms}
+    last = {}
+    for it in range(args.warmup + args.steps):
+        for key, (fn, inputs, grad) in forms.items():           # alternating: all forms see the same machine state
+            leaves = [x.detach().requires_grad_(True) for x in inputs]
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            out = fn(*leaves)
+            grads = torch.autograd.grad(out, leaves, grad)
+            b.record()
+            torch.cuda.synchronize()
+            if it >= args.warmup:
+                times[key].append(a.elapsed_time(b) * 1e3)
+            last[key] = [out.detach()] + list(grads)
+    unpad = lambda x: x.transpose(1, 2)[seg, pos]  # noqa: E731
+    line = {"tool": "segment_mha_bench", "batch": name, "graphs": B, "m": m, "n_max": nmax, "pairs": pairs, "h": h, "f": f,
+            "steps": args.steps}
+    for key in forms:
+        line[key + "_us"] = round(float(np.median(times[key])), 1)
+        line[key + "_us_min"] = round(float(np.min(times[key])), 1)
+        if key != "new":                                         # same function: the forms agree to fp32 rounding
+            other = [unpad(x) for x in last[key]] if key == "sdpa" else last[key]
+            line[key + "_max_diff"] = max(float((x - y).abs().max()) for x, y in zip(last["new"], other))
+    return line
+
+
+if __name__ == "__main__":
+    main()
