@@ -5,7 +5,7 @@ import torch
 import torch.nn as nn
 
 import fused_gtconv as fused_gt
-from DFGNN.operators.fused_gtconv import SegmentMHAFuse
+from DFGNN.operators.fused_gtconv import SegmentMHABiasFuse, SegmentMHAFuse
 
 
 def segment_offsets(segments, device):
@@ -22,7 +22,8 @@ def segment_offsets(segments, device):
 
 
 class GlobalMHA(nn.Module):
-    """out = W_o concat_heads(softmax_graph(scale Q K^T) V), the softmax of a node running over its own graph's nodes."""
+    """out = W_o concat_heads(softmax_graph(scale Q K^T [+ bias]) V), the softmax of a node running over its own graph's
+    nodes."""
 
     def __init__(self, in_size, out_size, num_heads):
         super().__init__()
@@ -34,22 +35,46 @@ class GlobalMHA(nn.Module):
         self.v_proj = nn.Linear(in_size, out_size)
         self.out_proj = nn.Linear(out_size, out_size)
 
-    def forward(self, h, seg_ptr, fuse=True):
+    def forward(self, h, seg_ptr, fuse=True, bias=None):
         """h [N, in]; seg_ptr: int32[n_seg + 1] offsets (a tensor kept across layers and steps is looked up, not rebuilt) or
-        the batch's graph sizes.  fuse=False, or a head shape the fused pair does not serve: plain torch, graph by graph."""
+        the batch's graph sizes.  bias: None or fp32 [heads, sum of n_g^2], added to the logits -- per head the graphs'
+        packed row-major n_g x n_g blocks one after another (PairBias makes one from pair types).  fuse=False, or a head
+        shape the fused pair does not serve: plain torch, graph by graph."""
         seg_ptr = segment_offsets(seg_ptr, h.device)
         n = len(h)
         q, k, v = (p(h).reshape(n, self.num_heads, self.head_dim) for p in (self.q_proj, self.k_proj, self.v_proj))
         if fuse and h.is_cuda and fused_gt.segment_mha_applies(self.num_heads, self.head_dim):
-            out = SegmentMHAFuse(seg_ptr, q.contiguous(), k.contiguous(), v.contiguous(), self.scaling)
+            if bias is None:
+                out = SegmentMHAFuse(seg_ptr, q.contiguous(), k.contiguous(), v.contiguous(), self.scaling)
+            else:
+                out = SegmentMHABiasFuse(seg_ptr, q.contiguous(), k.contiguous(), v.contiguous(), bias.contiguous(), self.scaling)
         else:
-            out = self.forward_plain(seg_ptr, q, k, v)
+            out = self.forward_plain(seg_ptr, q, k, v, bias)
         return self.out_proj(out.reshape(n, -1))
 
-    def forward_plain(self, seg_ptr, q, k, v):
+    def forward_plain(self, seg_ptr, q, k, v, bias=None):
         outs = []
         ends = seg_ptr.tolist()
+        at = 0
         for lo, hi in zip(ends[:-1], ends[1:]):
             s = torch.einsum("ihf,jhf->hij", q[lo:hi], k[lo:hi]) * self.scaling
+            if bias is not None:
+                n = hi - lo
+                s = s + bias[:, at:at + n * n].reshape(bias.size(0), n, n)
+                at += n * n
             outs.append(torch.einsum("hij,jhf->ihf", torch.softmax(s, dim=-1), v[lo:hi]))
         return torch.cat(outs) if outs else torch.empty_like(q)
+
+
+class PairBias(nn.Module):
+    """A learnable scalar per (pair type, head) as the attention bias of GlobalMHA: Graphormer's spatial encoding with the
+    pair type = the (clipped) shortest-path distance.  pair_types int64[n_pairs] lists every graph's n x n type matrix,
+    flattened row-major, graph after graph -> bias [heads, n_pairs]; the table's gradient comes by autograd through dbias."""
+
+    def __init__(self, num_types, num_heads):
+        super().__init__()
+        self.table = nn.Parameter(torch.zeros(num_types, num_heads))
+        nn.init.normal_(self.table, std=0.02)
+
+    def forward(self, pair_types):
+        return self.table.t()[:, pair_types]

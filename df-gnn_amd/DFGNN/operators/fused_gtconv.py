@@ -130,6 +130,39 @@ def SegmentMHAFuse(seg_ptr, Q, K, V, scale=1.0):
     return FusedSegmentMHAFunction.apply(bounds, Q, K, V, scale)
 
 
+class FusedSegmentMHABiasFunction(torch.autograd.Function):
+    """FusedSegmentMHAFunction with a pair bias added to the logits (include/dfgnn_segment_bias.h).  Saved between forward and
+    backward: Q, K, V, bias and the row statistics.  dbias [h, n_pairs] is computed only when the bias requires a gradient;
+    otherwise the backward allocates and writes nothing of that size."""
+
+    @staticmethod
+    def forward(ctx, bounds, row_off, Q, K, V, bias, scale):
+        out, row_max, row_sum = fused_gt.segment_mha_bias_forward(bounds, row_off, bias, Q, K, V, scale)
+        ctx.save_for_backward(bounds, row_off, Q, K, V, bias, row_max, row_sum)
+        ctx.scale = scale
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        bounds, row_off, Q, K, V, bias, row_max, row_sum = ctx.saved_tensors
+        dQ, dK, dV, dbias = fused_gt.segment_mha_bias_backward(bounds, row_off, bias, Q, K, V, row_max, row_sum,
+                                                               grad_out.contiguous(), ctx.scale,
+                                                               need_dbias=ctx.needs_input_grad[5])
+        return None, None, dQ, dK, dV, dbias, None
+
+
+def SegmentMHABiasFuse(seg_ptr, Q, K, V, bias, scale=1.0):
+    """SegmentMHAFuse with s_ij = scale <Q_i, K_j> + bias[head, pair(i, j)]: bias fp32 [h, n_pairs], n_pairs = sum of n_g^2,
+    per head the graphs' packed row-major n_g x n_g blocks (query x key) one after another; finite values, a large negative
+    one masks a pair.  The gradient goes to Q, K, V and, where it requires one, to bias."""
+    m = Q.size(0)
+    bounds = fused_gt.segment_bounds(seg_ptr, m)
+    _, row_off = fused_gt.segment_pair_rows(seg_ptr, m)
+    if not (torch.is_grad_enabled() and (Q.requires_grad or K.requires_grad or V.requires_grad or bias.requires_grad)):
+        return fused_gt.segment_mha_bias_inference(bounds, row_off, bias, Q, K, V, scale)
+    return FusedSegmentMHABiasFunction.apply(bounds, row_off, Q, K, V, bias, scale)
+
+
 # ---- AGNN / dot-product attention with tied keys and values (this build's addition; fused_gtconv.agnn_*) -----------------
 def AGNNConvFuse_inference(row_ptr, col_ind, beta, X_row, X_col, cosine=True):
     """-> out[m, h, f] = softmax_j(beta[h] cos(X_row_i, X_col_j)) X_col_j (cosine=False: beta[h] <X_row_i, X_col_j>); beta

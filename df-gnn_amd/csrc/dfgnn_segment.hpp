@@ -26,6 +26,13 @@
 // delta_i = sum_j P_ij dP_ij is formed from P and dP themselves, never from the stored `out` row; a
 // row's keys may straddle two tiles however small its graph is, so the dQ kernel walks the keys twice: the first pass
 // accumulates t_i in registers, the second forms dS = P (dP - t) and dQ.  See DESIGN.md 3.3k.
+//
+// BIAS (include/dfgnn_segment_bias.h): s_ij = scale <Q_i, K_j> + bias[head, row_off_i + j - lo_i], fp32 planes of
+// packed n x n blocks.  Every bias element meets exactly one accumulator register of one lane, once per pass, so it goes
+// from global memory straight into registers (no LDS): the lane of a query strip owns 4 consecutive keys of its row per
+// key tile (one 16-byte load wherever the row covers all four), the lane of a key strip owns one key of four queries, whose
+// offsets are staged with the other per-row words.  A pair the mask removes is never read; dbias = dS is stored by the dQ
+// kernel's second pass under the same mask.  The logit is fma(S, c, b) in all four places that form one.
 #pragma once
 #include "dfgnn_dense.hpp"
 #include "dfgnn_launch.hpp"
@@ -36,7 +43,7 @@ constexpr int kSegWindow = kDenseWaves * 16;  // rows of a work item: one 16-row
 constexpr int kSegFixedLds = 2 * kDenseWaves * 4;  // the two workgroup-maximum slots
 
 // FR: the real width (16 runs zero-padded on the 32-wide layout, as in dfgnn_dense_fwd.hpp); ROW_WORDS: staged dwords
-// per tile row (dK / dV: row_max, 1 / row_sum, delta, lo, hi); CAP: rows * f the registers allow (dfgnn_lds_layout.hpp);
+// per tile row (dK / dV: row_max, 1 / row_sum, delta, lo, hi, and with a bias the two halves of seg_bias_at); CAP: rows * f the registers allow (dfgnn_lds_layout.hpp);
 // MAXR: rows at most (dK / dV: 64 -- with 128 the narrow heads' S, dP and staged row values spill)
 template <int FR, int ROW_WORDS, int CAP, int MAXR = 128>
 struct SegCfg {
@@ -50,7 +57,7 @@ struct SegCfg {
 constexpr int kSegCapFwd = 8192, kSegCapBwd = 4096;
 template <int FR> using SegFwdCfg = SegCfg<FR, 0, kSegCapFwd>;
 template <int FR> using SegDqCfg = SegCfg<FR, 0, kSegCapBwd>;
-template <int FR> using SegDkvCfg = SegCfg<FR, 5, kSegCapBwd, 64>;
+template <int FR, bool BIAS = false> using SegDkvCfg = SegCfg<FR, BIAS ? 7 : 5, kSegCapBwd, 64>;  // (+ a 64-bit bias offset)
 
 struct SegImages {
   const h16 *ahi, *alo, *bhi, *blo;
@@ -142,6 +149,49 @@ __device__ __forceinline__ SegStrip seg_strip(const int *__restrict__ bounds, in
   return s;
 }
 
+// ---- the pair bias ----------------------------------------------------------------------------------------------------
+struct SegBias {
+  const long long *row_off;  // int64[m]: offset of pair (i, lo_i) in a head's plane
+  long long n_pairs;         // length of a plane
+  const float *bias;         // fp32[h, n_pairs]
+  float *dbias;              // (dQ kernel) fp32[h, n_pairs] or null
+};
+constexpr long long kSegNoBias = -0x7fffffffffffffffll - 1;  // "this row has no place in the plane"
+// `at` such that element at + j of the planes is pair (row, j) for lo <= j < hi: row_off is clamped into [0, n_pairs - n],
+// so whatever row_off holds, at + j stays inside the head's plane; kSegNoBias when the plane cannot hold the row at all
+__device__ __forceinline__ long long seg_bias_at(const SegBias &sb, int head, int row, int lo, int hi) {
+  const long long room = sb.n_pairs - (long long)(hi - lo);
+  if (room < 0) return kSegNoBias;
+  return (long long)head * sb.n_pairs + min(max(sb.row_off[row], 0ll), room) - lo;
+}
+struct __attribute__((packed, aligned(4))) SegF4U {  // 4 floats at a 4-byte aligned address: a bias row starts anywhere
+  float v[4];
+};
+// keys j0 .. j0 + 3 of this lane's row: one 16-byte access where the row covers all four, else only the pairs in [lo, hi)
+__device__ __forceinline__ f32x4 seg_bias_load4(const float *__restrict__ bias, long long at, int j0, int lo, int hi) {
+  f32x4 b = {0.f, 0.f, 0.f, 0.f};
+  if (at == kSegNoBias) return b;
+  if (j0 >= lo && j0 + 4 <= hi) {
+    const SegF4U x = *reinterpret_cast<const SegF4U *>(bias + at + j0);
+    b = f32x4{x.v[0], x.v[1], x.v[2], x.v[3]};
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (j0 + r >= lo && j0 + r < hi) b[r] = bias[at + j0 + r];
+  }
+  return b;
+}
+__device__ __forceinline__ void seg_bias_store4(float *__restrict__ dbias, long long at, int j0, int lo, int hi, const f32x4 &d) {
+  if (at == kSegNoBias) return;
+  if (j0 >= lo && j0 + 4 <= hi) {
+    *reinterpret_cast<SegF4U *>(dbias + at + j0) = SegF4U{{d[0], d[1], d[2], d[3]}};
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (j0 + r >= lo && j0 + r < hi) dbias[at + j0 + r] = d[r];
+  }
+}
+
 // accumulator tiles of a strip -> its global rows (whole lines; the padded width tile by tile)
 template <int FR, int FT>
 __device__ __forceinline__ void seg_store(const f32x4 (&acc)[FT], float scale, float *__restrict__ base, unsigned hf,
@@ -162,11 +212,12 @@ __device__ __forceinline__ void seg_cols_mma(f32x4 (&acc)[NFT], const h16 *ihi, 
 }
 
 // ---- forward ----------------------------------------------------------------------------------------------------------
-template <int FR>
+template <int FR, bool BIAS = false>
 __device__ __forceinline__ void segment_fwd_body(float *lds, int m, int h, float scale, const int *__restrict__ bounds,
                                                  const float *__restrict__ Q, const float *__restrict__ K,
                                                  const float *__restrict__ V, float *__restrict__ out,
-                                                 float *__restrict__ row_max, float *__restrict__ row_sum) {
+                                                 float *__restrict__ row_max, float *__restrict__ row_sum,
+                                                 const SegBias &sb = SegBias{}) {
   using C = SegFwdCfg<FR>;
   constexpr int F = C::F, FT = C::FT, NT = C::NT, TR = C::TR;
   const int head = blockIdx.y, w0 = blockIdx.x * kSegWindow;
@@ -177,6 +228,9 @@ __device__ __forceinline__ void segment_fwd_body(float *lds, int m, int h, float
   SegRows<FR> q;
   seg_rows_load<FR>(q, Q + hoff, hf, st.row, m, L);
   float mrun = -INFINITY, lrun = 0.f;
+  long long bat = kSegNoBias;
+  if constexpr (BIAS)
+    if (st.row < m) bat = seg_bias_at(sb, head, st.row, st.lo, st.hi);
   f32x4 o[FT];
 #pragma unroll
   for (int ft = 0; ft < FT; ++ft) o[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -187,6 +241,12 @@ __device__ __forceinline__ void segment_fwd_body(float *lds, int m, int h, float
     f32x4 S[NT];
     const float c = im.ainv * q.inv * scale;
     float mx = -INFINITY;
+    [[maybe_unused]] f32x4 B[BIAS ? NT : 1];  // the tile's bias: issued ahead of the products
+    if constexpr (BIAS) {
+#pragma unroll
+      for (int jt = 0; jt < NT; ++jt)
+        B[jt] = st.sees(t + 16 * jt, 16) ? seg_bias_load4(sb.bias, bat, t + 16 * jt + 4 * L.mq, st.lo, st.hi) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
 #pragma unroll
     for (int jt = 0; jt < NT; ++jt) {
       const bool seen = st.sees(t + 16 * jt, 16);
@@ -194,7 +254,10 @@ __device__ __forceinline__ void segment_fwd_body(float *lds, int m, int h, float
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int j = t + 16 * jt + 4 * L.mq + r;
-        const float x = (seen && j >= st.lo && j < st.hi) ? S[jt][r] * c : -INFINITY;
+        float s;
+        if constexpr (BIAS) s = fmaf(S[jt][r], c, B[jt][r]);
+        else s = S[jt][r] * c;
+        const float x = (seen && j >= st.lo && j < st.hi) ? s : -INFINITY;
         S[jt][r] = x;
         mx = fmaxf(mx, x);
       }
@@ -237,11 +300,18 @@ __device__ __forceinline__ void segment_fwd_body(float *lds, int m, int h, float
 }
 
 // P of this strip against the resident K tile, from the rows' saved statistics; masked pairs are 0
-template <class C, int FR>
+template <class C, int FR, bool BIAS = false>
 __device__ __forceinline__ void seg_recompute_p(f32x4 (&S)[C::NT], f32x4 (&dP)[C::NT], const SegImages &im, int t,
                                                 const SegStrip &st, const SegRows<FR> &q, const SegRows<FR> &g, float scale,
-                                                float mx, float il, const LaneIds &L) {
+                                                float mx, float il, const LaneIds &L, const float *__restrict__ bias = nullptr,
+                                                long long bat = kSegNoBias) {
   const float c = im.ainv * q.inv * scale, cd = im.binv * g.inv;
+  [[maybe_unused]] f32x4 B[BIAS ? C::NT : 1];  // the tile's bias: issued ahead of the products
+  if constexpr (BIAS) {
+#pragma unroll
+    for (int jt = 0; jt < C::NT; ++jt)
+      B[jt] = st.sees(t + 16 * jt, 16) ? seg_bias_load4(bias, bat, t + 16 * jt + 4 * L.mq, st.lo, st.hi) : f32x4{0.f, 0.f, 0.f, 0.f};
+  }
 #pragma unroll
   for (int jt = 0; jt < C::NT; ++jt) {
     const bool seen = st.sees(t + 16 * jt, 16);
@@ -250,7 +320,9 @@ __device__ __forceinline__ void seg_recompute_p(f32x4 (&S)[C::NT], f32x4 (&dP)[C
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int j = t + 16 * jt + 4 * L.mq + r;
-      const float e = fast_exp(S[jt][r] * c - mx) * il;
+      float e;
+      if constexpr (BIAS) e = fast_exp(fmaf(S[jt][r], c, B[jt][r]) - mx) * il;
+      else e = fast_exp(S[jt][r] * c - mx) * il;
       S[jt][r] = (seen && j >= st.lo && j < st.hi) ? e : 0.f;
       dP[jt][r] *= cd;
     }
@@ -258,12 +330,13 @@ __device__ __forceinline__ void seg_recompute_p(f32x4 (&S)[C::NT], f32x4 (&dP)[C
 }
 
 // ---- dQ (and delta) ---------------------------------------------------------------------------------------------------
-template <int FR>
+template <int FR, bool BIAS = false>
 __device__ __forceinline__ void segment_dq_body(float *lds, int m, int h, float scale, const int *__restrict__ bounds,
                                                 const float *__restrict__ Q, const float *__restrict__ K,
                                                 const float *__restrict__ V, const float *__restrict__ row_max,
                                                 const float *__restrict__ row_sum, const float *__restrict__ dO,
-                                                float *__restrict__ dQ, float *__restrict__ delta) {
+                                                float *__restrict__ dQ, float *__restrict__ delta,
+                                                const SegBias &sb = SegBias{}) {
   using C = SegDqCfg<FR>;
   constexpr int F = C::F, FT = C::FT, NT = C::NT, TR = C::TR;
   const int head = blockIdx.y, w0 = blockIdx.x * kSegWindow;
@@ -276,13 +349,16 @@ __device__ __forceinline__ void segment_dq_body(float *lds, int m, int h, float 
   seg_rows_load<FR>(g, dO + hoff, hf, st.row, m, L);
   const size_t si = (size_t)min(st.row, m - 1) * h + head;
   const float mx = row_max[si], rs = row_sum[si], il = rs > 0.f ? 1.f / rs : 0.f;
+  long long bat = kSegNoBias;
+  if constexpr (BIAS)
+    if (st.row < m) bat = seg_bias_at(sb, head, st.row, st.lo, st.hi);
 
   float tsum = 0.f;  // pass 1: t_i = sum_j P_ij dP_ij
   seg_tile_loop<C>(lds, K + hoff, V + hoff, hf, t0, t1, FR, [](int) {}, [](float *) {}, [&](int t, const SegImages &im) {
     if (!st.sees(t, TR)) return;
     const LaneIds L = lane_ids();
     f32x4 S[NT], dP[NT];
-    seg_recompute_p<C, FR>(S, dP, im, t, st, q, g, scale, mx, il, L);
+    seg_recompute_p<C, FR, BIAS>(S, dP, im, t, st, q, g, scale, mx, il, L, sb.bias, bat);
 #pragma unroll
     for (int jt = 0; jt < NT; ++jt)
 #pragma unroll
@@ -298,7 +374,7 @@ __device__ __forceinline__ void segment_dq_body(float *lds, int m, int h, float 
     if (!st.sees(t, TR)) return;
     const LaneIds L = lane_ids();
     f32x4 S[NT], dP[NT];
-    seg_recompute_p<C, FR>(S, dP, im, t, st, q, g, scale, mx, il, L);
+    seg_recompute_p<C, FR, BIAS>(S, dP, im, t, st, q, g, scale, mx, il, L, sb.bias, bat);
     float am = 0.f;
 #pragma unroll
     for (int jt = 0; jt < NT; ++jt)
@@ -307,6 +383,13 @@ __device__ __forceinline__ void segment_dq_body(float *lds, int m, int h, float 
         S[jt][r] *= dP[jt][r] - dl;
         am = fmaxf(am, fabsf(S[jt][r]));
       }
+    if constexpr (BIAS) {  // dbias = dS, one store per valid pair (the mask of the loads)
+      if (sb.dbias) {
+#pragma unroll
+        for (int jt = 0; jt < NT; ++jt)
+          if (st.sees(t + 16 * jt, 16)) seg_bias_store4(sb.dbias, bat, t + 16 * jt + 4 * L.mq, st.lo, st.hi, S[jt]);
+      }
+    }
     const Pow2Scale ds = pow2_scale(wave_max(am));
     f32x4 tile[FT];
 #pragma unroll
@@ -322,14 +405,14 @@ __device__ __forceinline__ void segment_dq_body(float *lds, int m, int h, float 
 }
 
 // ---- dK, dV -----------------------------------------------------------------------------------------------------------
-template <int FR>
+template <int FR, bool BIAS = false>
 __device__ __forceinline__ void segment_dkv_body(float *lds, int m, int h, float scale, const int *__restrict__ bounds,
                                                  const float *__restrict__ Q, const float *__restrict__ K,
                                                  const float *__restrict__ V, const float *__restrict__ row_max,
                                                  const float *__restrict__ row_sum, const float *__restrict__ dO,
                                                  const float *__restrict__ delta, float *__restrict__ dK,
-                                                 float *__restrict__ dV) {
-  using C = SegDkvCfg<FR>;
+                                                 float *__restrict__ dV, const SegBias &sb = SegBias{}) {
+  using C = SegDkvCfg<FR, BIAS>;
   constexpr int F = C::F, FT = C::FT, NT = C::NT, TR = C::TR;
   const int head = blockIdx.y, w0 = blockIdx.x * kSegWindow;
   const unsigned hf = (unsigned)h * FR, hoff = (unsigned)head * FR;
@@ -346,6 +429,7 @@ __device__ __forceinline__ void segment_dkv_body(float *lds, int m, int h, float
 
   float xm = 0.f, xs = 0.f, xd = 0.f;  // a tile row's statistics, delta and bounds on their way to LDS (threads < TR)
   int xlo = 0, xhi = 0;
+  [[maybe_unused]] long long xat = kSegNoBias;  // (BIAS) seg_bias_at of the tile row: two more words
   auto xload = [&](int t) {
     const int tid = opaque_tid();
     if (tid < TR) {
@@ -356,6 +440,7 @@ __device__ __forceinline__ void segment_dkv_body(float *lds, int m, int h, float
       xd = delta[si];
       xlo = t + tid < t1 ? bounds[2 * i] : 0;  // a row past the range sees nothing
       xhi = t + tid < t1 ? bounds[2 * i + 1] : 0;
+      if constexpr (BIAS) xat = seg_bias_at(sb, head, i, xlo, xhi);
     }
   };
   auto xstore = [&](float *rows) {
@@ -366,6 +451,10 @@ __device__ __forceinline__ void segment_dkv_body(float *lds, int m, int h, float
       rows[2 * TR + tid] = xd;
       reinterpret_cast<int *>(rows)[3 * TR + tid] = xlo;
       reinterpret_cast<int *>(rows)[4 * TR + tid] = xhi;
+      if constexpr (BIAS) {
+        reinterpret_cast<int *>(rows)[5 * TR + tid] = (int)(unsigned)(unsigned long long)xat;
+        reinterpret_cast<int *>(rows)[6 * TR + tid] = (int)(xat >> 32);
+      }
     }
   };
   seg_tile_loop<C>(lds, Q + hoff, dO + hoff, hf, t0, t1, FR, xload, xstore, [&](int t, const SegImages &im) {
@@ -378,9 +467,23 @@ __device__ __forceinline__ void segment_dkv_body(float *lds, int m, int h, float
 #pragma unroll
     for (int u = 0; u < NT; ++u) {
       const bool seen = st.sees(t + 16 * u, 16);
+      const int at = 16 * u + 4 * L.mq;
+      [[maybe_unused]] f32x4 B = {0.f, 0.f, 0.f, 0.f};  // bias of (query at + r, key j): issued ahead of the products
+      if constexpr (BIAS) {
+        if (seen) {
+          const int4 al = *reinterpret_cast<const int4 *>(im.rows + 5 * TR + at), ah = *reinterpret_cast<const int4 *>(im.rows + 6 * TR + at);
+          const int4 lo = *reinterpret_cast<const int4 *>(im.rows + 3 * TR + at), hi = *reinterpret_cast<const int4 *>(im.rows + 4 * TR + at);
+          const int alr[4] = {al.x, al.y, al.z, al.w}, ahr[4] = {ah.x, ah.y, ah.z, ah.w};
+          const int lor[4] = {lo.x, lo.y, lo.z, lo.w}, hir[4] = {hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const long long a = (long long)(((unsigned long long)(unsigned)ahr[r] << 32) | (unsigned)alr[r]);
+            if (a != kSegNoBias && j >= lor[r] && j < hir[r]) B[r] = sb.bias[a + j];
+          }
+        }
+      }
       S[u] = seen ? dense_rows_mma<F>(im.ahi, im.alo, u, k.h, k.l, L) : f32x4{0.f, 0.f, 0.f, 0.f};
       dP[u] = seen ? dense_rows_mma<F>(im.bhi, im.blo, u, v.h, v.l, L) : f32x4{0.f, 0.f, 0.f, 0.f};
-      const int at = 16 * u + 4 * L.mq;
       const float4 mx = *reinterpret_cast<const float4 *>(im.rows + at), il = *reinterpret_cast<const float4 *>(im.rows + TR + at),
                    dl = *reinterpret_cast<const float4 *>(im.rows + 2 * TR + at);
       const int4 lo = *reinterpret_cast<const int4 *>(im.rows + 3 * TR + at), hi = *reinterpret_cast<const int4 *>(im.rows + 4 * TR + at);
@@ -388,7 +491,9 @@ __device__ __forceinline__ void segment_dkv_body(float *lds, int m, int h, float
       const int lor[4] = {lo.x, lo.y, lo.z, lo.w}, hir[4] = {hi.x, hi.y, hi.z, hi.w};
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float e = fast_exp(S[u][r] * c - mxr[r]) * ilr[r];
+        float e;
+        if constexpr (BIAS) e = fast_exp(fmaf(S[u][r], c, B[r]) - mxr[r]) * ilr[r];
+        else e = fast_exp(S[u][r] * c - mxr[r]) * ilr[r];
         const float p = (seen && j >= lor[r] && j < hir[r]) ? e : 0.f;
         const float ds = p * (dP[u][r] * cd - dlr[r]);
         S[u][r] = p;

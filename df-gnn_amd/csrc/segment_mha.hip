@@ -1,5 +1,6 @@
 // segment_mha.hip -- multi-head attention of every node over the nodes of its own graph in a batch: the C entries of
-// include/dfgnn_segment.h.  The kernel bodies and the design are in dfgnn_segment.hpp.
+// include/dfgnn_segment.h, and of include/dfgnn_segment_bias.h: the same pair with a per-pair bias added to the logits.  The
+// kernel bodies and the design are in dfgnn_segment.hpp.
 //
 // The whole structure of the problem is seg_ptr [n_seg + 1].  dfgnn_segment_bounds turns it into (lo, hi) per node once
 // per batch; every layer, head and direction reads that.  Grids follow from m alone -- ceil(m / 128) windows x h heads --
@@ -7,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/dfgnn_segment.h"
+#include "../../include/dfgnn_segment_bias.h"
 #include "dfgnn_segment.hpp"
 
 namespace dfgnn {
@@ -58,6 +60,93 @@ __global__ __launch_bounds__(kDenseThreads) void segment_mha_dkv_kernel(int m, i
                                                                         float *__restrict__ dV) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   segment_dkv_body<FR>(lds, m, h, scale, bounds, Q, K, V, row_max, row_sum, dO, delta, dK, dV);
+}
+
+// ---- the pair bias (include/dfgnn_segment_bias.h): the same bodies with BIAS, and the offsets they read ----------------------
+// pair_ptr = exclusive prefix sum of n_g^2 by ONE workgroup walking the segments 1024 at a time: a wave scan, the waves'
+// totals through LDS, the running total carried from chunk to chunk in a register.  Sizes come from seg_ptr clamped as
+// segment_bounds_kernel clamps it.
+constexpr int kPairScanThreads = 1024;
+__global__ __launch_bounds__(kPairScanThreads) void segment_pair_ptr_kernel(int m, int n_seg, const int *__restrict__ seg_ptr,
+                                                                            long long *__restrict__ pair_ptr) {
+  __shared__ long long wave_total[kPairScanThreads / kWave];
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  long long carry = 0;
+  for (int base = 0; base < n_seg; base += kPairScanThreads) {
+    const int g = base + tid;
+    long long n = 0;
+    if (g < n_seg) n = max(min(max(seg_ptr[g + 1], 0), m) - min(max(seg_ptr[g], 0), m), 0);
+    const long long v = n * n;
+    long long incl = v;
+#pragma unroll
+    for (int d = 1; d < kWave; d *= 2) {
+      const long long up = __shfl_up(incl, d, kWave);
+      if (lane >= d) incl += up;
+    }
+    if (lane == kWave - 1) wave_total[wave] = incl;
+    __syncthreads();
+    long long before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < kPairScanThreads / kWave; ++w) {
+      const long long x = wave_total[w];
+      if (w < wave) before += x;
+      total += x;
+    }
+    if (g < n_seg) pair_ptr[g] = carry + before + incl - v;
+    carry += total;
+    __syncthreads();  // wave_total is posted to again
+  }
+  if (tid == 0) pair_ptr[n_seg] = carry;
+}
+
+// one thread per node: its segment as in segment_bounds_kernel, then row_off_i = pair_ptr[g] + (i - lo) n
+__global__ void segment_row_off_kernel(int m, int n_seg, const int *__restrict__ seg_ptr, const long long *__restrict__ pair_ptr,
+                                       long long *__restrict__ row_off) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  int a = 0, b = n_seg - 1;
+  while (a < b) {
+    const int mid = (a + b + 1) >> 1;
+    if (seg_ptr[mid] <= i) a = mid;
+    else b = mid - 1;
+  }
+  const int lo = min(max(seg_ptr[a], 0), m), hi = min(max(seg_ptr[a + 1], 0), m);
+  row_off[i] = pair_ptr[a] + (long long)(i - lo) * max(hi - lo, 0);
+}
+
+template <int FR>
+__global__ __launch_bounds__(kDenseThreads) void segment_mha_bias_fwd_kernel(int m, int h, float scale, const int *__restrict__ bounds,
+                                                                             SegBias sb, const float *__restrict__ Q,
+                                                                             const float *__restrict__ K, const float *__restrict__ V,
+                                                                             float *__restrict__ out, float *__restrict__ row_max,
+                                                                             float *__restrict__ row_sum) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  segment_fwd_body<FR, true>(lds, m, h, scale, bounds, Q, K, V, out, row_max, row_sum, sb);
+}
+
+template <int FR>
+__global__ __launch_bounds__(kDenseThreads) void segment_mha_bias_dq_kernel(int m, int h, float scale, const int *__restrict__ bounds,
+                                                                            SegBias sb, const float *__restrict__ Q,
+                                                                            const float *__restrict__ K, const float *__restrict__ V,
+                                                                            const float *__restrict__ row_max,
+                                                                            const float *__restrict__ row_sum,
+                                                                            const float *__restrict__ dO, float *__restrict__ dQ,
+                                                                            float *__restrict__ delta) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  segment_dq_body<FR, true>(lds, m, h, scale, bounds, Q, K, V, row_max, row_sum, dO, dQ, delta, sb);
+}
+
+template <int FR>
+__global__ __launch_bounds__(kDenseThreads) void segment_mha_bias_dkv_kernel(int m, int h, float scale, const int *__restrict__ bounds,
+                                                                             SegBias sb, const float *__restrict__ Q,
+                                                                             const float *__restrict__ K, const float *__restrict__ V,
+                                                                             const float *__restrict__ row_max,
+                                                                             const float *__restrict__ row_sum,
+                                                                             const float *__restrict__ dO,
+                                                                             const float *__restrict__ delta, float *__restrict__ dK,
+                                                                             float *__restrict__ dV) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  segment_dkv_body<FR, true>(lds, m, h, scale, bounds, Q, K, V, row_max, row_sum, dO, delta, dK, dV, sb);
 }
 
 static bool segment_width_ok(int f) { return f == 16 || f == 32 || f == 64 || f == 128; }
@@ -130,6 +219,62 @@ int dfgnn_segment_mha_bwd(int m, int h, int f, float scale, const int *bounds, c
     segment_mha_dq_kernel<FR><<<grid, kDenseThreads, SegDqCfg<FR>::kLds, s>>>(m, h, scale, bounds, Q, K, V, row_max,
                                                                                           row_sum, dO, dQ, delta);
     segment_mha_dkv_kernel<FR><<<grid, kDenseThreads, SegDkvCfg<FR>::kLds, s>>>(m, h, scale, bounds, Q, K, V, row_max,
+                                                                                           row_sum, dO, delta, dK, dV);
+    return launch_status();
+  });
+}
+
+// ---- include/dfgnn_segment_bias.h ------------------------------------------------------------------------------------------
+int dfgnn_segment_bias_abi_version(void) { return DFGNN_SEGMENT_BIAS_ABI_VERSION; }
+
+int dfgnn_segment_pair_rows(int m, int n_seg, const int *seg_ptr, long long *pair_ptr, long long *row_off, dfgnn_stream_t stream) {
+  if (m < 0 || n_seg < 0 || (m > 0 && n_seg == 0)) return kErrBadArg;
+  if (m >= (1 << 30)) return kErrUnsupported;  // (as dfgnn_segment_bounds)
+  if (m == 0) return 0;
+  if (!seg_ptr || !pair_ptr || !row_off) return kErrBadArg;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  segment_pair_ptr_kernel<<<1, kPairScanThreads, 0, s>>>(m, n_seg, seg_ptr, pair_ptr);
+  segment_row_off_kernel<<<(m + 255) / 256, 256, 0, s>>>(m, n_seg, seg_ptr, pair_ptr, row_off);
+  return launch_status();
+}
+
+int dfgnn_segment_mha_bias_fwd(int m, int h, int f, float scale, const int *bounds, const long long *row_off, long long n_pairs,
+                               const float *bias, const float *Q, const float *K, const float *V, float *out, float *row_max,
+                               float *row_sum, dfgnn_stream_t stream) {
+  if (n_pairs < 0) return kErrBadArg;
+  if (int rc = segment_check(m, h, f)) return rc;
+  if ((row_max == nullptr) != (row_sum == nullptr)) return kErrBadArg;
+  if (m == 0) return 0;
+  if (!bounds || !row_off || !bias || !Q || !K || !V || !out) return kErrBadArg;
+  const dim3 grid((m + kSegWindow - 1) / kSegWindow, h);
+  const SegBias sb{row_off, n_pairs, bias, nullptr};
+  return dispatch_segment(f, [&](auto fc) {
+    constexpr int FR = decltype(fc)::value;
+    if (int rc = set_max_lds_cached(segment_mha_bias_fwd_kernel<FR>)) return rc;
+    segment_mha_bias_fwd_kernel<FR><<<grid, kDenseThreads, SegFwdCfg<FR>::kLds, reinterpret_cast<hipStream_t>(stream)>>>(
+        m, h, scale, bounds, sb, Q, K, V, out, row_max, row_sum);
+    return launch_status();
+  });
+}
+
+int dfgnn_segment_mha_bias_bwd(int m, int h, int f, float scale, const int *bounds, const long long *row_off, long long n_pairs,
+                               const float *bias, const float *Q, const float *K, const float *V, const float *row_max,
+                               const float *row_sum, const float *dO, float *dQ, float *dK, float *dV, float *dbias,
+                               float *delta, dfgnn_stream_t stream) {
+  if (n_pairs < 0) return kErrBadArg;
+  if (int rc = segment_check(m, h, f)) return rc;
+  if (m == 0) return 0;
+  if (!bounds || !row_off || !bias || !Q || !K || !V || !row_max || !row_sum || !dO || !dQ || !dK || !dV || !delta) return kErrBadArg;
+  const dim3 grid((m + kSegWindow - 1) / kSegWindow, h);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const SegBias sb{row_off, n_pairs, bias, dbias};
+  return dispatch_segment(f, [&](auto fc) {
+    constexpr int FR = decltype(fc)::value;
+    if (int rc = set_max_lds_cached(segment_mha_bias_dq_kernel<FR>)) return rc;
+    if (int rc = set_max_lds_cached(segment_mha_bias_dkv_kernel<FR>)) return rc;
+    segment_mha_bias_dq_kernel<FR><<<grid, kDenseThreads, SegDqCfg<FR>::kLds, s>>>(m, h, scale, bounds, sb, Q, K, V, row_max,
+                                                                                   row_sum, dO, dQ, delta);
+    segment_mha_bias_dkv_kernel<FR><<<grid, kDenseThreads, SegDkvCfg<FR, true>::kLds, s>>>(m, h, scale, bounds, sb, Q, K, V, row_max,
                                                                                            row_sum, dO, delta, dK, dV);
     return launch_status();
   });

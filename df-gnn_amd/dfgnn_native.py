@@ -114,6 +114,14 @@ SEGMENT_SIGNATURES = {
     "dfgnn_segment_mha_bwd": [_i, _i, _i, _f] + [_vp] * 13,
 }
 
+# the same pair with a pair bias: include/dfgnn_segment_bias.h one to one (checked by tests/test_segment_bias_host.py)
+SEGMENT_BIAS_SIGNATURES = {
+    "dfgnn_segment_bias_abi_version": [],
+    "dfgnn_segment_pair_rows": [_i, _i] + [_vp] * 4,
+    "dfgnn_segment_mha_bias_fwd": [_i, _i, _i, _f, _vp, _vp, ctypes.c_longlong] + [_vp] * 8,
+    "dfgnn_segment_mha_bias_bwd": [_i, _i, _i, _f, _vp, _vp, ctypes.c_longlong] + [_vp] * 13,
+}
+
 EXT_PATH = os.path.join(_HERE, "_dfgnn_ext.so")   # torch C++ extension over the same C ABI (csrc/torch_ext.cpp)
 
 _lib = None
@@ -166,7 +174,8 @@ def lib():
         # (no import order to respect: libdfgnn.so has no HIP dependency, libdfgnn_hip.so is opened by it at the first
         # call that needs the kernels -- csrc/gen_shim.py)
         L = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(SEGMENT_SIGNATURES.items()):
+        for name, argtypes in (list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(SEGMENT_SIGNATURES.items()) +
+                               list(SEGMENT_BIAS_SIGNATURES.items())):
             fn = getattr(L, name)  # AttributeError if the library is stale
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int

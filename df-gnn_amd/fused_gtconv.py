@@ -833,6 +833,67 @@ def segment_mha_backward(bounds, Q, K, V, out, row_max, row_sum, grad, scale=1.0
     return [dQ, dK, dV]
 
 
+# ---- the same pair with a pair bias (include/dfgnn_segment_bias.h): Graphormer-style global attention --------------------
+# bias fp32[h, n_pairs], n_pairs = sum of n_g^2: per head the graphs' packed row-major n_g x n_g blocks one after another.
+_pair_rows_cache = _KeyedCache()
+
+
+def segment_pair_rows(seg_ptr, m):
+    """-> (pair_ptr int64[n_seg + 1], row_off int64[m]): the exclusive prefix sum of n_g^2 and every node's row start in a
+    bias plane, built on the device once per seg_ptr tensor and cached like segment_bounds."""
+    check_family(seg_ptr, torch.int32, seg_ptr=seg_ptr)
+    if seg_ptr.dim() != 1 or seg_ptr.numel() < 1:
+        raise RuntimeError(f"seg_ptr must have shape (n_seg + 1,), got {tuple(seg_ptr.shape)}")
+    key = _KeyedCache.key_of(seg_ptr, extra=(m,))
+    hit = _pair_rows_cache.get(key)
+    if hit is None:
+        pair_ptr = torch.zeros(seg_ptr.numel(), dtype=torch.int64, device=seg_ptr.device)   # (m == 0 writes nothing)
+        row_off = torch.empty(m, dtype=torch.int64, device=seg_ptr.device)
+        call("dfgnn_segment_pair_rows", "segment_pair_rows", seg_ptr.device, m, seg_ptr.numel() - 1, seg_ptr, pair_ptr, row_off)
+        hit = _pair_rows_cache.put(key, (pair_ptr, row_off), seg_ptr)
+    return hit
+
+
+def _segment_bias_checks(bounds, row_off, bias, Q, K, V, **like_Q):
+    m, h, f = _segment_checks(bounds, Q, K, V, **like_Q)
+    _family(Q, torch.int64, (m,), {"row_off": row_off})
+    _family(Q, torch.float32, None, {"bias": bias})
+    if bias.dim() != 2 or bias.size(0) != h:
+        raise RuntimeError(f"bias must have shape ({h}, n_pairs): one plane per head, got {tuple(bias.shape)}")
+    return m, h, f, bias.size(1)
+
+
+def segment_mha_bias_inference(bounds, row_off, bias, Q, K, V, scale=1.0):
+    """-> out [m, h, f]; no statistics are written."""
+    m, h, f, n_pairs = _segment_bias_checks(bounds, row_off, bias, Q, K, V)
+    out = torch.empty_like(Q)
+    call("dfgnn_segment_mha_bias_fwd", "segment_mha_bias_inference", Q.device, m, h, f, float(scale), bounds, row_off, n_pairs,
+         bias, Q, K, V, out, None, None)
+    return out
+
+
+def segment_mha_bias_forward(bounds, row_off, bias, Q, K, V, scale=1.0):
+    """-> [out, row_max[m, h], row_sum[m, h]]: the training forward (statistics of the biased logits)."""
+    m, h, f, n_pairs = _segment_bias_checks(bounds, row_off, bias, Q, K, V)
+    out, row_max, row_sum = torch.empty_like(Q), _empty(Q, m, h), _empty(Q, m, h)
+    call("dfgnn_segment_mha_bias_fwd", "segment_mha_bias_forward", Q.device, m, h, f, float(scale), bounds, row_off, n_pairs,
+         bias, Q, K, V, out, row_max, row_sum)
+    return [out, row_max, row_sum]
+
+
+def segment_mha_bias_backward(bounds, row_off, bias, Q, K, V, row_max, row_sum, grad, scale=1.0, need_dbias=True):
+    """-> [dQ, dK, dV, dbias]; dbias [h, n_pairs] = dS, or None without need_dbias (then nothing of that size is written)."""
+    m, h, f, n_pairs = _segment_bias_checks(bounds, row_off, bias, Q, K, V, grad=grad)
+    check_2d(Q, m, h, row_max=row_max, row_sum=row_sum)
+    delta = _empty(Q, m, h)
+    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
+    # (every valid pair is written; with m == 0 there is none)
+    dbias = torch.empty_like(bias) if need_dbias else None
+    call("dfgnn_segment_mha_bias_bwd", "segment_mha_bias_backward", Q.device, m, h, f, float(scale), bounds, row_off, n_pairs,
+         bias, Q, K, V, row_max, row_sum, grad, dQ, dK, dV, dbias, delta)
+    return [dQ, dK, dV, dbias]
+
+
 # ---- the CSR-taking inference variants ----------------------------------------------------------------------------------
 _VARIANTS =("gt_tiling", "gt_csr", "gt_csr_gm", "gt_softmax", "gt_softmax_gm")   # by `which` of torch_ext.cpp: gt_variant_fwd
 

@@ -8,7 +8,12 @@ things a user could do before it, on identical inputs, forward + backward of one
 Batches: graph sizes drawn around 23 (ZINC-like), 119 (PATTERN-like), 150 (Peptides-like) and 1000-2000 nodes.  Device events
 around each step, warm-up first, the forms alternating step by step; the median and the minimum go to one JSON line per
 (batch, shape), appended to profiles/segment_mha_bench.jsonl.
-usage: python3 tools/segment_mha_bench.py [--shapes 4x32,8x16,1x128] [--steps 30]   (DESIGN.md 3.3k holds the table)"""
+--bias: the pair with a pair bias (SegmentMHABiasFuse, include/dfgnn_segment_bias.h), bias fp32 [h, sum of n^2] requiring a
+gradient, against
+  sdpa   the same padded SDPA with the bias as a float attn_mask [B, h, n_max, n_max] (-inf on the padding keys), its
+         gradient included
+  plain  the unbiased pair on the same Q, K, V: the difference is the price of the bias
+usage: python3 tools/segment_mha_bench.py [--shapes 4x32,8x16,1x128] [--steps 30] [--bias]   (DESIGN.md 3.3k, 3.3l hold the tables)"""
 import argparse
 import json
 import os
@@ -21,7 +26,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from torch.nn import functional as F  # noqa: E402
 
-from DFGNN.operators.fused_gtconv import GTConvFuse_rowstats, SegmentMHAFuse  # noqa: E402
+from DFGNN.operators.fused_gtconv import GTConvFuse_rowstats, SegmentMHABiasFuse, SegmentMHAFuse  # noqa: E402
 
 DEV = "cuda:0"
 BATCHES = {"zinc": (1024, 9, 37), "pattern": (256, 44, 188), "peptides": (128, 60, 240), "long": (16, 1000, 2000)}
@@ -49,6 +54,8 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--csr-max-edges", type=int, default=40_000_000)
+    ap.add_argument("--bias", action="store_true", help="time the biased pair against SDPA with a float mask and the unbiased pair")
+    ap.add_argument("--bias-max-pairs", type=int, default=40_000_000, help="skip batches whose padded mask would be larger")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "segment_mha_bench.jsonl"))
     args = ap.parse_args()
     for name in args.batches.split(","):
@@ -56,6 +63,8 @@ def main():
         sizes = np.random.default_rng(7).integers(a, b + 1, size=count)
         for shape in args.shapes.split(","):
             h, f = (int(x) for x in shape.split("x"))
+            if args.bias and len(sizes) * int(sizes.max()) ** 2 > args.bias_max_pairs:
+                continue
             line = bench(args, name, sizes, h, f)
             print(json.dumps(line), flush=True)
             with open(args.out, "a") as fh:
@@ -77,7 +86,18 @@ def bench(args, name, sizes, h, f):
     Qp, Kp, Vp, dOp = (pad(x) for x in (Q0, K0, V0, dO))
     forms = {"new": (lambda q, k, v: SegmentMHAFuse(seg_ptr, q, k, v, scale), (Q0, K0, V0), dO),
              "sdpa": (lambda q, k, v: F.scaled_dot_product_attention(q, k, v, attn_mask=keep, scale=scale), (Qp, Kp, Vp), dOp)}
-    if pairs <= args.csr_max_edges:
+    if args.bias:
+        # bias [h, pairs] and the same numbers as a padded float mask: pair (i, j) of graph b at [b, :, i - lo, j - lo]
+        n_of = torch.as_tensor(sizes, device=DEV)[seg]
+        prow = torch.repeat_interleave(torch.arange(m, device=DEV), n_of)
+        pcol = torch.arange(pairs, device=DEV) - torch.repeat_interleave(torch.cumsum(n_of, 0) - n_of, n_of)
+        bias0 = torch.randn(h, pairs, generator=gen).to(DEV)
+        mask0 = torch.zeros(B, h, nmax, nmax, device=DEV).masked_fill_(~keep, float("-inf"))
+        mask0[seg[prow], :, pos[prow], pcol] = bias0.t()
+        forms = {"new": (lambda q, k, v, b: SegmentMHABiasFuse(seg_ptr, q, k, v, b, scale), (Q0, K0, V0, bias0), dO),
+                 "sdpa": (lambda q, k, v, b: F.scaled_dot_product_attention(q, k, v, attn_mask=b, scale=scale), (Qp, Kp, Vp, mask0), dOp),
+                 "plain": (lambda q, k, v: SegmentMHAFuse(seg_ptr, q, k, v, scale), (Q0, K0, V0), dO)}
+    elif pairs <= args.csr_max_edges:
         csr = complete_csr(sizes)
         forms["csr"] = (lambda q, k, v: GTConvFuse_rowstats(*csr, q * scale, k, v), (Q0, K0, V0), dO)
     times = {k: [] for k in forms}
@@ -95,13 +115,17 @@ def bench(args, name, sizes, h, f):
                 times[key].append(a.elapsed_time(b) * 1e3)
             last[key] = [out.detach()] + list(grads)
     unpad = lambda x: x.transpose(1, 2)[seg, pos]  # noqa: E731
-    line = {"tool": "segment_mha_bench", "batch": name, "graphs": B, "m": m, "n_max": nmax, "pairs": pairs, "h": h, "f": f,
+    line = {"tool": "segment_mha_bench" + ("_bias" if args.bias else ""), "batch": name, "graphs": B, "m": m, "n_max": nmax, "pairs": pairs, "h": h, "f": f,
             "steps": args.steps}
     for key in forms:
         line[key + "_us"] = round(float(np.median(times[key])), 1)
         line[key + "_us_min"] = round(float(np.min(times[key])), 1)
+        if key == "plain":                                       # (another function)
+            continue
         if key != "new":                                         # same function: the forms agree to fp32 rounding
-            other = [unpad(x) for x in last[key]] if key == "sdpa" else last[key]
+            other = [unpad(x) for x in last[key][:4]] if key == "sdpa" else last[key]
+            if args.bias:
+                other.append(last[key][4][seg[prow], :, pos[prow], pcol].t())
             line[key + "_max_diff"] = max(float((x - y).abs().max()) for x, y in zip(last["new"], other))
     return line
 
