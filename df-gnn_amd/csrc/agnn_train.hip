@@ -6,7 +6,9 @@
 // of an edge are therefore ONE row up to a scalar: every pass gathers it once per edge, and the norm is taken from the
 // registers that hold the row -- in the same cross-lane sweep as the dot product -- so nothing per node is precomputed,
 // saved or gathered.  The structure is gatv2_train.hip's: a forward with online softmax that saves two floats per (row, head),
-// a CSR pass and a CSC pass that recompute each edge, each in a wave-per-row and a lane-group-per-row form:
+// a CSR pass and a CSC pass that recompute each edge, each in a wave-per-row and a lane-group-per-row form.  The kernels of
+// the two forms, their grids and the choice between them are the shared shell of dfgnn_pair_shell.hpp (AgnnOp<COS> below
+// plugs into it); the per-row routines are this file's own:
 //   c_e  = r_i q_j <Xr_i, Xc_j>    s_e = beta c_e    P_e = exp(s_e - row_max_i) / row_sum_i    out_i = sum_e P_e Xc_j
 //   dS_e = P_e (<dO_i, Xc_j> - delta_i)              g_i = sum_{e of i} dS_e c_e              g'_j = sum_{e into j} dS_e c_e
 //   forward           CSR.  Xr_i and r_i in registers.  The lane-group form gathers Xc_j once per edge (dot, norm, message);
@@ -19,6 +21,7 @@
 // dbeta[h] = sum_i g_i is the caller's column sum of dbeta_rows: no workspace, no persistent grid, no reduction kernel.
 // Every output is written in full by plain stores; all sums are deterministic (no atomics).
 #include "dfgnn_launch.hpp"
+#include "dfgnn_pair_shell.hpp"
 #include "dfgnn_rows.hpp"
 
 namespace dfgnn {
@@ -366,85 +369,31 @@ __device__ __forceinline__ void agnn_bwd_col_group(const Agnn &a, int j, int gid
 }
 
 // ======================================================================================================================
-// kernels.  PASS: 0 forward, 1 backward CSR pass, 2 backward CSC pass.
+// the operator as dfgnn_pair_shell.hpp sees it: the kernels, their grids and the launch are there.  COS is part of the
+// operator type, so the shell knows nothing of it.
 // ======================================================================================================================
-template <class C, bool COS, int PASS, bool COOP>
-__device__ __forceinline__ void agnn_group_pass(const Agnn &a, int r, int gid, int gl) {
-  if constexpr (PASS == 0) agnn_fwd_row_group<C, COS, COOP>(a, r, gid, gl);
-  else if constexpr (PASS == 1) agnn_bwd_row_group<C, COS, COOP>(a, r, gid, gl);
-  else agnn_bwd_col_group<C, COS, COOP>(a, r, gid, gl);
-}
-
-// general: a wave per row / column, grid-strided over the whole graph.  The forward works in 64-edge tiles through the
-// wave's LDS scratch; the backward passes are the COOP form of the group routines.
-template <class C, bool COS, int PASS>
-__global__ __launch_bounds__(kBlock) void agnn_wave_kernel(Agnn a) {
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  const int gid = lane / C::G, gl = lane % C::G;
-  a.at_head(blockIdx.y);
-  const int n = PASS == 2 ? a.n_cols : a.m;  // the extent this pass walks: rows, or (CSC pass) columns
-  const int beg = blockIdx.x * kWavesPerBlock + wave, step = gridDim.x * kWavesPerBlock;
-  if constexpr (PASS == 0) {
-    __shared__ __attribute__((aligned(16))) float lds[kWavesPerBlock * kScratchFloatsPerWave];
-    float *sw = lds + wave * kScratchFloatsPerWave;
-    int *sc = reinterpret_cast<int *>(sw + kWave);
-    for (int r = beg; r < n; r += step) agnn_fwd_row_wave<C, COS>(a, r, lane, sw, sc);
-  } else {
-    for (int r = beg; r < n; r += step) agnn_group_pass<C, COS, PASS, true>(a, r, gid, gl);
+constexpr int kAgnnGroupMaxDegree = 24;  // a lane-group wave with a longer row takes its rows cooperatively
+template <bool COS>
+struct AgnnOp {
+  using Args = Agnn;
+  static constexpr int kGroupMaxDegree = kAgnnGroupMaxDegree;
+  static constexpr bool kFwdTiles = true;
+  template <class C>
+  static __device__ __forceinline__ void fwd_row_wave(const Args &a, int r, int lane, float *sw, int *sc) {
+    agnn_fwd_row_wave<C, COS>(a, r, lane, sw, sc);
   }
-}
-
-// low-degree graphs: a workgroup takes blocks of kBlock / G consecutive rows, one lane group per row -- unless a wave's
-// EPW rows include one of more than kAgnnGroupMaxDegree entries, which a single lane group would walk serially while the
-// rest of the wave waits: that wave takes its rows one after the other with all its groups on each (COOP).  The choice is
-// wave-uniform (ballot).  As gatv2_group_kernel.
-constexpr int kAgnnGroupMaxDegree = 24;
-template <class C, bool COS, int PASS>
-__global__ __launch_bounds__(kBlock) void agnn_group_kernel(Agnn a) {
-  constexpr int G = C::G, R = kBlock / G;  // rows per block
-  const int gid = (threadIdx.x & (kWave - 1)) / G, gl = threadIdx.x % G, wave = threadIdx.x / kWave;
-  a.at_head(blockIdx.y);
-  const int *ptr = PASS == 2 ? a.col_ptr : a.row_ptr;
-  const int n = PASS == 2 ? a.n_cols : a.m;  // the extent this pass walks: rows, or (CSC pass) columns
-  for (int b0 = blockIdx.x * R; b0 < n; b0 += gridDim.x * R) {
-    const int r = b0 + threadIdx.x / G;
-    const int deg = r < n ? ptr[r + 1] - ptr[r] : 0;
-    if (__any(deg > kAgnnGroupMaxDegree)) {
-      for (int rr = b0 + wave * C::EPW; rr < min(n, b0 + (wave + 1) * C::EPW); ++rr)
-        agnn_group_pass<C, COS, PASS, true>(a, rr, gid, gl);
-    } else if (r < n) {
-      agnn_group_pass<C, COS, PASS, false>(a, r, gid, gl);
-    }
+  template <class C, int PASS, bool COOP>
+  static __device__ __forceinline__ void group_pass(const Args &a, int r, int gid, int gl) {
+    if constexpr (PASS == 0) agnn_fwd_row_group<C, COS, COOP>(a, r, gid, gl);
+    else if constexpr (PASS == 1) agnn_bwd_row_group<C, COS, COOP>(a, r, gid, gl);
+    else agnn_bwd_col_group<C, COS, COOP>(a, r, gid, gl);
   }
-}
-
-static dim3 agnn_group_grid(int n, int h, int G) {
-  const long per = kBlock / G;
-  long blocks = ((long)n + per - 1) / per;
-  if (blocks > 16384) blocks = 16384;
-  return dim3((unsigned)(blocks < 1 ? 1 : blocks), h);
-}
-static dim3 agnn_wave_grid(int n, int h) {
-  const long want = ((long)n + kWavesPerBlock - 1) / kWavesPerBlock;
-  return dim3((unsigned)(want > (1 << 20) ? (1 << 20) : want), h);
-}
+};
 
 template <int PASS>
 static int launch_agnn_pass(const Agnn &a, bool cosine, bool v4, hipStream_t s) {
-  const int n = PASS == 2 ? a.n_cols : a.m;  // the form is chosen per pass, by the average degree of what it walks
-  if (n == 0) return 0;  // nothing to walk and nothing to write (a rectangular graph without rows / without columns)
-  const bool groups = low_degree(n, a.nnz);
-  return dispatch_cfg(a.f, v4, [&](auto cfg) {
-    using C = decltype(cfg);
-    auto go = [&](auto cos) {
-      constexpr bool COS = decltype(cos)::value;
-      if (groups) agnn_group_kernel<C, COS, PASS><<<agnn_group_grid(n, a.h, C::G), kBlock, 0, s>>>(a);
-      else agnn_wave_kernel<C, COS, PASS><<<agnn_wave_grid(n, a.h), kBlock, 0, s>>>(a);
-    };
-    if (cosine) go(std::true_type{});
-    else go(std::false_type{});
-    return launch_status();
-  });
+  if (cosine) return launch_pair_pass<AgnnOp<true>, PASS>(a, v4, s);
+  return launch_pair_pass<AgnnOp<false>, PASS>(a, v4, s);
 }
 
 static Agnn agnn_args(const Csr &g, const AgnnGraph &v, const float *X_row, const float *X_col) {

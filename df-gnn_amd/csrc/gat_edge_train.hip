@@ -17,7 +17,9 @@
 //
 // The structure is gt_bias_train.hip's, pass for pass -- forward, CSR backward pass, CSC backward pass; each as a wave per
 // row / column and, for low-degree sides (nnz < 8 n), as a group of G lanes per row / column with the cooperative switch
-// for long rows; two floats saved per (row, head); no atomics -- with GAT's rank-one logit in place of the dot product:
+// for long rows; two floats saved per (row, head); no atomics.  The kernels, their grids and the choice between the two
+// forms are the shared shell of dfgnn_pair_shell.hpp (GatEdgeOp below plugs into it); the per-row routines are this
+// file's own, with GAT's rank-one logit in place of the dot product:
 //   forward           a lane per edge forms the logit of a 64-edge tile (wave form); no key gather exists
 //   backward, CSR     gathers X_j once per edge for <dO_i, X_j> and sums delta_i over the edges (the forward's `out` is
 //                     not read); grad_attn_row from three running sums; grad_score, when the caller wants it, parked and
@@ -33,6 +35,7 @@
 // cover every edge) and has out = 0, delta = 0.  Saved between forward and backward: edge_max and edge_sum (and the caller's
 // randoms); the backward needs neither `out` nor anything of size nnz.
 #include "dfgnn_launch.hpp"
+#include "dfgnn_pair_shell.hpp"
 #include "dfgnn_rows.hpp"
 
 namespace dfgnn {
@@ -303,80 +306,24 @@ __device__ __forceinline__ void gte_bwd_col_group(const GatEdge &a, int j, int g
 }
 
 // ======================================================================================================================
-// kernels.  PASS: 0 forward, 1 backward CSR pass, 2 backward CSC pass.
+// the operator as dfgnn_pair_shell.hpp sees it: the kernels, their grids and the launch are there.
 // ======================================================================================================================
-template <class C, int PASS, bool COOP>
-__device__ __forceinline__ void gte_group_pass(const GatEdge &a, int r, int gid, int gl) {
-  if constexpr (PASS == 0) gte_fwd_row_group<C, COOP>(a, r, gid, gl);
-  else if constexpr (PASS == 1) gte_bwd_row_group<C, COOP>(a, r, gid, gl);
-  else gte_bwd_col_group<C, COOP>(a, r, gid, gl);
-}
-
-// general: a wave per row / column, grid-strided over the whole graph.  The forward works in 64-edge tiles through the
-// wave's LDS scratch; the backward passes are the COOP form of the group routines (no LDS).
-template <class C, int PASS>
-__global__ __launch_bounds__(kBlock) void gat_edge_wave_kernel(GatEdge a) {
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  a.at_head(blockIdx.y);
-  const int n = PASS == 2 ? a.n_cols : a.m;  // the extent this pass walks: rows, or (CSC pass) columns
-  const int beg = blockIdx.x * kWavesPerBlock + wave, step = gridDim.x * kWavesPerBlock;
-  if constexpr (PASS == 0) {
-    __shared__ __attribute__((aligned(16))) float lds[kWavesPerBlock * kScratchFloatsPerWave];
-    float *sw = lds + wave * kScratchFloatsPerWave;
-    int *sc = reinterpret_cast<int *>(sw + kWave);
-    for (int r = beg; r < n; r += step) gte_fwd_row_wave<C>(a, r, lane, sw, sc);
-  } else {
-    for (int r = beg; r < n; r += step) gte_group_pass<C, PASS, true>(a, r, lane / C::G, lane % C::G);
+constexpr int kGatEdgeGroupMaxDegree = 24;  // a lane-group wave with a longer row takes its rows cooperatively
+struct GatEdgeOp {
+  using Args = GatEdge;
+  static constexpr int kGroupMaxDegree = kGatEdgeGroupMaxDegree;
+  static constexpr bool kFwdTiles = true;
+  template <class C>
+  static __device__ __forceinline__ void fwd_row_wave(const Args &a, int r, int lane, float *sw, int *sc) {
+    gte_fwd_row_wave<C>(a, r, lane, sw, sc);
   }
-}
-
-// low-degree sides: a workgroup takes blocks of kBlock / G consecutive rows, one lane group per row -- unless a wave's
-// EPW rows include one of more than kGatEdgeGroupMaxDegree entries, which a single lane group would walk serially while the
-// rest of the wave waits: that wave takes its rows one after the other with all its groups on each (COOP).  The choice is
-// wave-uniform (ballot): no barrier, no LDS.  As gt_bias_group_kernel of gt_bias_train.hip, with the same threshold.
-constexpr int kGatEdgeGroupMaxDegree = 24;
-template <class C, int PASS>
-__global__ __launch_bounds__(kBlock) void gat_edge_group_kernel(GatEdge a) {
-  constexpr int G = C::G, R = kBlock / G;  // rows per block
-  const int gid = (threadIdx.x & (kWave - 1)) / G, gl = threadIdx.x % G, wave = threadIdx.x / kWave;
-  a.at_head(blockIdx.y);
-  const int *ptr = PASS == 2 ? a.col_ptr : a.row_ptr;
-  const int n = PASS == 2 ? a.n_cols : a.m;  // the extent this pass walks: rows, or (CSC pass) columns
-  for (int b0 = blockIdx.x * R; b0 < n; b0 += gridDim.x * R) {
-    const int r = b0 + threadIdx.x / G;
-    const int deg = r < n ? ptr[r + 1] - ptr[r] : 0;
-    if (__any(deg > kGatEdgeGroupMaxDegree)) {
-      for (int rr = b0 + wave * C::EPW; rr < min(n, b0 + (wave + 1) * C::EPW); ++rr)
-        gte_group_pass<C, PASS, true>(a, rr, gid, gl);
-    } else if (r < n) {
-      gte_group_pass<C, PASS, false>(a, r, gid, gl);
-    }
+  template <class C, int PASS, bool COOP>
+  static __device__ __forceinline__ void group_pass(const Args &a, int r, int gid, int gl) {
+    if constexpr (PASS == 0) gte_fwd_row_group<C, COOP>(a, r, gid, gl);
+    else if constexpr (PASS == 1) gte_bwd_row_group<C, COOP>(a, r, gid, gl);
+    else gte_bwd_col_group<C, COOP>(a, r, gid, gl);
   }
-}
-
-static dim3 gte_group_grid(int m, int h, int G) {
-  const long per = kBlock / G;
-  long blocks = ((long)m + per - 1) / per;
-  if (blocks > 16384) blocks = 16384;
-  return dim3((unsigned)(blocks < 1 ? 1 : blocks), h);
-}
-static dim3 gte_wave_grid(int m, int h) {
-  const long want = ((long)m + kWavesPerBlock - 1) / kWavesPerBlock;
-  return dim3((unsigned)(want > (1 << 20) ? (1 << 20) : want), h);
-}
-
-template <int PASS>
-static int launch_gat_edge_pass(const GatEdge &a, bool v4, hipStream_t s) {
-  const int n = PASS == 2 ? a.n_cols : a.m;  // the form is chosen per pass, by the average degree of what it walks
-  if (n == 0) return 0;  // nothing to walk and nothing to write (a rectangular graph without rows / without columns)
-  const bool groups = low_degree(n, a.nnz);
-  return dispatch_cfg(a.f, v4, [&](auto cfg) {
-    using C = decltype(cfg);
-    if (groups) gat_edge_group_kernel<C, PASS><<<gte_group_grid(n, a.h, C::G), kBlock, 0, s>>>(a);
-    else gat_edge_wave_kernel<C, PASS><<<gte_wave_grid(n, a.h), kBlock, 0, s>>>(a);
-    return launch_status();
-  });
-}
+};
 
 static GatEdge gat_edge_args(const Csr &g, const GatEdgeTerms &t, const float *X) {
   GatEdge a{};
@@ -392,7 +339,7 @@ int launch_gat_edge_fwd(const Csr &g, const GatEdgeTerms &t, const float *X, flo
                         hipStream_t s) {
   GatEdge a = gat_edge_args(g, t, X);
   a.outh = out; a.edge_max = edge_max; a.edge_sum = edge_sum;
-  return launch_gat_edge_pass<0>(a, (g.f % 4 == 0) && aligned16(X) && aligned16(out), s);
+  return launch_pair_pass<GatEdgeOp, 0>(a, (g.f % 4 == 0) && aligned16(X) && aligned16(out), s);
 }
 
 int launch_gat_edge_bwd(const Csr &g, const GatEdgeTerms &t, const int *col_ptr, const int *row_ind, const int *val_idx,
@@ -405,8 +352,8 @@ int launch_gat_edge_bwd(const Csr &g, const GatEdgeTerms &t, const int *col_ptr,
   a.grad_feath = grad_feat; a.grad_attn_row = grad_attn_row; a.grad_attn_col = grad_attn_col; a.grad_score = grad_score;
   // one layout for both passes, so that <dO_i, X_j> is summed in the same order on either side
   const bool v4 = (g.f % 4 == 0) && aligned16(X) && aligned16(grad_out) && aligned16(grad_feat);
-  if (int rc = launch_gat_edge_pass<1>(a, v4, s)) return rc;
-  return launch_gat_edge_pass<2>(a, v4, s);
+  if (int rc = launch_pair_pass<GatEdgeOp, 1>(a, v4, s)) return rc;
+  return launch_pair_pass<GatEdgeOp, 2>(a, v4, s);
 }
 
 }  // namespace dfgnn

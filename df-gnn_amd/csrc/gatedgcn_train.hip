@@ -16,7 +16,9 @@
 //
 // The structure is gatv2_edge_train.hip's and gt_gate_train.hip's -- forward, CSR backward pass, CSC backward pass; each as
 // a wave per row / column and, for low-degree graphs (nnz < 8 m on the side it walks), as a group of G lanes per row /
-// column with the cooperative switch for long rows; no atomics, fixed summation order -- with these differences:
+// column with the cooperative switch for long rows; no atomics, fixed summation order.  The kernels, their grids and the
+// choice between the two forms are the shared shell of dfgnn_pair_shell.hpp (GatedGcnOp below plugs into it); the per-row
+// routines are this file's own, with these differences:
 //   no row maximum, no dot product, no cross-lane sum: a lane's slice of an edge never meets another lane's.  The only
 //       exchange is the sum over the wave's lane groups at the end of a cooperative row (frag_reduce_groups), so the
 //       forward needs no 64-edge tiles either: its wave form is the cooperative group routine, and no kernel uses LDS
@@ -30,6 +32,7 @@
 // sigmoid: v_exp_f32 and v_rcp_f32.  exp(-z) overflows to +inf for z < -88.7 and 1 / (1 + inf) = 0: finite for any finite z.
 // An empty row: out = 0, den = 0, dXr = 0; an empty column: dXc = dV = 0.
 #include "dfgnn_launch.hpp"
+#include "dfgnn_pair_shell.hpp"
 
 namespace dfgnn {
 
@@ -353,72 +356,21 @@ __device__ __forceinline__ void ggc_bwd_col_group(const GatedGcn &a, int j, int 
 }
 
 // ======================================================================================================================
-// kernels.  PASS: 0 forward, 1 backward CSR pass, 2 backward CSC pass.
+// the operator as dfgnn_pair_shell.hpp sees it: the kernels, their grids and the launch are there.  No 64-edge tiles: the
+// forward's wave form is the COOP form of its group routine, like the backward passes' (no LDS).
 // ======================================================================================================================
-template <class C, int PASS, bool COOP>
-__device__ __forceinline__ void ggc_group_pass(const GatedGcn &a, int r, int gid, int gl) {
-  if constexpr (PASS == 0) ggc_fwd_row_group<C, COOP>(a, r, gid, gl);
-  else if constexpr (PASS == 1) ggc_bwd_row_group<C, COOP>(a, r, gid, gl);
-  else ggc_bwd_col_group<C, COOP>(a, r, gid, gl);
-}
-
-// general: a wave per row / column, grid-strided over the whole graph: the COOP form of the group routines (no LDS).
-template <class C, int PASS>
-__global__ __launch_bounds__(kBlock) void gatedgcn_wave_kernel(GatedGcn a) {
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  a.at_head(blockIdx.y);
-  const int n = PASS == 2 ? a.n_cols : a.m;  // the extent this pass walks: rows, or (CSC pass) columns
-  const int beg = blockIdx.x * kWavesPerBlock + wave, step = gridDim.x * kWavesPerBlock;
-  for (int r = beg; r < n; r += step) ggc_group_pass<C, PASS, true>(a, r, lane / C::G, lane % C::G);
-}
-
-// low-degree graphs: a workgroup takes blocks of kBlock / G consecutive rows, one lane group per row -- unless a wave's
-// EPW rows include one of more than kGatedGcnGroupMaxDegree entries, which a single lane group would walk serially while
-// the rest of the wave waits: that wave takes its rows one after the other with all its groups on each (COOP).  The choice
-// is wave-uniform (ballot): no barrier, no LDS.  As gt_gate_group_kernel, with the same threshold.
-constexpr int kGatedGcnGroupMaxDegree = 24;
-template <class C, int PASS>
-__global__ __launch_bounds__(kBlock) void gatedgcn_group_kernel(GatedGcn a) {
-  constexpr int G = C::G, R = kBlock / G;  // rows per block
-  const int gid = (threadIdx.x & (kWave - 1)) / G, gl = threadIdx.x % G, wave = threadIdx.x / kWave;
-  a.at_head(blockIdx.y);
-  const int *ptr = PASS == 2 ? a.col_ptr : a.row_ptr;
-  const int n = PASS == 2 ? a.n_cols : a.m;  // the extent this pass walks: rows, or (CSC pass) columns
-  for (int b0 = blockIdx.x * R; b0 < n; b0 += gridDim.x * R) {
-    const int r = b0 + threadIdx.x / G;
-    const int deg = r < n ? ptr[r + 1] - ptr[r] : 0;
-    if (__any(deg > kGatedGcnGroupMaxDegree)) {
-      for (int rr = b0 + wave * C::EPW; rr < min(n, b0 + (wave + 1) * C::EPW); ++rr)
-        ggc_group_pass<C, PASS, true>(a, rr, gid, gl);
-    } else if (r < n) {
-      ggc_group_pass<C, PASS, false>(a, r, gid, gl);
-    }
+constexpr int kGatedGcnGroupMaxDegree = 24;  // a lane-group wave with a longer row takes its rows cooperatively
+struct GatedGcnOp {
+  using Args = GatedGcn;
+  static constexpr int kGroupMaxDegree = kGatedGcnGroupMaxDegree;
+  static constexpr bool kFwdTiles = false;
+  template <class C, int PASS, bool COOP>
+  static __device__ __forceinline__ void group_pass(const Args &a, int r, int gid, int gl) {
+    if constexpr (PASS == 0) ggc_fwd_row_group<C, COOP>(a, r, gid, gl);
+    else if constexpr (PASS == 1) ggc_bwd_row_group<C, COOP>(a, r, gid, gl);
+    else ggc_bwd_col_group<C, COOP>(a, r, gid, gl);
   }
-}
-
-static dim3 ggc_group_grid(int m, int h, int G) {
-  const long per = kBlock / G;
-  long blocks = ((long)m + per - 1) / per;
-  if (blocks > 16384) blocks = 16384;
-  return dim3((unsigned)(blocks < 1 ? 1 : blocks), h);
-}
-static dim3 ggc_wave_grid(int m, int h) {
-  const long want = ((long)m + kWavesPerBlock - 1) / kWavesPerBlock;
-  return dim3((unsigned)(want > (1 << 20) ? (1 << 20) : want), h);
-}
-
-template <int PASS>
-static int launch_gatedgcn_pass(const GatedGcn &a, bool v4, hipStream_t s) {
-  const int n = PASS == 2 ? a.n_cols : a.m;  // the form is chosen per pass, by the average degree of what it walks
-  if (n == 0) return 0;  // nothing to walk and nothing to write (a rectangular graph without rows / without columns)
-  const bool groups = low_degree(n, a.nnz);
-  return dispatch_cfg(a.f, v4, [&](auto cfg) {
-    using C = decltype(cfg);
-    if (groups) gatedgcn_group_kernel<C, PASS><<<ggc_group_grid(n, a.h, C::G), kBlock, 0, s>>>(a);
-    else gatedgcn_wave_kernel<C, PASS><<<ggc_wave_grid(n, a.h), kBlock, 0, s>>>(a);
-    return launch_status();
-  });
-}
+};
 
 static GatedGcn gatedgcn_args(const Csr &g, const GatedGcnGraph &v, const float *X_row, const float *X_col, const float *V,
                               const float *E) {
@@ -436,7 +388,7 @@ int launch_gatedgcn_fwd(const Csr &g, const GatedGcnGraph &v, const float *X_row
   a.denh = den; a.outh = out; a.Zh = Z;
   const bool v4 = (g.f % 4 == 0) && aligned16(X_row) && aligned16(X_col) && aligned16(V) && aligned16(E) && aligned16(den) &&
                   aligned16(out) && aligned16(Z);
-  return launch_gatedgcn_pass<0>(a, v4, s);
+  return launch_pair_pass<GatedGcnOp, 0>(a, v4, s);
 }
 
 int launch_gatedgcn_bwd(const Csr &g, const GatedGcnGraph &v, const float *X_row, const float *X_col, const float *V,
@@ -453,8 +405,8 @@ int launch_gatedgcn_bwd(const Csr &g, const GatedGcnGraph &v, const float *X_row
   const bool v4 = (g.f % 4 == 0) && aligned16(X_row) && aligned16(X_col) && aligned16(V) && aligned16(E) && aligned16(out) &&
                   aligned16(den) && aligned16(grad_out) && aligned16(G) && aligned16(dX_row) && aligned16(dX_col) &&
                   aligned16(dV) && aligned16(dE) && aligned16(ws);
-  if (int rc = launch_gatedgcn_pass<1>(a, v4, s)) return rc;
-  return launch_gatedgcn_pass<2>(a, v4, s);
+  if (int rc = launch_pair_pass<GatedGcnOp, 1>(a, v4, s)) return rc;
+  return launch_pair_pass<GatedGcnOp, 2>(a, v4, s);
 }
 
 }  // namespace dfgnn

@@ -18,8 +18,9 @@
 //
 // The structure is gt_bias_train.hip's, pass for pass -- forward, CSR backward pass, CSC backward pass; each as a wave per
 // row / column and, for low-degree graphs (nnz < 8 m), as a group of G lanes per row / column with the cooperative switch
-// for long rows; two floats saved per (row, head); no atomics, fixed summation order -- and the code is a copy with E
-// worked in, so that the existing pairs' code objects stay as they are and this operator is one file:
+// for long rows; two floats saved per (row, head); no atomics, fixed summation order.  The kernels, their grids and the
+// choice between the two forms are the shared shell of dfgnn_pair_shell.hpp (GtEdgeOp below plugs into it); the per-row
+// routines are this file's own, a copy with E worked in, so that the existing pairs' code objects stay as they are:
 //   forward           one more fragment load per edge, of E_e at the edge's own slot (no index), added to the K_j and V_j
 //                     fragments before the dot product and the accumulate.  The wave form's 64-edge tiles go through
 //                     gte_tile_dots / gte_spmm_accum below, the tile routines of dfgnn_rows.hpp with that load
@@ -32,6 +33,7 @@
 // recomputes is the forward's to the bit; with E = 0 every output equals gt_train.hip's.
 // An empty row: out = 0, row_max = -1e38, row_sum = 0, dQ = 0.
 #include "dfgnn_launch.hpp"
+#include "dfgnn_pair_shell.hpp"
 #include "dfgnn_rows.hpp"
 
 namespace dfgnn {
@@ -373,80 +375,24 @@ __device__ __forceinline__ void gte_bwd_col_group(const GtEdge &a, int j, int gi
 }
 
 // ======================================================================================================================
-// kernels.  PASS: 0 forward, 1 backward CSR pass, 2 backward CSC pass.
+// the operator as dfgnn_pair_shell.hpp sees it: the kernels, their grids and the launch are there.
 // ======================================================================================================================
-template <class C, int PASS, bool COOP>
-__device__ __forceinline__ void gte_group_pass(const GtEdge &a, int r, int gid, int gl) {
-  if constexpr (PASS == 0) gte_fwd_row_group<C, COOP>(a, r, gid, gl);
-  else if constexpr (PASS == 1) gte_bwd_row_group<C, COOP>(a, r, gid, gl);
-  else gte_bwd_col_group<C, COOP>(a, r, gid, gl);
-}
-
-// general: a wave per row / column, grid-strided over the whole graph.  The forward works in 64-edge tiles through the
-// wave's LDS scratch; the backward passes are the COOP form of the group routines (no LDS).
-template <class C, int PASS>
-__global__ __launch_bounds__(kBlock) void gt_edge_wave_kernel(GtEdge a) {
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  a.at_head(blockIdx.y);
-  const int n = PASS == 2 ? a.n_cols : a.m;  // the extent this pass walks: rows, or (CSC pass) columns
-  const int beg = blockIdx.x * kWavesPerBlock + wave, step = gridDim.x * kWavesPerBlock;
-  if constexpr (PASS == 0) {
-    __shared__ __attribute__((aligned(16))) float lds[kWavesPerBlock * kScratchFloatsPerWave];
-    float *sw = lds + wave * kScratchFloatsPerWave;
-    int *sc = reinterpret_cast<int *>(sw + kWave);
-    for (int r = beg; r < n; r += step) gte_fwd_row_wave<C>(a, r, lane, sw, sc);
-  } else {
-    for (int r = beg; r < n; r += step) gte_group_pass<C, PASS, true>(a, r, lane / C::G, lane % C::G);
+constexpr int kGtEdgeGroupMaxDegree = 24;  // a lane-group wave with a longer row takes its rows cooperatively
+struct GtEdgeOp {
+  using Args = GtEdge;
+  static constexpr int kGroupMaxDegree = kGtEdgeGroupMaxDegree;
+  static constexpr bool kFwdTiles = true;
+  template <class C>
+  static __device__ __forceinline__ void fwd_row_wave(const Args &a, int r, int lane, float *sw, int *sc) {
+    gte_fwd_row_wave<C>(a, r, lane, sw, sc);
   }
-}
-
-// low-degree graphs: a workgroup takes blocks of kBlock / G consecutive rows, one lane group per row -- unless a wave's
-// EPW rows include one of more than kGtEdgeGroupMaxDegree entries, which a single lane group would walk serially while the
-// rest of the wave waits: that wave takes its rows one after the other with all its groups on each (COOP).  The choice is
-// wave-uniform (ballot): no barrier, no LDS.  As gt_train_group_kernel of gt_train.hip, with the same threshold.
-constexpr int kGtEdgeGroupMaxDegree = 24;
-template <class C, int PASS>
-__global__ __launch_bounds__(kBlock) void gt_edge_group_kernel(GtEdge a) {
-  constexpr int G = C::G, R = kBlock / G;  // rows per block
-  const int gid = (threadIdx.x & (kWave - 1)) / G, gl = threadIdx.x % G, wave = threadIdx.x / kWave;
-  a.at_head(blockIdx.y);
-  const int *ptr = PASS == 2 ? a.col_ptr : a.row_ptr;
-  const int n = PASS == 2 ? a.n_cols : a.m;  // the extent this pass walks: rows, or (CSC pass) columns
-  for (int b0 = blockIdx.x * R; b0 < n; b0 += gridDim.x * R) {
-    const int r = b0 + threadIdx.x / G;
-    const int deg = r < n ? ptr[r + 1] - ptr[r] : 0;
-    if (__any(deg > kGtEdgeGroupMaxDegree)) {
-      for (int rr = b0 + wave * C::EPW; rr < min(n, b0 + (wave + 1) * C::EPW); ++rr)
-        gte_group_pass<C, PASS, true>(a, rr, gid, gl);
-    } else if (r < n) {
-      gte_group_pass<C, PASS, false>(a, r, gid, gl);
-    }
+  template <class C, int PASS, bool COOP>
+  static __device__ __forceinline__ void group_pass(const Args &a, int r, int gid, int gl) {
+    if constexpr (PASS == 0) gte_fwd_row_group<C, COOP>(a, r, gid, gl);
+    else if constexpr (PASS == 1) gte_bwd_row_group<C, COOP>(a, r, gid, gl);
+    else gte_bwd_col_group<C, COOP>(a, r, gid, gl);
   }
-}
-
-static dim3 gte_group_grid(int m, int h, int G) {
-  const long per = kBlock / G;
-  long blocks = ((long)m + per - 1) / per;
-  if (blocks > 16384) blocks = 16384;
-  return dim3((unsigned)(blocks < 1 ? 1 : blocks), h);
-}
-static dim3 gte_wave_grid(int m, int h) {
-  const long want = ((long)m + kWavesPerBlock - 1) / kWavesPerBlock;
-  return dim3((unsigned)(want > (1 << 20) ? (1 << 20) : want), h);
-}
-
-template <int PASS>
-static int launch_gt_edge_pass(const GtEdge &a, bool v4, hipStream_t s) {
-  const int n = PASS == 2 ? a.n_cols : a.m;  // the form is chosen per pass, by the average degree of what it walks
-  if (n == 0) return 0;  // nothing to walk and nothing to write (a rectangular graph without rows / without columns)
-  const bool groups = low_degree(n, a.nnz);
-  return dispatch_cfg(a.f, v4, [&](auto cfg) {
-    using C = decltype(cfg);
-    if (groups) gt_edge_group_kernel<C, PASS><<<gte_group_grid(n, a.h, C::G), kBlock, 0, s>>>(a);
-    else gt_edge_wave_kernel<C, PASS><<<gte_wave_grid(n, a.h), kBlock, 0, s>>>(a);
-    return launch_status();
-  });
-}
+};
 
 static GtEdge gt_edge_args(const Csr &g, const float *E, const float *Q, const float *K, const float *V) {
   GtEdge a{};
@@ -461,7 +407,7 @@ int launch_gt_edge_fwd(const Csr &g, const float *E, const float *Q, const float
   GtEdge a = gt_edge_args(g, E, Q, K, V);
   a.outh = out; a.row_max = row_max; a.row_sum = row_sum;
   const bool v4 = (g.f % 4 == 0) && aligned16(E) && aligned16(Q) && aligned16(K) && aligned16(V) && aligned16(out);
-  return launch_gt_edge_pass<0>(a, v4, s);
+  return launch_pair_pass<GtEdgeOp, 0>(a, v4, s);
 }
 
 int launch_gt_edge_bwd_rows(const Csr &g, const float *E, const float *Q, const float *K, const float *V,
@@ -472,7 +418,7 @@ int launch_gt_edge_bwd_rows(const Csr &g, const float *E, const float *Q, const 
   a.row_max = const_cast<float *>(row_max); a.row_sum = const_cast<float *>(row_sum);
   const bool v4 = (g.f % 4 == 0) && aligned16(E) && aligned16(Q) && aligned16(K) && aligned16(V) && aligned16(out) &&
                   aligned16(grad_out) && aligned16(dQ) && aligned16(dE);
-  return launch_gt_edge_pass<1>(a, v4, s);
+  return launch_pair_pass<GtEdgeOp, 1>(a, v4, s);
 }
 
 int launch_gt_edge_bwd_cols(const Csr &g, const float *E, const int *col_ptr, const int *row_ind, const int *val_idx,
@@ -485,7 +431,7 @@ int launch_gt_edge_bwd_cols(const Csr &g, const float *E, const int *col_ptr, co
   a.delta = const_cast<float *>(delta);
   const bool v4 = (g.f % 4 == 0) && aligned16(E) && aligned16(Q) && aligned16(K) && aligned16(V) &&
                   aligned16(grad_out) && aligned16(dK) && aligned16(dV);
-  return launch_gt_edge_pass<2>(a, v4, s);
+  return launch_pair_pass<GtEdgeOp, 2>(a, v4, s);
 }
 
 }  // namespace dfgnn

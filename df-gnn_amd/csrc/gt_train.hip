@@ -23,7 +23,10 @@
 // CSC pass takes its loop bounds, its grid and its form (low_degree(n_cols, nnz)) from the column extent, the other two
 // from m.  A neighbour-sampled block (96 seeds x 257 sampled nodes, fanout 10) runs a wave per row and a lane group per
 // column.
+// This file holds the per-row routines and the launch functions; the kernels that call the former, their grids and the
+// choice between the two forms are the shared shell of dfgnn_pair_shell.hpp, which GtTrainOp below plugs into.
 #include "dfgnn_launch.hpp"
+#include "dfgnn_pair_shell.hpp"
 #include "dfgnn_rows.hpp"
 
 namespace dfgnn {
@@ -250,80 +253,24 @@ __device__ __forceinline__ void gt_bwd_col_group(const GtTrain &a, int j, int gi
 }
 
 // ======================================================================================================================
-// kernels.  PASS: 0 forward, 1 backward CSR pass, 2 backward CSC pass.
+// the operator as dfgnn_pair_shell.hpp sees it: the kernels, their grids and the launch are there.
 // ======================================================================================================================
-template <class C, int PASS, bool COOP>
-__device__ __forceinline__ void gt_group_pass(const GtTrain &a, int r, int gid, int gl) {
-  if constexpr (PASS == 0) gt_fwd_row_group<C, COOP>(a, r, gid, gl);
-  else if constexpr (PASS == 1) gt_bwd_row_group<C, COOP>(a, r, gid, gl);
-  else gt_bwd_col_group<C, COOP>(a, r, gid, gl);
-}
-
-// general: a wave per row / column, grid-strided over the whole graph.  The forward works in 64-edge tiles through the
-// wave's LDS scratch; the backward passes are the COOP form of the group routines (no LDS).
-template <class C, int PASS>
-__global__ __launch_bounds__(kBlock) void gt_train_wave_kernel(GtTrain a) {
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  a.at_head(blockIdx.y);
-  const int n = PASS == 2 ? a.n_cols : a.m;  // the extent this pass walks: rows, or (CSC pass) columns
-  const int beg = blockIdx.x * kWavesPerBlock + wave, step = gridDim.x * kWavesPerBlock;
-  if constexpr (PASS == 0) {
-    __shared__ __attribute__((aligned(16))) float lds[kWavesPerBlock * kScratchFloatsPerWave];
-    float *sw = lds + wave * kScratchFloatsPerWave;
-    int *sc = reinterpret_cast<int *>(sw + kWave);
-    for (int r = beg; r < n; r += step) gt_fwd_row_wave<C>(a, r, lane, sw, sc);
-  } else {
-    for (int r = beg; r < n; r += step) gt_group_pass<C, PASS, true>(a, r, lane / C::G, lane % C::G);
+constexpr int kGtGroupMaxDegree = 24;  // a lane-group wave with a longer row takes its rows cooperatively
+struct GtTrainOp {
+  using Args = GtTrain;
+  static constexpr int kGroupMaxDegree = kGtGroupMaxDegree;
+  static constexpr bool kFwdTiles = true;
+  template <class C>
+  static __device__ __forceinline__ void fwd_row_wave(const Args &a, int r, int lane, float *sw, int *sc) {
+    gt_fwd_row_wave<C>(a, r, lane, sw, sc);
   }
-}
-
-// low-degree graphs: a workgroup takes blocks of kBlock / G consecutive rows, one lane group per row -- unless a wave's
-// EPW rows include one of more than kGtGroupMaxDegree entries (a hub of a citation graph), which a single lane group
-// would walk serially while the rest of the wave waits: that wave takes its rows one after the other with all its
-// groups on each (COOP).  The choice is wave-uniform (ballot): no barrier, no LDS.  As group_row_loop of gt_lowdeg.hip.
-constexpr int kGtGroupMaxDegree = 24;
-template <class C, int PASS>
-__global__ __launch_bounds__(kBlock) void gt_train_group_kernel(GtTrain a) {
-  constexpr int G = C::G, R = kBlock / G;  // rows per block
-  const int gid = (threadIdx.x & (kWave - 1)) / G, gl = threadIdx.x % G, wave = threadIdx.x / kWave;
-  a.at_head(blockIdx.y);
-  const int *ptr = PASS == 2 ? a.col_ptr : a.row_ptr;
-  const int n = PASS == 2 ? a.n_cols : a.m;  // the extent this pass walks: rows, or (CSC pass) columns
-  for (int b0 = blockIdx.x * R; b0 < n; b0 += gridDim.x * R) {
-    const int r = b0 + threadIdx.x / G;
-    const int deg = r < n ? ptr[r + 1] - ptr[r] : 0;
-    if (__any(deg > kGtGroupMaxDegree)) {
-      for (int rr = b0 + wave * C::EPW; rr < min(n, b0 + (wave + 1) * C::EPW); ++rr)
-        gt_group_pass<C, PASS, true>(a, rr, gid, gl);
-    } else if (r < n) {
-      gt_group_pass<C, PASS, false>(a, r, gid, gl);
-    }
+  template <class C, int PASS, bool COOP>
+  static __device__ __forceinline__ void group_pass(const Args &a, int r, int gid, int gl) {
+    if constexpr (PASS == 0) gt_fwd_row_group<C, COOP>(a, r, gid, gl);
+    else if constexpr (PASS == 1) gt_bwd_row_group<C, COOP>(a, r, gid, gl);
+    else gt_bwd_col_group<C, COOP>(a, r, gid, gl);
   }
-}
-
-static dim3 gt_group_grid(int m, int h, int G) {
-  const long per = kBlock / G;
-  long blocks = ((long)m + per - 1) / per;
-  if (blocks > 16384) blocks = 16384;
-  return dim3((unsigned)(blocks < 1 ? 1 : blocks), h);
-}
-static dim3 gt_wave_grid(int m, int h) {
-  const long want = ((long)m + kWavesPerBlock - 1) / kWavesPerBlock;
-  return dim3((unsigned)(want > (1 << 20) ? (1 << 20) : want), h);
-}
-
-template <int PASS>
-static int launch_gt_train_pass(const GtTrain &a, bool v4, hipStream_t s) {
-  const int n = PASS == 2 ? a.n_cols : a.m;  // the form is chosen per pass, by the average degree of what it walks
-  if (n == 0) return 0;  // nothing to walk and nothing to write (a rectangular graph without rows / without columns)
-  const bool groups = low_degree(n, a.nnz);
-  return dispatch_cfg(a.f, v4, [&](auto cfg) {
-    using C = decltype(cfg);
-    if (groups) gt_train_group_kernel<C, PASS><<<gt_group_grid(n, a.h, C::G), kBlock, 0, s>>>(a);
-    else gt_train_wave_kernel<C, PASS><<<gt_wave_grid(n, a.h), kBlock, 0, s>>>(a);
-    return launch_status();
-  });
-}
+};
 
 static GtTrain gt_train_args(const Csr &g, const float *Q, const float *K, const float *V) {
   GtTrain a{};
@@ -337,7 +284,8 @@ int launch_gt_train_fwd(const Csr &g, const float *Q, const float *K, const floa
                         float *out, hipStream_t s) {
   GtTrain a = gt_train_args(g, Q, K, V);
   a.outh = out; a.row_max = row_max; a.row_sum = row_sum;
-  return launch_gt_train_pass<0>(a, (g.f % 4 == 0) && aligned16(Q) && aligned16(K) && aligned16(V) && aligned16(out), s);
+  const bool v4 = (g.f % 4 == 0) && aligned16(Q) && aligned16(K) && aligned16(V) && aligned16(out);
+  return launch_pair_pass<GtTrainOp, 0>(a, v4, s);
 }
 
 int launch_gt_train_bwd_rows(const Csr &g, const float *Q, const float *K, const float *V, const float *out,
@@ -348,7 +296,7 @@ int launch_gt_train_bwd_rows(const Csr &g, const float *Q, const float *K, const
   a.row_max = const_cast<float *>(row_max); a.row_sum = const_cast<float *>(row_sum);
   const bool v4 = (g.f % 4 == 0) && aligned16(Q) && aligned16(K) && aligned16(V) && aligned16(out) &&
                   aligned16(grad_out) && aligned16(dQ);
-  return launch_gt_train_pass<1>(a, v4, s);
+  return launch_pair_pass<GtTrainOp, 1>(a, v4, s);
 }
 
 int launch_gt_train_bwd_cols(const Csr &g, const int *col_ptr, const int *row_ind, const int *val_idx, const float *Q,
@@ -361,7 +309,7 @@ int launch_gt_train_bwd_cols(const Csr &g, const int *col_ptr, const int *row_in
   a.delta = const_cast<float *>(delta);
   const bool v4 = (g.f % 4 == 0) && aligned16(Q) && aligned16(K) && aligned16(V) && aligned16(grad_out) &&
                   aligned16(dK) && aligned16(dV);
-  return launch_gt_train_pass<2>(a, v4, s);
+  return launch_pair_pass<GtTrainOp, 2>(a, v4, s);
 }
 
 }  // namespace dfgnn
