@@ -5,7 +5,7 @@ import torch
 import torch.nn as nn
 
 import fused_gtconv as fused_gt
-from DFGNN.operators.fused_gtconv import SegmentMHABiasFuse, SegmentMHAFuse
+from DFGNN.operators.fused_gtconv import SegmentMHABiasFuse, SegmentMHAFuse, SegmentMHATBiasFuse
 
 
 def segment_offsets(segments, device):
@@ -35,20 +35,33 @@ class GlobalMHA(nn.Module):
         self.v_proj = nn.Linear(in_size, out_size)
         self.out_proj = nn.Linear(out_size, out_size)
 
-    def forward(self, h, seg_ptr, fuse=True, bias=None):
+    def forward(self, h, seg_ptr, fuse=True, bias=None, pair_types=None, pair_table=None):
         """h [N, in]; seg_ptr: int32[n_seg + 1] offsets (a tensor kept across layers and steps is looked up, not rebuilt) or
         the batch's graph sizes.  bias: None or fp32 [heads, sum of n_g^2], added to the logits -- per head the graphs'
-        packed row-major n_g x n_g blocks one after another (PairBias makes one from pair types).  fuse=False, or a head
-        shape the fused pair does not serve: plain torch, graph by graph."""
+        packed row-major n_g x n_g blocks one after another (PairBias makes one from pair types).  pair_types [sum of n_g^2]
+        (integers, best uint8) with pair_table fp32 [T, heads] instead of bias: the same bias, table.t()[:, pair_types],
+        looked up inside the fused kernels for T <= 256 -- no plane is built and the table's gradient is summed there.
+        fuse=False, or a head shape the fused pair does not serve: plain torch, graph by graph."""
+        if (pair_types is None) != (pair_table is None):
+            raise ValueError("pair_types and pair_table go together")
+        if pair_types is not None and bias is not None:
+            raise ValueError("give either bias or pair_types with pair_table, not both")
         seg_ptr = segment_offsets(seg_ptr, h.device)
         n = len(h)
         q, k, v = (p(h).reshape(n, self.num_heads, self.head_dim) for p in (self.q_proj, self.k_proj, self.v_proj))
         if fuse and h.is_cuda and fused_gt.segment_mha_applies(self.num_heads, self.head_dim):
-            if bias is None:
+            if pair_types is not None:
+                if pair_table.size(0) <= fused_gt.SEGMENT_TBIAS_MAX_TYPES:
+                    pair_types = pair_types.to(torch.uint8)   # (no host read; a no-op for uint8)
+                out = SegmentMHATBiasFuse(seg_ptr, q.contiguous(), k.contiguous(), v.contiguous(), pair_types.contiguous(),
+                                          pair_table, self.scaling)
+            elif bias is None:
                 out = SegmentMHAFuse(seg_ptr, q.contiguous(), k.contiguous(), v.contiguous(), self.scaling)
             else:
                 out = SegmentMHABiasFuse(seg_ptr, q.contiguous(), k.contiguous(), v.contiguous(), bias.contiguous(), self.scaling)
         else:
+            if pair_types is not None:
+                bias = pair_table.t()[:, pair_types.long()]
             out = self.forward_plain(seg_ptr, q, k, v, bias)
         return self.out_proj(out.reshape(n, -1))
 

@@ -163,6 +163,44 @@ def SegmentMHABiasFuse(seg_ptr, Q, K, V, bias, scale=1.0):
     return FusedSegmentMHABiasFunction.apply(bounds, row_off, Q, K, V, bias, scale)
 
 
+class FusedSegmentMHATBiasFunction(torch.autograd.Function):
+    """FusedSegmentMHABiasFunction with the bias looked up in the kernels: table[T, h] by the pair's type
+    (include/dfgnn_segment_tbias.h).  Saved between forward and backward: Q, K, V, the types, the table and the row statistics;
+    no plane [h, n_pairs] exists at any point.  dtable [T, h] is summed by the kernels, without atomics, only when the table
+    requires a gradient."""
+
+    @staticmethod
+    def forward(ctx, bounds, row_off, Q, K, V, types, table, scale):
+        out, row_max, row_sum = fused_gt.segment_mha_tbias_forward(bounds, row_off, types, table, Q, K, V, scale)
+        ctx.save_for_backward(bounds, row_off, Q, K, V, types, table, row_max, row_sum)
+        ctx.scale = scale
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        bounds, row_off, Q, K, V, types, table, row_max, row_sum = ctx.saved_tensors
+        dQ, dK, dV, dtable = fused_gt.segment_mha_tbias_backward(bounds, row_off, types, table, Q, K, V, row_max, row_sum,
+                                                                 grad_out.contiguous(), ctx.scale,
+                                                                 need_dtable=ctx.needs_input_grad[6])
+        return None, None, dQ, dK, dV, None, dtable, None
+
+
+def SegmentMHATBiasFuse(seg_ptr, Q, K, V, types, table, scale=1.0):
+    """SegmentMHABiasFuse with bias[head, p] = table[min(types[p], T - 1), head]: types uint8 [n_pairs] in the layout of one
+    bias plane, shared by all heads, table fp32 [T, h] with finite values, T <= 256.  The gradient goes to Q, K, V and, where
+    it requires one, to table.  More than 256 types, or types of another dtype: the bias is materialised and
+    SegmentMHABiasFuse runs."""
+    if table.size(0) > fused_gt.SEGMENT_TBIAS_MAX_TYPES or types.dtype != torch.uint8:
+        return SegmentMHABiasFuse(seg_ptr, Q, K, V, table.t()[:, types.long()].contiguous(), scale)
+    m = Q.size(0)
+    bounds = fused_gt.segment_bounds(seg_ptr, m)
+    _, row_off = fused_gt.segment_pair_rows(seg_ptr, m)
+    table = table.contiguous()
+    if not (torch.is_grad_enabled() and (Q.requires_grad or K.requires_grad or V.requires_grad or table.requires_grad)):
+        return fused_gt.segment_mha_tbias_inference(bounds, row_off, types, table, Q, K, V, scale)
+    return FusedSegmentMHATBiasFunction.apply(bounds, row_off, Q, K, V, types, table, scale)
+
+
 # ---- AGNN / dot-product attention with tied keys and values (this build's addition; fused_gtconv.agnn_*) -----------------
 def AGNNConvFuse_inference(row_ptr, col_ind, beta, X_row, X_col, cosine=True):
     """-> out[m, h, f] = softmax_j(beta[h] cos(X_row_i, X_col_j)) X_col_j (cosine=False: beta[h] <X_row_i, X_col_j>); beta

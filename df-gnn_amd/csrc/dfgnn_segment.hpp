@@ -33,6 +33,16 @@
 // key tile (one 16-byte load wherever the row covers all four), the lane of a key strip owns one key of four queries, whose
 // offsets are staged with the other per-row words.  A pair the mask removes is never read; dbias = dS is stored by the dQ
 // kernel's second pass under the same mask.  The logit is fma(S, c, b) in all four places that form one.
+//
+// TYPED BIAS (include/dfgnn_segment_tbias.h): b = B[min(types[row_off_i + j - lo_i], T - 1), head], one byte per
+// pair shared by all heads.  The head's column of B is staged once per workgroup into LDS behind the tile (seg_table_stage);
+// a lane of a query strip reads the 4 types of its 4 keys as ONE dword from a byte-aligned address (byte loads at a row's
+// ends), a lane of a key strip reads one byte per query; every lookup is one LDS read.  The same fma forms the logit, so
+// everything but dB equals the plane pair's bits.  dB comes from the dS registers of the dQ kernel's second pass, without
+// atomics: every wave owns a table tab[T][W] in LDS, lane l adds to slot t W + (l mod W) with a plain read, add and write
+// (W = 64: a slot and a bank of its own; smaller W for larger T: the 64 / W lanes of a slot take turns, a wave's DS
+// operations execute in issue order), the workgroup folds slots and waves in a fixed order into one partial [T] per work
+// item, and segment_tbias_reduce_kernel sums the partials of a head in a fixed order.
 #pragma once
 #include "dfgnn_dense.hpp"
 #include "dfgnn_launch.hpp"
@@ -54,6 +64,7 @@ struct SegCfg {
   static constexpr int kLds = kSegFixedLds + segment_tile_bytes(F, TR, ROW_WORDS);
   static_assert(TR % 32 == 0 && kLds <= kBlockLdsBudget, "a tile is whole 32-row k-blocks inside the LDS budget");
 };
+enum class SegKind { None, Plane, Typed };  // the bias of a logit: none, read from a plane, looked up by the pair's type
 constexpr int kSegCapFwd = 8192, kSegCapBwd = 4096;
 template <int FR> using SegFwdCfg = SegCfg<FR, 0, kSegCapFwd>;
 template <int FR> using SegDqCfg = SegCfg<FR, 0, kSegCapBwd>;
@@ -192,6 +203,108 @@ __device__ __forceinline__ void seg_bias_store4(float *__restrict__ dbias, long 
   }
 }
 
+// ---- the typed pair bias ----------------------------------------------------------------------------------------------
+constexpr int kSegMaxTypes = 256;                    // a type is a byte
+constexpr int kSegTabBytes = 4 * kSegMaxTypes;       // the head's staged column of B, behind the tile of every typed kernel
+constexpr int kSegWaveTabFloats = 3072;              // floats of a wave's dB table at most: T W
+// slots per type of a wave's dB table: the widest power of two that keeps T W inside kSegWaveTabFloats, by T alone
+constexpr int seg_tbias_slots(int T) { return T <= 48 ? 64 : T <= 96 ? 32 : T <= 192 ? 16 : 8; }
+static_assert(48 * seg_tbias_slots(48) <= kSegWaveTabFloats && 96 * seg_tbias_slots(96) <= kSegWaveTabFloats &&
+                  192 * seg_tbias_slots(192) <= kSegWaveTabFloats && 256 * seg_tbias_slots(256) <= kSegWaveTabFloats,
+              "a wave's dB table fits its share of LDS at every threshold");
+struct SegTBias {
+  const long long *row_off;    // int64[m]: offset of pair (i, lo_i) in types
+  long long n_pairs;           // length of types
+  const unsigned char *types;  // uint8[n_pairs], one plane for all heads
+  const float *table;          // B, fp32[T, h]
+  int T;
+  float *ws;                   // (dQ kernel) the dB partials [windows, T, h], or null: the table is frozen
+  int W, wshift;               // (dQ kernel) seg_tbias_slots(T) and its log2
+};
+// seg_bias_at without the head: element at + j of types is pair (row, j)
+__device__ __forceinline__ long long seg_types_at(const SegTBias &tb, int row, int lo, int hi) {
+  const long long room = tb.n_pairs - (long long)(hi - lo);
+  if (room < 0) return kSegNoBias;
+  return min(max(tb.row_off[row], 0ll), room) - lo;
+}
+struct __attribute__((packed)) SegB4U {  // 4 bytes at any address
+  unsigned v;
+};
+// the types of keys j0 .. j0 + 3 of this lane's row, key j0 + r in byte r: one 4-byte access where the row covers all four,
+// else only the pairs in [lo, hi) (the other bytes are 0)
+__device__ __forceinline__ unsigned seg_types_load4(const unsigned char *__restrict__ types, long long at, int j0, int lo, int hi) {
+  unsigned x = 0;
+  if (at == kSegNoBias) return x;
+  if (j0 >= lo && j0 + 4 <= hi) {
+    x = reinterpret_cast<const SegB4U *>(types + at + j0)->v;
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (j0 + r >= lo && j0 + r < hi) x |= (unsigned)types[at + j0 + r] << (8 * r);
+  }
+  return x;
+}
+// the head's column of B -> tab[0 .. T); visible after the next workgroup barrier (seg_tile_loop has two before its first fn)
+__device__ __forceinline__ void seg_table_stage(float *tab, const SegTBias &tb, int head, int h) {
+  const int tid = opaque_tid();
+  if (tid < tb.T) tab[tid] = tb.table[(size_t)tid * h + head];
+}
+// bias of the pair whose type is byte r of x (clamped to T - 1: no address outside tab)
+__device__ __forceinline__ float seg_table_at(const float *tab, unsigned x, int r, int T) {
+  return tab[min((int)((x >> (8 * r)) & 255u), T - 1)];
+}
+// what seg_recompute_p needs for KIND == Typed, and the tile's packed types it hands back for the dB sums
+struct SegTypedLane {
+  const unsigned char *types;
+  const float *tab;
+  int T;
+  long long at;  // seg_types_at of the lane's row
+};
+
+// dB of a tile: lane l adds dS of its 4 NT pairs to slot type W + (l mod W) of its wave's table, a plain read, add and write.
+// The 64 / W lanes that share a slot take turns, round after round; within a round a lane's slots are its own, and a wave's
+// DS operations execute in issue order, so a round sees what the rounds before it wrote (wave_sync keeps the compiler from
+// moving them).  Masked pairs hold dS = 0 and type 0: they add nothing.
+template <int NT>
+__device__ __forceinline__ void seg_dtable_add(float *wtab, const SegTBias &tb, const f32x4 (&dS)[NT], const unsigned (&ty)[NT],
+                                               const SegStrip &st, int t, bool nobias, const LaneIds &L) {
+  const int lane = L.mi + 16 * L.mq, turn = lane >> tb.wshift;
+  float *mine = wtab + (lane & (tb.W - 1));
+  for (int round = 0; round < (kWave >> tb.wshift); ++round) {
+    if (turn == round) {
+#pragma unroll
+      for (int jt = 0; jt < NT; ++jt)
+        if (st.sees(t + 16 * jt, 16)) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            float *p = mine + (min((int)((ty[jt] >> (8 * r)) & 255u), tb.T - 1) << tb.wshift);
+            *p += nobias ? 0.f : dS[jt][r];
+          }
+        }
+    }
+    wave_sync();
+  }
+}
+// the work item's partial: every wave folds the W slots of its types (lane l the types l, l + 64, ..: each read of a round
+// hits 64 banks, the start rotated by the type), then the first T threads add the 8 waves and store [T] with stride h
+__device__ __forceinline__ void seg_dtable_fold(float *tabs, const SegTBias &tb, float *__restrict__ part, int h) {
+  const int tid = opaque_tid(), lane = tid & (kWave - 1), per = tb.T << tb.wshift;
+  float *wtab = tabs + (tid / kWave) * per;
+  wave_sync();
+  for (int ty = lane; ty < tb.T; ty += kWave) {
+    float s = 0.f;
+    for (int w = 0; w < tb.W; ++w) s += wtab[(ty << tb.wshift) + ((w + ty) & (tb.W - 1))];
+    wtab[ty << tb.wshift] = s;
+  }
+  lds_barrier();
+  if (tid < tb.T) {
+    float s = 0.f;
+#pragma unroll
+    for (int wv = 0; wv < kDenseWaves; ++wv) s += tabs[wv * per + (tid << tb.wshift)];
+    part[(size_t)tid * h] = s;
+  }
+}
+
 // accumulator tiles of a strip -> its global rows (whole lines; the padded width tile by tile)
 template <int FR, int FT>
 __device__ __forceinline__ void seg_store(const f32x4 (&acc)[FT], float scale, float *__restrict__ base, unsigned hf,
@@ -212,12 +325,12 @@ __device__ __forceinline__ void seg_cols_mma(f32x4 (&acc)[NFT], const h16 *ihi, 
 }
 
 // ---- forward ----------------------------------------------------------------------------------------------------------
-template <int FR, bool BIAS = false>
+template <int FR, SegKind KIND = SegKind::None, class SB = SegBias>
 __device__ __forceinline__ void segment_fwd_body(float *lds, int m, int h, float scale, const int *__restrict__ bounds,
                                                  const float *__restrict__ Q, const float *__restrict__ K,
                                                  const float *__restrict__ V, float *__restrict__ out,
                                                  float *__restrict__ row_max, float *__restrict__ row_sum,
-                                                 const SegBias &sb = SegBias{}) {
+                                                 const SB &sb = SB{}) {
   using C = SegFwdCfg<FR>;
   constexpr int F = C::F, FT = C::FT, NT = C::NT, TR = C::TR;
   const int head = blockIdx.y, w0 = blockIdx.x * kSegWindow;
@@ -229,8 +342,13 @@ __device__ __forceinline__ void segment_fwd_body(float *lds, int m, int h, float
   seg_rows_load<FR>(q, Q + hoff, hf, st.row, m, L);
   float mrun = -INFINITY, lrun = 0.f;
   long long bat = kSegNoBias;
-  if constexpr (BIAS)
+  if constexpr (KIND == SegKind::Plane)
     if (st.row < m) bat = seg_bias_at(sb, head, st.row, st.lo, st.hi);
+  [[maybe_unused]] float *tab = lds + C::kLds / 4;  // (Typed) the head's column of the table
+  if constexpr (KIND == SegKind::Typed) {
+    if (st.row < m) bat = seg_types_at(sb, st.row, st.lo, st.hi);
+    seg_table_stage(tab, sb, head, h);
+  }
   f32x4 o[FT];
 #pragma unroll
   for (int ft = 0; ft < FT; ++ft) o[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -241,11 +359,17 @@ __device__ __forceinline__ void segment_fwd_body(float *lds, int m, int h, float
     f32x4 S[NT];
     const float c = im.ainv * q.inv * scale;
     float mx = -INFINITY;
-    [[maybe_unused]] f32x4 B[BIAS ? NT : 1];  // the tile's bias: issued ahead of the products
-    if constexpr (BIAS) {
+    [[maybe_unused]] f32x4 B[KIND == SegKind::Plane ? NT : 1];  // the tile's bias: issued ahead of the products
+    if constexpr (KIND == SegKind::Plane) {
 #pragma unroll
       for (int jt = 0; jt < NT; ++jt)
         B[jt] = st.sees(t + 16 * jt, 16) ? seg_bias_load4(sb.bias, bat, t + 16 * jt + 4 * L.mq, st.lo, st.hi) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    [[maybe_unused]] unsigned ty[KIND == SegKind::Typed ? NT : 1];  // the tile's types, likewise; looked up under the products
+    if constexpr (KIND == SegKind::Typed) {
+#pragma unroll
+      for (int jt = 0; jt < NT; ++jt)
+        ty[jt] = st.sees(t + 16 * jt, 16) ? seg_types_load4(sb.types, bat, t + 16 * jt + 4 * L.mq, st.lo, st.hi) : 0u;
     }
 #pragma unroll
     for (int jt = 0; jt < NT; ++jt) {
@@ -255,7 +379,8 @@ __device__ __forceinline__ void segment_fwd_body(float *lds, int m, int h, float
       for (int r = 0; r < 4; ++r) {
         const int j = t + 16 * jt + 4 * L.mq + r;
         float s;
-        if constexpr (BIAS) s = fmaf(S[jt][r], c, B[jt][r]);
+        if constexpr (KIND == SegKind::Plane) s = fmaf(S[jt][r], c, B[jt][r]);
+        else if constexpr (KIND == SegKind::Typed) s = fmaf(S[jt][r], c, bat == kSegNoBias ? 0.f : seg_table_at(tab, ty[jt], r, sb.T));
         else s = S[jt][r] * c;
         const float x = (seen && j >= st.lo && j < st.hi) ? s : -INFINITY;
         S[jt][r] = x;
@@ -300,17 +425,23 @@ __device__ __forceinline__ void segment_fwd_body(float *lds, int m, int h, float
 }
 
 // P of this strip against the resident K tile, from the rows' saved statistics; masked pairs are 0
-template <class C, int FR, bool BIAS = false>
+template <class C, int FR, SegKind KIND = SegKind::None>
 __device__ __forceinline__ void seg_recompute_p(f32x4 (&S)[C::NT], f32x4 (&dP)[C::NT], const SegImages &im, int t,
                                                 const SegStrip &st, const SegRows<FR> &q, const SegRows<FR> &g, float scale,
                                                 float mx, float il, const LaneIds &L, const float *__restrict__ bias = nullptr,
-                                                long long bat = kSegNoBias) {
+                                                long long bat = kSegNoBias, const SegTypedLane *tl = nullptr,
+                                                unsigned *ty = nullptr) {
   const float c = im.ainv * q.inv * scale, cd = im.binv * g.inv;
-  [[maybe_unused]] f32x4 B[BIAS ? C::NT : 1];  // the tile's bias: issued ahead of the products
-  if constexpr (BIAS) {
+  [[maybe_unused]] f32x4 B[KIND == SegKind::Plane ? C::NT : 1];  // the tile's bias: issued ahead of the products
+  if constexpr (KIND == SegKind::Plane) {
 #pragma unroll
     for (int jt = 0; jt < C::NT; ++jt)
       B[jt] = st.sees(t + 16 * jt, 16) ? seg_bias_load4(bias, bat, t + 16 * jt + 4 * L.mq, st.lo, st.hi) : f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  if constexpr (KIND == SegKind::Typed) {  // ty[NT]: the tile's types, the caller's to keep
+#pragma unroll
+    for (int jt = 0; jt < C::NT; ++jt)
+      ty[jt] = st.sees(t + 16 * jt, 16) ? seg_types_load4(tl->types, tl->at, t + 16 * jt + 4 * L.mq, st.lo, st.hi) : 0u;
   }
 #pragma unroll
   for (int jt = 0; jt < C::NT; ++jt) {
@@ -321,7 +452,9 @@ __device__ __forceinline__ void seg_recompute_p(f32x4 (&S)[C::NT], f32x4 (&dP)[C
     for (int r = 0; r < 4; ++r) {
       const int j = t + 16 * jt + 4 * L.mq + r;
       float e;
-      if constexpr (BIAS) e = fast_exp(fmaf(S[jt][r], c, B[jt][r]) - mx) * il;
+      if constexpr (KIND == SegKind::Plane) e = fast_exp(fmaf(S[jt][r], c, B[jt][r]) - mx) * il;
+      else if constexpr (KIND == SegKind::Typed)
+        e = fast_exp(fmaf(S[jt][r], c, tl->at == kSegNoBias ? 0.f : seg_table_at(tl->tab, ty[jt], r, tl->T)) - mx) * il;
       else e = fast_exp(S[jt][r] * c - mx) * il;
       S[jt][r] = (seen && j >= st.lo && j < st.hi) ? e : 0.f;
       dP[jt][r] *= cd;
@@ -330,13 +463,13 @@ __device__ __forceinline__ void seg_recompute_p(f32x4 (&S)[C::NT], f32x4 (&dP)[C
 }
 
 // ---- dQ (and delta) ---------------------------------------------------------------------------------------------------
-template <int FR, bool BIAS = false>
+template <int FR, SegKind KIND = SegKind::None, class SB = SegBias>
 __device__ __forceinline__ void segment_dq_body(float *lds, int m, int h, float scale, const int *__restrict__ bounds,
                                                 const float *__restrict__ Q, const float *__restrict__ K,
                                                 const float *__restrict__ V, const float *__restrict__ row_max,
                                                 const float *__restrict__ row_sum, const float *__restrict__ dO,
                                                 float *__restrict__ dQ, float *__restrict__ delta,
-                                                const SegBias &sb = SegBias{}) {
+                                                const SB &sb = SB{}) {
   using C = SegDqCfg<FR>;
   constexpr int F = C::F, FT = C::FT, NT = C::NT, TR = C::TR;
   const int head = blockIdx.y, w0 = blockIdx.x * kSegWindow;
@@ -350,15 +483,34 @@ __device__ __forceinline__ void segment_dq_body(float *lds, int m, int h, float 
   const size_t si = (size_t)min(st.row, m - 1) * h + head;
   const float mx = row_max[si], rs = row_sum[si], il = rs > 0.f ? 1.f / rs : 0.f;
   long long bat = kSegNoBias;
-  if constexpr (BIAS)
+  if constexpr (KIND == SegKind::Plane)
     if (st.row < m) bat = seg_bias_at(sb, head, st.row, st.lo, st.hi);
+  // (Typed) behind the tile: the head's column of the table, then one dB table per wave, zeroed by its wave
+  [[maybe_unused]] float *tab = lds + C::kLds / 4, *tabs = tab + kSegMaxTypes;
+  [[maybe_unused]] SegTypedLane tl{};
+  [[maybe_unused]] float *wtab = nullptr;
+  if constexpr (KIND == SegKind::Typed) {
+    if (st.row < m) bat = seg_types_at(sb, st.row, st.lo, st.hi);
+    tl = SegTypedLane{sb.types, tab, sb.T, bat};
+    seg_table_stage(tab, sb, head, h);
+    if (sb.ws) {
+      const int tid = opaque_tid(), per = sb.T << sb.wshift;
+      wtab = tabs + (tid / kWave) * per;
+      for (int k = tid & (kWave - 1); k < per; k += kWave) wtab[k] = 0.f;
+    }
+  }
 
   float tsum = 0.f;  // pass 1: t_i = sum_j P_ij dP_ij
   seg_tile_loop<C>(lds, K + hoff, V + hoff, hf, t0, t1, FR, [](int) {}, [](float *) {}, [&](int t, const SegImages &im) {
     if (!st.sees(t, TR)) return;
     const LaneIds L = lane_ids();
     f32x4 S[NT], dP[NT];
-    seg_recompute_p<C, FR, BIAS>(S, dP, im, t, st, q, g, scale, mx, il, L, sb.bias, bat);
+    if constexpr (KIND == SegKind::Typed) {
+      unsigned ty[NT];
+      seg_recompute_p<C, FR, KIND>(S, dP, im, t, st, q, g, scale, mx, il, L, nullptr, kSegNoBias, &tl, ty);
+    } else {
+      seg_recompute_p<C, FR, KIND>(S, dP, im, t, st, q, g, scale, mx, il, L, sb.bias, bat);
+    }
 #pragma unroll
     for (int jt = 0; jt < NT; ++jt)
 #pragma unroll
@@ -374,7 +526,9 @@ __device__ __forceinline__ void segment_dq_body(float *lds, int m, int h, float 
     if (!st.sees(t, TR)) return;
     const LaneIds L = lane_ids();
     f32x4 S[NT], dP[NT];
-    seg_recompute_p<C, FR, BIAS>(S, dP, im, t, st, q, g, scale, mx, il, L, sb.bias, bat);
+    [[maybe_unused]] unsigned ty[KIND == SegKind::Typed ? NT : 1];
+    if constexpr (KIND == SegKind::Typed) seg_recompute_p<C, FR, KIND>(S, dP, im, t, st, q, g, scale, mx, il, L, nullptr, kSegNoBias, &tl, ty);
+    else seg_recompute_p<C, FR, KIND>(S, dP, im, t, st, q, g, scale, mx, il, L, sb.bias, bat);
     float am = 0.f;
 #pragma unroll
     for (int jt = 0; jt < NT; ++jt)
@@ -383,7 +537,10 @@ __device__ __forceinline__ void segment_dq_body(float *lds, int m, int h, float 
         S[jt][r] *= dP[jt][r] - dl;
         am = fmaxf(am, fabsf(S[jt][r]));
       }
-    if constexpr (BIAS) {  // dbias = dS, one store per valid pair (the mask of the loads)
+    if constexpr (KIND == SegKind::Typed) {  // dB += dS by type, in this wave's table
+      if (sb.ws) seg_dtable_add<NT>(wtab, sb, S, ty, st, t, bat == kSegNoBias, L);
+    }
+    if constexpr (KIND == SegKind::Plane) {  // dbias = dS, one store per valid pair (the mask of the loads)
       if (sb.dbias) {
 #pragma unroll
         for (int jt = 0; jt < NT; ++jt)
@@ -402,17 +559,20 @@ __device__ __forceinline__ void segment_dq_body(float *lds, int m, int h, float 
     for (int ft = 0; ft < FT; ++ft) dq[ft] += tile[ft] * u;
   });
   seg_store<FR, FT>(dq, scale, dQ + hoff, hf, st, m, L);
+  if constexpr (KIND == SegKind::Typed) {
+    if (sb.ws) seg_dtable_fold(tabs, sb, sb.ws + ((size_t)blockIdx.x * sb.T) * h + head, h);
+  }
 }
 
 // ---- dK, dV -----------------------------------------------------------------------------------------------------------
-template <int FR, bool BIAS = false>
+template <int FR, SegKind KIND = SegKind::None, class SB = SegBias>
 __device__ __forceinline__ void segment_dkv_body(float *lds, int m, int h, float scale, const int *__restrict__ bounds,
                                                  const float *__restrict__ Q, const float *__restrict__ K,
                                                  const float *__restrict__ V, const float *__restrict__ row_max,
                                                  const float *__restrict__ row_sum, const float *__restrict__ dO,
                                                  const float *__restrict__ delta, float *__restrict__ dK,
-                                                 float *__restrict__ dV, const SegBias &sb = SegBias{}) {
-  using C = SegDkvCfg<FR, BIAS>;
+                                                 float *__restrict__ dV, const SB &sb = SB{}) {
+  using C = SegDkvCfg<FR, KIND != SegKind::None>;
   constexpr int F = C::F, FT = C::FT, NT = C::NT, TR = C::TR;
   const int head = blockIdx.y, w0 = blockIdx.x * kSegWindow;
   const unsigned hf = (unsigned)h * FR, hoff = (unsigned)head * FR;
@@ -429,7 +589,9 @@ __device__ __forceinline__ void segment_dkv_body(float *lds, int m, int h, float
 
   float xm = 0.f, xs = 0.f, xd = 0.f;  // a tile row's statistics, delta and bounds on their way to LDS (threads < TR)
   int xlo = 0, xhi = 0;
-  [[maybe_unused]] long long xat = kSegNoBias;  // (BIAS) seg_bias_at of the tile row: two more words
+  [[maybe_unused]] long long xat = kSegNoBias;  // (with a bias) seg_bias_at / seg_types_at of the tile row: two more words
+  [[maybe_unused]] float *tab = lds + C::kLds / 4;  // (Typed) the head's column of the table
+  if constexpr (KIND == SegKind::Typed) seg_table_stage(tab, sb, head, h);
   auto xload = [&](int t) {
     const int tid = opaque_tid();
     if (tid < TR) {
@@ -440,7 +602,8 @@ __device__ __forceinline__ void segment_dkv_body(float *lds, int m, int h, float
       xd = delta[si];
       xlo = t + tid < t1 ? bounds[2 * i] : 0;  // a row past the range sees nothing
       xhi = t + tid < t1 ? bounds[2 * i + 1] : 0;
-      if constexpr (BIAS) xat = seg_bias_at(sb, head, i, xlo, xhi);
+      if constexpr (KIND == SegKind::Plane) xat = seg_bias_at(sb, head, i, xlo, xhi);
+      if constexpr (KIND == SegKind::Typed) xat = seg_types_at(sb, i, xlo, xhi);
     }
   };
   auto xstore = [&](float *rows) {
@@ -451,7 +614,7 @@ __device__ __forceinline__ void segment_dkv_body(float *lds, int m, int h, float
       rows[2 * TR + tid] = xd;
       reinterpret_cast<int *>(rows)[3 * TR + tid] = xlo;
       reinterpret_cast<int *>(rows)[4 * TR + tid] = xhi;
-      if constexpr (BIAS) {
+      if constexpr (KIND != SegKind::None) {
         reinterpret_cast<int *>(rows)[5 * TR + tid] = (int)(unsigned)(unsigned long long)xat;
         reinterpret_cast<int *>(rows)[6 * TR + tid] = (int)(xat >> 32);
       }
@@ -469,7 +632,7 @@ __device__ __forceinline__ void segment_dkv_body(float *lds, int m, int h, float
       const bool seen = st.sees(t + 16 * u, 16);
       const int at = 16 * u + 4 * L.mq;
       [[maybe_unused]] f32x4 B = {0.f, 0.f, 0.f, 0.f};  // bias of (query at + r, key j): issued ahead of the products
-      if constexpr (BIAS) {
+      if constexpr (KIND == SegKind::Plane) {
         if (seen) {
           const int4 al = *reinterpret_cast<const int4 *>(im.rows + 5 * TR + at), ah = *reinterpret_cast<const int4 *>(im.rows + 6 * TR + at);
           const int4 lo = *reinterpret_cast<const int4 *>(im.rows + 3 * TR + at), hi = *reinterpret_cast<const int4 *>(im.rows + 4 * TR + at);
@@ -482,8 +645,26 @@ __device__ __forceinline__ void segment_dkv_body(float *lds, int m, int h, float
           }
         }
       }
+      [[maybe_unused]] int tyq[4] = {-1, -1, -1, -1};  // (Typed) type of (query at + r, key j), -1 where there is none
+      if constexpr (KIND == SegKind::Typed) {
+        if (seen) {
+          const int4 al = *reinterpret_cast<const int4 *>(im.rows + 5 * TR + at), ah = *reinterpret_cast<const int4 *>(im.rows + 6 * TR + at);
+          const int4 lo = *reinterpret_cast<const int4 *>(im.rows + 3 * TR + at), hi = *reinterpret_cast<const int4 *>(im.rows + 4 * TR + at);
+          const int alr[4] = {al.x, al.y, al.z, al.w}, ahr[4] = {ah.x, ah.y, ah.z, ah.w};
+          const int lor[4] = {lo.x, lo.y, lo.z, lo.w}, hir[4] = {hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const long long a = (long long)(((unsigned long long)(unsigned)ahr[r] << 32) | (unsigned)alr[r]);
+            if (a != kSegNoBias && j >= lor[r] && j < hir[r]) tyq[r] = sb.types[a + j];
+          }
+        }
+      }
       S[u] = seen ? dense_rows_mma<F>(im.ahi, im.alo, u, k.h, k.l, L) : f32x4{0.f, 0.f, 0.f, 0.f};
       dP[u] = seen ? dense_rows_mma<F>(im.bhi, im.blo, u, v.h, v.l, L) : f32x4{0.f, 0.f, 0.f, 0.f};
+      if constexpr (KIND == SegKind::Typed) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) B[r] = tyq[r] < 0 ? 0.f : tab[min(tyq[r], sb.T - 1)];
+      }
       const float4 mx = *reinterpret_cast<const float4 *>(im.rows + at), il = *reinterpret_cast<const float4 *>(im.rows + TR + at),
                    dl = *reinterpret_cast<const float4 *>(im.rows + 2 * TR + at);
       const int4 lo = *reinterpret_cast<const int4 *>(im.rows + 3 * TR + at), hi = *reinterpret_cast<const int4 *>(im.rows + 4 * TR + at);
@@ -492,7 +673,7 @@ __device__ __forceinline__ void segment_dkv_body(float *lds, int m, int h, float
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float e;
-        if constexpr (BIAS) e = fast_exp(fmaf(S[u][r], c, B[r]) - mxr[r]) * ilr[r];
+        if constexpr (KIND != SegKind::None) e = fast_exp(fmaf(S[u][r], c, B[r]) - mxr[r]) * ilr[r];
         else e = fast_exp(S[u][r] * c - mxr[r]) * ilr[r];
         const float p = (seen && j >= lor[r] && j < hir[r]) ? e : 0.f;
         const float ds = p * (dP[u][r] * cd - dlr[r]);

@@ -1,6 +1,7 @@
 // segment_mha.hip -- multi-head attention of every node over the nodes of its own graph in a batch: the C entries of
-// include/dfgnn_segment.h, and of include/dfgnn_segment_bias.h: the same pair with a per-pair bias added to the logits.  The
-// kernel bodies and the design are in dfgnn_segment.hpp.
+// include/dfgnn_segment.h, of include/dfgnn_segment_bias.h: the same pair with a per-pair bias added to the logits, and of
+// include/dfgnn_segment_tbias.h: that bias looked up in the kernels from a table by the pair's type.  The kernel bodies and
+// the design are in dfgnn_segment.hpp.
 //
 // The whole structure of the problem is seg_ptr [n_seg + 1].  dfgnn_segment_bounds turns it into (lo, hi) per node once
 // per batch; every layer, head and direction reads that.  Grids follow from m alone -- ceil(m / 128) windows x h heads --
@@ -9,6 +10,7 @@
 
 #include "../../include/dfgnn_segment.h"
 #include "../../include/dfgnn_segment_bias.h"
+#include "../../include/dfgnn_segment_tbias.h"
 #include "dfgnn_segment.hpp"
 
 namespace dfgnn {
@@ -121,7 +123,7 @@ __global__ __launch_bounds__(kDenseThreads) void segment_mha_bias_fwd_kernel(int
                                                                              float *__restrict__ out, float *__restrict__ row_max,
                                                                              float *__restrict__ row_sum) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  segment_fwd_body<FR, true>(lds, m, h, scale, bounds, Q, K, V, out, row_max, row_sum, sb);
+  segment_fwd_body<FR, SegKind::Plane>(lds, m, h, scale, bounds, Q, K, V, out, row_max, row_sum, sb);
 }
 
 template <int FR>
@@ -133,7 +135,7 @@ __global__ __launch_bounds__(kDenseThreads) void segment_mha_bias_dq_kernel(int 
                                                                             const float *__restrict__ dO, float *__restrict__ dQ,
                                                                             float *__restrict__ delta) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  segment_dq_body<FR, true>(lds, m, h, scale, bounds, Q, K, V, row_max, row_sum, dO, dQ, delta, sb);
+  segment_dq_body<FR, SegKind::Plane>(lds, m, h, scale, bounds, Q, K, V, row_max, row_sum, dO, dQ, delta, sb);
 }
 
 template <int FR>
@@ -146,8 +148,79 @@ __global__ __launch_bounds__(kDenseThreads) void segment_mha_bias_dkv_kernel(int
                                                                              const float *__restrict__ delta, float *__restrict__ dK,
                                                                              float *__restrict__ dV) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  segment_dkv_body<FR, true>(lds, m, h, scale, bounds, Q, K, V, row_max, row_sum, dO, delta, dK, dV, sb);
+  segment_dkv_body<FR, SegKind::Plane>(lds, m, h, scale, bounds, Q, K, V, row_max, row_sum, dO, delta, dK, dV, sb);
 }
+
+// ---- the typed pair bias (include/dfgnn_segment_tbias.h): the same bodies with SegKind::Typed ----------------------------------
+template <int FR>
+__global__ __launch_bounds__(kDenseThreads) void segment_mha_tbias_fwd_kernel(int m, int h, float scale, const int *__restrict__ bounds,
+                                                                              SegTBias tb, const float *__restrict__ Q,
+                                                                              const float *__restrict__ K, const float *__restrict__ V,
+                                                                              float *__restrict__ out, float *__restrict__ row_max,
+                                                                              float *__restrict__ row_sum) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  segment_fwd_body<FR, SegKind::Typed, SegTBias>(lds, m, h, scale, bounds, Q, K, V, out, row_max, row_sum, tb);
+}
+
+template <int FR>
+__global__ __launch_bounds__(kDenseThreads) void segment_mha_tbias_dq_kernel(int m, int h, float scale, const int *__restrict__ bounds,
+                                                                             SegTBias tb, const float *__restrict__ Q,
+                                                                             const float *__restrict__ K, const float *__restrict__ V,
+                                                                             const float *__restrict__ row_max,
+                                                                             const float *__restrict__ row_sum,
+                                                                             const float *__restrict__ dO, float *__restrict__ dQ,
+                                                                             float *__restrict__ delta) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  segment_dq_body<FR, SegKind::Typed, SegTBias>(lds, m, h, scale, bounds, Q, K, V, row_max, row_sum, dO, dQ, delta, tb);
+}
+
+template <int FR>
+__global__ __launch_bounds__(kDenseThreads) void segment_mha_tbias_dkv_kernel(int m, int h, float scale, const int *__restrict__ bounds,
+                                                                              SegTBias tb, const float *__restrict__ Q,
+                                                                              const float *__restrict__ K, const float *__restrict__ V,
+                                                                              const float *__restrict__ row_max,
+                                                                              const float *__restrict__ row_sum,
+                                                                              const float *__restrict__ dO,
+                                                                              const float *__restrict__ delta, float *__restrict__ dK,
+                                                                              float *__restrict__ dV) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  segment_dkv_body<FR, SegKind::Typed, SegTBias>(lds, m, h, scale, bounds, Q, K, V, row_max, row_sum, dO, delta, dK, dV, tb);
+}
+
+// dB[c] = sum over the work items' partials parts[p, c], c = t h + head: 64 columns per workgroup, wave w adds the partials
+// w, w + 16, .. in that order, the 16 sums are added in wave order.  nparts == 0 writes zeros.
+constexpr int kSegReduceWaves = 16;
+__global__ __launch_bounds__(kSegReduceWaves *kWave) void segment_tbias_reduce_kernel(const float *__restrict__ parts, int nparts,
+                                                                                      int th, float *__restrict__ dB) {
+  __shared__ float red[kSegReduceWaves][kWave];
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const int c = blockIdx.x * kWave + lane;
+  float s = 0.f;
+  if (c < th)
+    for (int p = wave; p < nparts; p += kSegReduceWaves) s += parts[(size_t)p * th + c];
+  red[wave][lane] = s;
+  __syncthreads();
+  if (wave == 0 && c < th) {
+    float t = 0.f;
+#pragma unroll
+    for (int w = 0; w < kSegReduceWaves; ++w) t += red[w][lane];
+    dB[c] = t;
+  }
+}
+
+// the typed kernels' LDS: the tile, the staged column of the table and, in a dQ kernel that sums dB, 8 wave tables
+template <int FR>
+constexpr int seg_tbias_dq_lds(int T, bool want_db) {
+  return SegDqCfg<FR>::kLds + kSegTabBytes + (want_db ? kDenseWaves * T * seg_tbias_slots(T) * 4 : 0);
+}
+template <int FR>
+constexpr bool seg_tbias_lds_ok() {
+  return SegFwdCfg<FR>::kLds % 16 == 0 && SegDqCfg<FR>::kLds % 16 == 0 && SegDkvCfg<FR, true>::kLds % 16 == 0 &&
+         SegFwdCfg<FR>::kLds + kSegTabBytes <= kBlockLdsBudget && SegDkvCfg<FR, true>::kLds + kSegTabBytes <= kBlockLdsBudget &&
+         SegDqCfg<FR>::kLds + kSegTabBytes + kDenseWaves * kSegWaveTabFloats * 4 <= kBlockLdsBudget;
+}
+static_assert(seg_tbias_lds_ok<16>() && seg_tbias_lds_ok<32>() && seg_tbias_lds_ok<64>() && seg_tbias_lds_ok<128>(),
+              "tile + staged table + 8 wave tables stay inside the LDS budget");
 
 static bool segment_width_ok(int f) { return f == 16 || f == 32 || f == 64 || f == 128; }
 
@@ -276,6 +349,70 @@ int dfgnn_segment_mha_bias_bwd(int m, int h, int f, float scale, const int *boun
                                                                                    row_sum, dO, dQ, delta);
     segment_mha_bias_dkv_kernel<FR><<<grid, kDenseThreads, SegDkvCfg<FR, true>::kLds, s>>>(m, h, scale, bounds, sb, Q, K, V, row_max,
                                                                                            row_sum, dO, delta, dK, dV);
+    return launch_status();
+  });
+}
+
+// ---- include/dfgnn_segment_tbias.h -----------------------------------------------------------------------------------------
+int dfgnn_segment_tbias_abi_version(void) { return DFGNN_SEGMENT_TBIAS_ABI_VERSION; }
+
+static int segment_tbias_check(int m, int h, int f, long long n_pairs, int T) {
+  if (n_pairs < 0 || m < 0 || h < 1 || f < 1 || T < 1) return kErrBadArg;
+  if (T > kSegMaxTypes) return kErrUnsupported;
+  return segment_check(m, h, f);
+}
+
+long long dfgnn_segment_mha_tbias_ws_floats(int m, int h, int T) {
+  if (m < 0 || h < 1 || T < 1) return kErrBadArg;
+  if (T > kSegMaxTypes || h > 65535 || m >= (1 << 30)) return kErrUnsupported;
+  return (long long)((m + kSegWindow - 1) / kSegWindow) * h * T;
+}
+
+int dfgnn_segment_mha_tbias_fwd(int m, int h, int f, float scale, const int *bounds, const long long *row_off, long long n_pairs,
+                                const unsigned char *types, int T, const float *B, const float *Q, const float *K, const float *V,
+                                float *out, float *row_max, float *row_sum, dfgnn_stream_t stream) {
+  if (int rc = segment_tbias_check(m, h, f, n_pairs, T)) return rc;
+  if ((row_max == nullptr) != (row_sum == nullptr)) return kErrBadArg;
+  if (m == 0) return 0;
+  if (!bounds || !row_off || !types || !B || !Q || !K || !V || !out) return kErrBadArg;
+  const dim3 grid((m + kSegWindow - 1) / kSegWindow, h);
+  const SegTBias tb{row_off, n_pairs, types, B, T, nullptr, 0, 0};
+  return dispatch_segment(f, [&](auto fc) {
+    constexpr int FR = decltype(fc)::value;
+    if (int rc = set_max_lds_cached(segment_mha_tbias_fwd_kernel<FR>)) return rc;
+    segment_mha_tbias_fwd_kernel<FR><<<grid, kDenseThreads, SegFwdCfg<FR>::kLds + kSegTabBytes, reinterpret_cast<hipStream_t>(stream)>>>(
+        m, h, scale, bounds, tb, Q, K, V, out, row_max, row_sum);
+    return launch_status();
+  });
+}
+
+int dfgnn_segment_mha_tbias_bwd(int m, int h, int f, float scale, const int *bounds, const long long *row_off, long long n_pairs,
+                                const unsigned char *types, int T, const float *B, const float *Q, const float *K, const float *V,
+                                const float *row_max, const float *row_sum, const float *dO, float *dQ, float *dK, float *dV,
+                                float *dB, float *ws, float *delta, dfgnn_stream_t stream) {
+  if (int rc = segment_tbias_check(m, h, f, n_pairs, T)) return rc;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int th = T * h, nparts = (m + kSegWindow - 1) / kSegWindow;
+  if (m == 0) {  // nothing to differentiate, but a wanted dB is zeros
+    if (dB) segment_tbias_reduce_kernel<<<(th + kWave - 1) / kWave, kSegReduceWaves * kWave, 0, s>>>(nullptr, 0, th, dB);
+    return dB ? launch_status() : 0;
+  }
+  if (!bounds || !row_off || !types || !B || !Q || !K || !V || !row_max || !row_sum || !dO || !dQ || !dK || !dV || !delta ||
+      (dB && !ws))
+    return kErrBadArg;
+  const dim3 grid(nparts, h);
+  int W = seg_tbias_slots(T), wshift = 0;
+  while ((1 << wshift) < W) ++wshift;
+  const SegTBias tb{row_off, n_pairs, types, B, T, dB ? ws : nullptr, W, wshift};
+  return dispatch_segment(f, [&](auto fc) {
+    constexpr int FR = decltype(fc)::value;
+    if (int rc = set_max_lds_cached(segment_mha_tbias_dq_kernel<FR>)) return rc;
+    if (int rc = set_max_lds_cached(segment_mha_tbias_dkv_kernel<FR>)) return rc;
+    segment_mha_tbias_dq_kernel<FR><<<grid, kDenseThreads, seg_tbias_dq_lds<FR>(T, dB != nullptr), s>>>(m, h, scale, bounds, tb, Q, K, V,
+                                                                                                      row_max, row_sum, dO, dQ, delta);
+    segment_mha_tbias_dkv_kernel<FR><<<grid, kDenseThreads, SegDkvCfg<FR, true>::kLds + kSegTabBytes, s>>>(
+        m, h, scale, bounds, tb, Q, K, V, row_max, row_sum, dO, delta, dK, dV);
+    if (dB) segment_tbias_reduce_kernel<<<(th + kWave - 1) / kWave, kSegReduceWaves * kWave, 0, s>>>(ws, nparts, th, dB);
     return launch_status();
   });
 }

@@ -122,6 +122,15 @@ SEGMENT_BIAS_SIGNATURES = {
     "dfgnn_segment_mha_bias_bwd": [_i, _i, _i, _f, _vp, _vp, ctypes.c_longlong] + [_vp] * 13,
 }
 
+# the same pair with a typed pair bias: include/dfgnn_segment_tbias.h one to one (checked by tests/test_segment_tbias_host.py);
+# dfgnn_segment_mha_tbias_ws_floats answers a long long, the rest an int
+SEGMENT_TBIAS_SIGNATURES = {
+    "dfgnn_segment_tbias_abi_version": [],
+    "dfgnn_segment_mha_tbias_ws_floats": [_i, _i, _i],
+    "dfgnn_segment_mha_tbias_fwd": [_i, _i, _i, _f, _vp, _vp, ctypes.c_longlong, _vp, _i] + [_vp] * 8,
+    "dfgnn_segment_mha_tbias_bwd": [_i, _i, _i, _f, _vp, _vp, ctypes.c_longlong, _vp, _i] + [_vp] * 14,
+}
+
 EXT_PATH = os.path.join(_HERE, "_dfgnn_ext.so")   # torch C++ extension over the same C ABI (csrc/torch_ext.cpp)
 
 _lib = None
@@ -175,10 +184,11 @@ def lib():
         # call that needs the kernels -- csrc/gen_shim.py)
         L = ctypes.CDLL(LIB_PATH)
         for name, argtypes in (list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(SEGMENT_SIGNATURES.items()) +
-                               list(SEGMENT_BIAS_SIGNATURES.items())):
+                               list(SEGMENT_BIAS_SIGNATURES.items()) + list(SEGMENT_TBIAS_SIGNATURES.items())):
             fn = getattr(L, name)  # AttributeError if the library is stale
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int
+        L.dfgnn_segment_mha_tbias_ws_floats.restype = ctypes.c_longlong
         L.dfgnn_error_string.argtypes = [ctypes.c_int]
         L.dfgnn_error_string.restype = ctypes.c_char_p
         L.dfgnn_abi_version.restype = ctypes.c_int

@@ -894,6 +894,58 @@ def segment_mha_bias_backward(bounds, row_off, bias, Q, K, V, row_max, row_sum, 
     return [dQ, dK, dV, dbias]
 
 
+# ---- the same pair with a TYPED pair bias (include/dfgnn_segment_tbias.h): the bias looked up in the kernels ----------------
+# types uint8[n_pairs] in the layout of one bias plane, shared by all heads; table fp32[T, h], T <= 256.
+SEGMENT_TBIAS_MAX_TYPES = 256
+
+
+def _segment_tbias_checks(bounds, row_off, types, table, Q, K, V, **like_Q):
+    m, h, f = _segment_checks(bounds, Q, K, V, **like_Q)
+    _family(Q, torch.int64, (m,), {"row_off": row_off})
+    _family(Q, torch.uint8, None, {"types": types})
+    _family(Q, torch.float32, None, {"table": table})
+    if types.dim() != 1:
+        raise RuntimeError(f"types must have shape (n_pairs,): one plane for all heads, got {tuple(types.shape)}")
+    if table.dim() != 2 or table.size(1) != h or not 1 <= table.size(0) <= SEGMENT_TBIAS_MAX_TYPES:
+        raise RuntimeError(f"table must have shape (T, {h}) with 1 <= T <= {SEGMENT_TBIAS_MAX_TYPES}, got {tuple(table.shape)}")
+    return m, h, f, types.numel(), table.size(0)
+
+
+def segment_mha_tbias_inference(bounds, row_off, types, table, Q, K, V, scale=1.0):
+    """-> out [m, h, f]; no statistics are written."""
+    m, h, f, n_pairs, T = _segment_tbias_checks(bounds, row_off, types, table, Q, K, V)
+    out = torch.empty_like(Q)
+    call("dfgnn_segment_mha_tbias_fwd", "segment_mha_tbias_inference", Q.device, m, h, f, float(scale), bounds, row_off, n_pairs,
+         types, T, table, Q, K, V, out, None, None)
+    return out
+
+
+def segment_mha_tbias_forward(bounds, row_off, types, table, Q, K, V, scale=1.0):
+    """-> [out, row_max[m, h], row_sum[m, h]]: the training forward (statistics of the biased logits)."""
+    m, h, f, n_pairs, T = _segment_tbias_checks(bounds, row_off, types, table, Q, K, V)
+    out, row_max, row_sum = torch.empty_like(Q), _empty(Q, m, h), _empty(Q, m, h)
+    call("dfgnn_segment_mha_tbias_fwd", "segment_mha_tbias_forward", Q.device, m, h, f, float(scale), bounds, row_off, n_pairs,
+         types, T, table, Q, K, V, out, row_max, row_sum)
+    return [out, row_max, row_sum]
+
+
+def segment_mha_tbias_backward(bounds, row_off, types, table, Q, K, V, row_max, row_sum, grad, scale=1.0, need_dtable=True):
+    """-> [dQ, dK, dV, dtable]; dtable [T, h] summed in the kernels without atomics, or None without need_dtable (a frozen
+    table: no table work at all)."""
+    m, h, f, n_pairs, T = _segment_tbias_checks(bounds, row_off, types, table, Q, K, V, grad=grad)
+    check_2d(Q, m, h, row_max=row_max, row_sum=row_sum)
+    delta = _empty(Q, m, h)
+    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
+    dtable = ws = None
+    if need_dtable:
+        n_ws = _n.lib().dfgnn_segment_mha_tbias_ws_floats(m, h, T)
+        _n.check(min(n_ws, 0), "segment_mha_tbias_backward")
+        dtable, ws = torch.empty_like(table), _empty(Q, n_ws)
+    call("dfgnn_segment_mha_tbias_bwd", "segment_mha_tbias_backward", Q.device, m, h, f, float(scale), bounds, row_off, n_pairs,
+         types, T, table, Q, K, V, row_max, row_sum, grad, dQ, dK, dV, dtable, ws, delta)
+    return [dQ, dK, dV, dtable]
+
+
 # ---- the CSR-taking inference variants ----------------------------------------------------------------------------------
 _VARIANTS =("gt_tiling", "gt_csr", "gt_csr_gm", "gt_softmax", "gt_softmax_gm")   # by `which` of torch_ext.cpp: gt_variant_fwd
 

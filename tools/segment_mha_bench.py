@@ -13,7 +13,15 @@ gradient, against
   sdpa   the same padded SDPA with the bias as a float attn_mask [B, h, n_max, n_max] (-inf on the padding keys), its
          gradient included
   plain  the unbiased pair on the same Q, K, V: the difference is the price of the bias
-usage: python3 tools/segment_mha_bench.py [--shapes 4x32,8x16,1x128] [--steps 30] [--bias]   (DESIGN.md 3.3k, 3.3l hold the tables)"""
+--tbias: the pair with a typed pair bias (SegmentMHATBiasFuse, include/dfgnn_segment_tbias.h), T = --types, one training step
+with the table's gradient:
+  typed         SegmentMHATBiasFuse(seg_ptr, Q, K, V, types uint8, table)
+  materialised  what a user ran before it: bias = table.t()[:, types int64], SegmentMHABiasFuse, autograd's index backward --
+                all of it inside the timed region
+  plain         the unbiased pair
+and the peak of torch's allocator over one step of typed and of materialised, above what is allocated before the step.
+usage: python3 tools/segment_mha_bench.py [--shapes 4x32,8x16,1x128] [--steps 30] [--bias | --tbias [--types 20]]
+(DESIGN.md 3.3k, 3.3l, 3.3m hold the tables)"""
 import argparse
 import json
 import os
@@ -26,7 +34,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from torch.nn import functional as F  # noqa: E402
 
-from DFGNN.operators.fused_gtconv import GTConvFuse_rowstats, SegmentMHABiasFuse, SegmentMHAFuse  # noqa: E402
+from DFGNN.operators.fused_gtconv import GTConvFuse_rowstats, SegmentMHABiasFuse, SegmentMHAFuse, SegmentMHATBiasFuse  # noqa: E402
 
 DEV = "cuda:0"
 BATCHES = {"zinc": (1024, 9, 37), "pattern": (256, 44, 188), "peptides": (128, 60, 240), "long": (16, 1000, 2000)}
@@ -55,6 +63,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--csr-max-edges", type=int, default=40_000_000)
     ap.add_argument("--bias", action="store_true", help="time the biased pair against SDPA with a float mask and the unbiased pair")
+    ap.add_argument("--tbias", action="store_true", help="time the typed pair against the materialised bias and the unbiased pair")
+    ap.add_argument("--types", type=int, default=20, help="--tbias: rows of the table")
     ap.add_argument("--bias-max-pairs", type=int, default=40_000_000, help="skip batches whose padded mask would be larger")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "segment_mha_bench.jsonl"))
     args = ap.parse_args()
@@ -63,7 +73,7 @@ def main():
         sizes = np.random.default_rng(7).integers(a, b + 1, size=count)
         for shape in args.shapes.split(","):
             h, f = (int(x) for x in shape.split("x"))
-            if args.bias and len(sizes) * int(sizes.max()) ** 2 > args.bias_max_pairs:
+            if (args.bias or args.tbias) and len(sizes) * int(sizes.max()) ** 2 > args.bias_max_pairs:
                 continue
             line = bench(args, name, sizes, h, f)
             print(json.dumps(line), flush=True)
@@ -97,15 +107,24 @@ def bench(args, name, sizes, h, f):
         forms = {"new": (lambda q, k, v, b: SegmentMHABiasFuse(seg_ptr, q, k, v, b, scale), (Q0, K0, V0, bias0), dO),
                  "sdpa": (lambda q, k, v, b: F.scaled_dot_product_attention(q, k, v, attn_mask=b, scale=scale), (Qp, Kp, Vp, mask0), dOp),
                  "plain": (lambda q, k, v: SegmentMHAFuse(seg_ptr, q, k, v, scale), (Q0, K0, V0), dO)}
+    elif args.tbias:
+        types = torch.randint(0, args.types, (pairs,), generator=gen)
+        t8, t64, table0 = types.to(torch.uint8).to(DEV), types.to(DEV), torch.randn(args.types, h, generator=gen).to(DEV)
+        forms = {"typed": (lambda q, k, v, tb: SegmentMHATBiasFuse(seg_ptr, q, k, v, t8, tb, scale), (Q0, K0, V0, table0), dO),
+                 "materialised": (lambda q, k, v, tb: SegmentMHABiasFuse(seg_ptr, q, k, v, tb.t()[:, t64], scale), (Q0, K0, V0, table0), dO),
+                 "plain": (lambda q, k, v: SegmentMHAFuse(seg_ptr, q, k, v, scale), (Q0, K0, V0), dO)}
     elif pairs <= args.csr_max_edges:
         csr = complete_csr(sizes)
         forms["csr"] = (lambda q, k, v: GTConvFuse_rowstats(*csr, q * scale, k, v), (Q0, K0, V0), dO)
     times = {k: [] for k in forms}
-    last = {}
+    last, peak = {}, {}
     for it in range(args.warmup + args.steps):
         for key, (fn, inputs, grad) in forms.items():           # alternating: all forms see the same machine state
             leaves = [x.detach().requires_grad_(True) for x in inputs]
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            if args.tbias and it == args.warmup - 1:
+                torch.cuda.reset_peak_memory_stats()
+                before = torch.cuda.memory_allocated()
             a.record()
             out = fn(*leaves)
             grads = torch.autograd.grad(out, leaves, grad)
@@ -113,8 +132,18 @@ def bench(args, name, sizes, h, f):
             torch.cuda.synchronize()
             if it >= args.warmup:
                 times[key].append(a.elapsed_time(b) * 1e3)
+            if args.tbias and it == args.warmup - 1:
+                peak[key] = torch.cuda.max_memory_allocated() - before
             last[key] = [out.detach()] + list(grads)
     unpad = lambda x: x.transpose(1, 2)[seg, pos]  # noqa: E731
+    if args.tbias:
+        line = {"tool": "segment_mha_bench_tbias", "batch": name, "graphs": B, "m": m, "pairs": pairs, "h": h, "f": f, "T": args.types,
+                "steps": args.steps}
+        for key in forms:
+            line[key + "_us"], line[key + "_us_min"] = round(float(np.median(times[key])), 1), round(float(np.min(times[key])), 1)
+            line[key + "_peak_mib"] = round(peak[key] / 2 ** 20, 1)
+        line["max_diff"] = max(float((x - y).abs().max()) for x, y in zip(last["typed"], last["materialised"]))
+        return line
     line = {"tool": "segment_mha_bench" + ("_bias" if args.bias else ""), "batch": name, "graphs": B, "m": m, "n_max": nmax, "pairs": pairs, "h": h, "f": f,
             "steps": args.steps}
     for key in forms:
