@@ -5,7 +5,7 @@ import torch
 import torch.nn as nn
 
 import fused_gtconv as fused_gt
-from DFGNN.operators.fused_gtconv import SegmentMHABiasFuse, SegmentMHAFuse, SegmentMHATBiasFuse
+from DFGNN.operators.fused_gtconv import SegmentCrossMHAFuse, SegmentMHABiasFuse, SegmentMHAFuse, SegmentMHATBiasFuse
 
 
 def segment_offsets(segments, device):
@@ -91,3 +91,66 @@ class PairBias(nn.Module):
 
     def forward(self, pair_types):
         return self.table.t()[:, pair_types]
+
+
+class CrossMHA(nn.Module):
+    """out = W_o concat_heads(softmax_graph(scale Q K^T) V) with the queries from one node array and the keys / values from
+    another, both ordered by graph: the rows hq of graph g attend to the rows hk of graph g (DFGNN/operators/fused_gtconv.py:
+    SegmentCrossMHAFuse, csrc/segment_cross.hip).  A query of a graph without keys gets W_o's bias."""
+
+    def __init__(self, q_size, kv_size, out_size, num_heads):
+        super().__init__()
+        self.num_heads = num_heads
+        self.head_dim = out_size // num_heads
+        self.scaling = self.head_dim ** -0.5
+        self.q_proj = nn.Linear(q_size, out_size)
+        self.k_proj = nn.Linear(kv_size, out_size)
+        self.v_proj = nn.Linear(kv_size, out_size)
+        self.out_proj = nn.Linear(out_size, out_size)
+
+    def forward(self, hq, hk, seg_q, seg_k, fuse=True):
+        """hq [N_q, q_size], hk [N_k, kv_size]; seg_q, seg_k: int32 offsets on the device or the graphs' sizes (as
+        GlobalMHA's seg_ptr), of the same number of graphs.  fuse=False, CPU tensors or a head shape the fused pair does not
+        serve: plain torch, graph by graph."""
+        seg_q, seg_k = segment_offsets(seg_q, hq.device), segment_offsets(seg_k, hk.device)
+        q = self.q_proj(hq).reshape(len(hq), self.num_heads, self.head_dim)
+        k = self.k_proj(hk).reshape(len(hk), self.num_heads, self.head_dim)
+        v = self.v_proj(hk).reshape(len(hk), self.num_heads, self.head_dim)
+        return self.out_proj(self.attend(seg_q, seg_k, q, k, v, fuse).reshape(len(hq), -1))
+
+    def attend(self, seg_q, seg_k, q, k, v, fuse=True):
+        if fuse and q.is_cuda and fused_gt.segment_mha_applies(self.num_heads, self.head_dim):
+            return SegmentCrossMHAFuse(seg_q, seg_k, q.contiguous(), k.contiguous(), v.contiguous(), self.scaling)
+        outs = []
+        eq, ek = seg_q.tolist(), seg_k.tolist()
+        for a, b, lo, hi in zip(eq[:-1], eq[1:], ek[:-1], ek[1:]):
+            if hi == lo:
+                outs.append(torch.zeros_like(q[a:b]))
+                continue
+            s = torch.einsum("ihf,jhf->hij", q[a:b], k[lo:hi]) * self.scaling
+            outs.append(torch.einsum("hij,jhf->ihf", torch.softmax(s, dim=-1), v[lo:hi]))
+        return torch.cat(outs) if outs else torch.empty_like(q)
+
+
+class AttentionReadout(nn.Module):
+    """Graph embedding by attention (Set Transformer's PMA, Graph Multiset pooling): num_seeds learnable queries per graph
+    attend to that graph's nodes -> [B, num_seeds * out_size]; a graph without nodes gives zeros.  The queries of all graphs
+    are the seed matrix repeated, seg_ptr_q = num_seeds * arange(B + 1) built on the device without a host read."""
+
+    def __init__(self, in_size, out_size, num_heads, num_seeds=1):
+        super().__init__()
+        self.num_seeds = num_seeds
+        self.seeds = nn.Parameter(torch.empty(num_seeds, out_size))
+        nn.init.xavier_uniform_(self.seeds)
+        self.mha = CrossMHA(out_size, in_size, out_size, num_heads)
+
+    def forward(self, h, seg_ptr, fuse=True):
+        m = self.mha
+        seg_k = segment_offsets(seg_ptr, h.device)
+        B = seg_k.numel() - 1
+        seg_q = torch.arange(B + 1, dtype=torch.int32, device=h.device) * self.num_seeds
+        q = m.q_proj(self.seeds).reshape(self.num_seeds, m.num_heads, m.head_dim).repeat(B, 1, 1)
+        k, v = (p(h).reshape(len(h), m.num_heads, m.head_dim) for p in (m.k_proj, m.v_proj))
+        out = m.attend(seg_q, seg_k, q, k, v, fuse).reshape(B * self.num_seeds, -1)
+        has_nodes = (seg_k[1:] > seg_k[:-1]).repeat_interleave(self.num_seeds).unsqueeze(1)
+        return (m.out_proj(out) * has_nodes).reshape(B, -1)

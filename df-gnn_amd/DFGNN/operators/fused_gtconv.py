@@ -130,6 +130,36 @@ def SegmentMHAFuse(seg_ptr, Q, K, V, scale=1.0):
     return FusedSegmentMHAFunction.apply(bounds, Q, K, V, scale)
 
 
+class FusedSegmentCrossMHAFunction(torch.autograd.Function):
+    """FusedSegmentMHAFunction with the queries and the keys / values in two node arrays
+    (include/dfgnn_segment_cross.h).  Saved: Q, K, V and the row statistics [m_q, h]."""
+
+    @staticmethod
+    def forward(ctx, qbounds, kbounds, Q, K, V, scale, form):
+        out, row_max, row_sum = fused_gt.segment_mha_cross_forward(qbounds, Q, K, V, scale, form)
+        ctx.save_for_backward(qbounds, kbounds, Q, K, V, row_max, row_sum)
+        ctx.scale, ctx.form = scale, form
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        qbounds, kbounds, Q, K, V, row_max, row_sum = ctx.saved_tensors
+        dQ, dK, dV = fused_gt.segment_mha_cross_backward(qbounds, kbounds, Q, K, V, row_max, row_sum, grad_out.contiguous(),
+                                                         ctx.scale, ctx.form)
+        return None, None, dQ, dK, dV, None, None
+
+
+def SegmentCrossMHAFuse(seg_ptr_q, seg_ptr_k, Q, K, V, scale=1.0, form=0):
+    """Differentiable cross attention over batched graphs: Q fp32 [m_q, h, f] and K, V fp32 [m_k, h, f], both ordered by
+    graph, seg_ptr_q / seg_ptr_k int32[n_seg + 1] their offsets; the queries of graph g attend to the keys of graph g
+    -> out [m_q, h, f] (zeros for a graph without keys).  form: fused_gtconv.SEGMENT_CROSS_AUTO / _WIDE / _SPLIT.  Without a
+    gradient to compute, the inference forward (no statistics)."""
+    qbounds, kbounds = fused_gt.segment_cross_bounds(seg_ptr_q, seg_ptr_k, Q.size(0), K.size(0))
+    if not (torch.is_grad_enabled() and (Q.requires_grad or K.requires_grad or V.requires_grad)):
+        return fused_gt.segment_mha_cross_inference(qbounds, Q, K, V, scale, form)
+    return FusedSegmentCrossMHAFunction.apply(qbounds, kbounds, Q, K, V, scale, form)
+
+
 class FusedSegmentMHABiasFunction(torch.autograd.Function):
     """FusedSegmentMHAFunction with a pair bias added to the logits (include/dfgnn_segment_bias.h).  Saved between forward and
     backward: Q, K, V, bias and the row statistics.  dbias [h, n_pairs] is computed only when the bias requires a gradient;

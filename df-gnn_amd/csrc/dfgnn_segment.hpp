@@ -13,6 +13,9 @@
 //   forward    queries      Q               K, V        S^T = K Q^T             O^T  += V^T P^T
 //   dQ         queries      Q, dO           K, V        S^T, dP^T = V dO^T      dQ^T += K^T dS^T   (after a pass for t, below)
 //   dK / dV    keys         K, V            Q, dO       S = Q K^T, dP = dO V^T  dV^T += dO^T P,  dK^T += Q^T dS
+// The strip side and the tile side need not be one node array: a body takes the strip side's extent and bounds, and walks
+// whatever range of the other side those bounds name (the forward and dQ: m_q and the key range of each query; dK / dV: m_k
+// and the query range of each key, plus the queries' own bounds for the mask).  segment_cross.hip runs them that way.
 // The dK / dV kernel is the forward turned round: with the KEYS on the register side the accumulators of S and dP are
 // already the B operands of dO^T P and Q^T dS, so P and dS never leave the registers (no LDS tile, no third barrier) and
 // every key row is summed by one wave in a fixed order: no atomics.  It takes the row statistics, delta and the bounds
@@ -565,9 +568,11 @@ __device__ __forceinline__ void segment_dq_body(float *lds, int m, int h, float 
 }
 
 // ---- dK, dV -----------------------------------------------------------------------------------------------------------
+// m, bounds: the strip side (the keys and, per key, the query rows that see it); tbounds: the tile side (per query row its
+// key range, the mask).  One node array has one bounds array for both; the cross pair (segment_cross.hip) has two.
 template <int FR, SegKind KIND = SegKind::None, class SB = SegBias>
 __device__ __forceinline__ void segment_dkv_body(float *lds, int m, int h, float scale, const int *__restrict__ bounds,
-                                                 const float *__restrict__ Q, const float *__restrict__ K,
+                                                 const int *__restrict__ tbounds, const float *__restrict__ Q, const float *__restrict__ K,
                                                  const float *__restrict__ V, const float *__restrict__ row_max,
                                                  const float *__restrict__ row_sum, const float *__restrict__ dO,
                                                  const float *__restrict__ delta, float *__restrict__ dK,
@@ -600,8 +605,8 @@ __device__ __forceinline__ void segment_dkv_body(float *lds, int m, int h, float
       xm = row_max[si];
       xs = row_sum[si];
       xd = delta[si];
-      xlo = t + tid < t1 ? bounds[2 * i] : 0;  // a row past the range sees nothing
-      xhi = t + tid < t1 ? bounds[2 * i + 1] : 0;
+      xlo = t + tid < t1 ? tbounds[2 * i] : 0;  // a row past the range sees nothing
+      xhi = t + tid < t1 ? tbounds[2 * i + 1] : 0;
       if constexpr (KIND == SegKind::Plane) xat = seg_bias_at(sb, head, i, xlo, xhi);
       if constexpr (KIND == SegKind::Typed) xat = seg_types_at(sb, i, xlo, xhi);
     }

@@ -61,7 +61,7 @@ __global__ __launch_bounds__(kDenseThreads) void segment_mha_dkv_kernel(int m, i
                                                                         const float *__restrict__ delta, float *__restrict__ dK,
                                                                         float *__restrict__ dV) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  segment_dkv_body<FR>(lds, m, h, scale, bounds, Q, K, V, row_max, row_sum, dO, delta, dK, dV);
+  segment_dkv_body<FR>(lds, m, h, scale, bounds, bounds, Q, K, V, row_max, row_sum, dO, delta, dK, dV);
 }
 
 // ---- the pair bias (include/dfgnn_segment_bias.h): the same bodies with BIAS, and the offsets they read ----------------------
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(kDenseThreads) void segment_mha_bias_dkv_kernel(int
                                                                              const float *__restrict__ delta, float *__restrict__ dK,
                                                                              float *__restrict__ dV) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  segment_dkv_body<FR, SegKind::Plane>(lds, m, h, scale, bounds, Q, K, V, row_max, row_sum, dO, delta, dK, dV, sb);
+  segment_dkv_body<FR, SegKind::Plane>(lds, m, h, scale, bounds, bounds, Q, K, V, row_max, row_sum, dO, delta, dK, dV, sb);
 }
 
 // ---- the typed pair bias (include/dfgnn_segment_tbias.h): the same bodies with SegKind::Typed ----------------------------------
@@ -184,7 +184,7 @@ __global__ __launch_bounds__(kDenseThreads) void segment_mha_tbias_dkv_kernel(in
                                                                               const float *__restrict__ delta, float *__restrict__ dK,
                                                                               float *__restrict__ dV) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  segment_dkv_body<FR, SegKind::Typed, SegTBias>(lds, m, h, scale, bounds, Q, K, V, row_max, row_sum, dO, delta, dK, dV, tb);
+  segment_dkv_body<FR, SegKind::Typed, SegTBias>(lds, m, h, scale, bounds, bounds, Q, K, V, row_max, row_sum, dO, delta, dK, dV, tb);
 }
 
 // dB[c] = sum over the work items' partials parts[p, c], c = t h + head: 64 columns per workgroup, wave w adds the partials

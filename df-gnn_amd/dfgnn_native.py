@@ -131,6 +131,15 @@ SEGMENT_TBIAS_SIGNATURES = {
     "dfgnn_segment_mha_tbias_bwd": [_i, _i, _i, _f, _vp, _vp, ctypes.c_longlong, _vp, _i] + [_vp] * 14,
 }
 
+# the cross pair, queries and keys of two node arrays: include/dfgnn_segment_cross.h one to one (checked by
+# tests/test_segment_cross_host.py); all answer an int
+SEGMENT_CROSS_SIGNATURES = {
+    "dfgnn_segment_cross_abi_version": [],
+    "dfgnn_segment_cross_bounds": [_i, _i, _i] + [_vp] * 5,
+    "dfgnn_segment_mha_cross_fwd": [_i, _i, _i, _i, _f, _i] + [_vp] * 8,
+    "dfgnn_segment_mha_cross_bwd": [_i, _i, _i, _i, _f, _i] + [_vp] * 13,
+}
+
 EXT_PATH = os.path.join(_HERE, "_dfgnn_ext.so")   # torch C++ extension over the same C ABI (csrc/torch_ext.cpp)
 
 _lib = None
@@ -184,7 +193,8 @@ def lib():
         # call that needs the kernels -- csrc/gen_shim.py)
         L = ctypes.CDLL(LIB_PATH)
         for name, argtypes in (list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(SEGMENT_SIGNATURES.items()) +
-                               list(SEGMENT_BIAS_SIGNATURES.items()) + list(SEGMENT_TBIAS_SIGNATURES.items())):
+                               list(SEGMENT_BIAS_SIGNATURES.items()) + list(SEGMENT_TBIAS_SIGNATURES.items()) +
+                               list(SEGMENT_CROSS_SIGNATURES.items())):
             fn = getattr(L, name)  # AttributeError if the library is stale
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int

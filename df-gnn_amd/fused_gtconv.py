@@ -833,6 +833,69 @@ def segment_mha_backward(bounds, Q, K, V, out, row_max, row_sum, grad, scale=1.0
     return [dQ, dK, dV]
 
 
+# ---- cross attention: queries and keys of two node arrays (include/dfgnn_segment_cross.h, csrc/segment_cross.hip) ----------
+# Segment g of the queries (seg_ptr_q over m_q rows) attends to segment g of the keys (seg_ptr_k over m_k rows).  form: 0 the
+# library's choice, 1 the wide kernels (128-row query windows), 2 the split kernels (16-row query strips, the waves share the
+# keys): SEGMENT_CROSS_AUTO / _WIDE / _SPLIT.
+SEGMENT_CROSS_AUTO, SEGMENT_CROSS_WIDE, SEGMENT_CROSS_SPLIT = 0, 1, 2
+_cross_bounds_cache = _KeyedCache()
+
+
+def segment_cross_bounds(seg_ptr_q, seg_ptr_k, m_q, m_k):
+    """-> (qbounds int32[2 m_q]: the key range of every query, kbounds int32[2 m_k]: the query range of every key), built
+    once per pair of seg_ptr tensors and cached."""
+    check_family(seg_ptr_q, torch.int32, seg_ptr_q=seg_ptr_q, seg_ptr_k=seg_ptr_k)
+    if seg_ptr_q.dim() != 1 or seg_ptr_q.numel() < 1 or seg_ptr_k.shape != seg_ptr_q.shape:
+        raise RuntimeError(f"seg_ptr_q and seg_ptr_k must both have shape (n_seg + 1,), got {tuple(seg_ptr_q.shape)} and "
+                           f"{tuple(seg_ptr_k.shape)}")
+    key = _KeyedCache.key_of(seg_ptr_q, seg_ptr_k, extra=(m_q, m_k))
+    hit = _cross_bounds_cache.get(key)
+    if hit is None:
+        qbounds = torch.empty(2 * m_q, dtype=torch.int32, device=seg_ptr_q.device)
+        kbounds = torch.empty(2 * m_k, dtype=torch.int32, device=seg_ptr_q.device)
+        call("dfgnn_segment_cross_bounds", "segment_cross_bounds", seg_ptr_q.device, m_q, m_k, seg_ptr_q.numel() - 1, seg_ptr_q,
+             seg_ptr_k, qbounds, kbounds)
+        hit = _cross_bounds_cache.put(key, (qbounds, kbounds), seg_ptr_q, seg_ptr_k)
+    return hit
+
+
+def _segment_cross_checks(qbounds, Q, K, V, **like_Q):
+    m_q, h, f = check_feats(Q=Q, **like_Q)
+    m_k = check_cols("Q", Q, K=K, V=V)
+    _family(Q, torch.int32, (2 * m_q,), {"qbounds": qbounds})
+    return m_q, m_k, h, f
+
+
+def segment_mha_cross_inference(qbounds, Q, K, V, scale=1.0, form=0):
+    """-> out [m_q, h, f]; no statistics are written."""
+    m_q, m_k, h, f = _segment_cross_checks(qbounds, Q, K, V)
+    out = torch.empty_like(Q)
+    call("dfgnn_segment_mha_cross_fwd", "segment_mha_cross_inference", Q.device, m_q, m_k, h, f, float(scale), int(form), qbounds,
+         Q, K, V, out, None, None)
+    return out
+
+
+def segment_mha_cross_forward(qbounds, Q, K, V, scale=1.0, form=0):
+    """-> [out, row_max[m_q, h], row_sum[m_q, h]]: the training forward."""
+    m_q, m_k, h, f = _segment_cross_checks(qbounds, Q, K, V)
+    out, row_max, row_sum = torch.empty_like(Q), _empty(Q, m_q, h), _empty(Q, m_q, h)
+    call("dfgnn_segment_mha_cross_fwd", "segment_mha_cross_forward", Q.device, m_q, m_k, h, f, float(scale), int(form), qbounds,
+         Q, K, V, out, row_max, row_sum)
+    return [out, row_max, row_sum]
+
+
+def segment_mha_cross_backward(qbounds, kbounds, Q, K, V, row_max, row_sum, grad, scale=1.0, form=0):
+    """-> [dQ [m_q, h, f], dK, dV [m_k, h, f]] from the forward's row statistics."""
+    m_q, m_k, h, f = _segment_cross_checks(qbounds, Q, K, V, grad=grad)
+    _family(Q, torch.int32, (2 * m_k,), {"kbounds": kbounds})
+    check_2d(Q, m_q, h, row_max=row_max, row_sum=row_sum)
+    delta = _empty(Q, m_q, h)
+    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
+    call("dfgnn_segment_mha_cross_bwd", "segment_mha_cross_backward", Q.device, m_q, m_k, h, f, float(scale), int(form), qbounds,
+         kbounds, Q, K, V, row_max, row_sum, grad, dQ, dK, dV, delta)
+    return [dQ, dK, dV]
+
+
 # ---- the same pair with a pair bias (include/dfgnn_segment_bias.h): Graphormer-style global attention --------------------
 # bias fp32[h, n_pairs], n_pairs = sum of n_g^2: per head the graphs' packed row-major n_g x n_g blocks one after another.
 _pair_rows_cache = _KeyedCache()

@@ -20,8 +20,14 @@ with the table's gradient:
                 all of it inside the timed region
   plain         the unbiased pair
 and the peak of torch's allocator over one step of typed and of materialised, above what is allocated before the step.
-usage: python3 tools/segment_mha_bench.py [--shapes 4x32,8x16,1x128] [--steps 30] [--bias | --tbias [--types 20]]
-(DESIGN.md 3.3k, 3.3l, 3.3m hold the tables)"""
+--cross: the cross pair (SegmentCrossMHAFuse, include/dfgnn_segment_cross.h) with every batch as the KEY side and --seeds
+queries per graph (0: the square row, the queries are the keys' own array), one training step of
+  wide, split, auto   the three values of `form`
+  sdpa                the padded SDPA with [B, h, seeds, f] queries and the key-padding mask
+  self                (square row only) SegmentMHAFuse on the same arrays
+one JSON line per (batch, seeds, shape), appended to profiles/segment_cross_bench.jsonl.
+usage: python3 tools/segment_mha_bench.py [--shapes 4x32,8x16,1x128] [--steps 30] [--bias | --tbias [--types 20] | --cross [--seeds 1,4,16,0]]
+(DESIGN.md 3.3k, 3.3l, 3.3m, 3.3n hold the tables)"""
 import argparse
 import json
 import os
@@ -34,7 +40,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from torch.nn import functional as F  # noqa: E402
 
-from DFGNN.operators.fused_gtconv import GTConvFuse_rowstats, SegmentMHABiasFuse, SegmentMHAFuse, SegmentMHATBiasFuse  # noqa: E402
+from DFGNN.operators.fused_gtconv import (GTConvFuse_rowstats, SegmentCrossMHAFuse, SegmentMHABiasFuse, SegmentMHAFuse,  # noqa: E402
+                                          SegmentMHATBiasFuse)
 
 DEV = "cuda:0"
 BATCHES = {"zinc": (1024, 9, 37), "pattern": (256, 44, 188), "peptides": (128, 60, 240), "long": (16, 1000, 2000)}
@@ -66,8 +73,11 @@ def main():
     ap.add_argument("--tbias", action="store_true", help="time the typed pair against the materialised bias and the unbiased pair")
     ap.add_argument("--types", type=int, default=20, help="--tbias: rows of the table")
     ap.add_argument("--bias-max-pairs", type=int, default=40_000_000, help="skip batches whose padded mask would be larger")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "segment_mha_bench.jsonl"))
+    ap.add_argument("--cross", action="store_true", help="time the cross pair's forms against padded SDPA (and the self pair)")
+    ap.add_argument("--seeds", default="1,4,16,0", help="--cross: queries per graph, comma-separated; 0: queries = keys (square)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "segment_cross_bench.jsonl" if args.cross else "segment_mha_bench.jsonl")
     for name in args.batches.split(","):
         count, a, b = BATCHES[name]
         sizes = np.random.default_rng(7).integers(a, b + 1, size=count)
@@ -75,10 +85,11 @@ def main():
             h, f = (int(x) for x in shape.split("x"))
             if (args.bias or args.tbias) and len(sizes) * int(sizes.max()) ** 2 > args.bias_max_pairs:
                 continue
-            line = bench(args, name, sizes, h, f)
-            print(json.dumps(line), flush=True)
-            with open(args.out, "a") as fh:
-                fh.write(json.dumps(line) + "\n")
+            lines = [bench_cross(args, name, sizes, h, f, int(k)) for k in args.seeds.split(",")] if args.cross else [bench(args, name, sizes, h, f)]
+            for line in lines:
+                print(json.dumps(line), flush=True)
+                with open(args.out, "a") as fh:
+                    fh.write(json.dumps(line) + "\n")
 
 
 def bench(args, name, sizes, h, f):
@@ -156,6 +167,57 @@ def bench(args, name, sizes, h, f):
             if args.bias:
                 other.append(last[key][4][seg[prow], :, pos[prow], pcol].t())
             line[key + "_max_diff"] = max(float((x - y).abs().max()) for x, y in zip(last["new"], other))
+    return line
+
+
+def bench_cross(args, name, sizes, h, f, seeds):
+    """One training step of the cross pair with `sizes` as the key side and `seeds` queries per graph (0: the square row)."""
+    B, nmax = len(sizes), int(sizes.max())
+    qsizes = sizes if seeds == 0 else np.full(B, seeds)
+    ek, eq = (np.concatenate([[0], np.cumsum(s)]) for s in (sizes, qsizes))
+    m_k, m_q, qmax = int(ek[-1]), int(eq[-1]), int(qsizes.max())
+    sk, sq = (torch.tensor(e, dtype=torch.int32, device=DEV) for e in (ek, eq))
+    gen = torch.Generator().manual_seed(5)
+    Q0, dO = (torch.randn(m_q, h, f, generator=gen).to(DEV) for _ in range(2))
+    K0, V0 = (torch.randn(m_k, h, f, generator=gen).to(DEV) for _ in range(2))
+    scale = f ** -0.5
+
+    def padder(sz, ptr, m, width):        # row i of graph b at [b, :, i - lo_b]
+        seg = torch.repeat_interleave(torch.arange(B, device=DEV), torch.as_tensor(sz, device=DEV))
+        pos = torch.arange(m, device=DEV) - ptr[seg.long()].long()
+        return seg, pos, lambda x: torch.zeros(B, width, h, f, device=DEV).index_put_((seg, pos), x).transpose(1, 2).contiguous()
+    qseg, qpos, padq = padder(qsizes, sq, m_q, qmax)
+    kseg, kpos, padk = padder(sizes, sk, m_k, nmax)
+    keep = (torch.arange(nmax, device=DEV)[None, :] < torch.as_tensor(sizes, device=DEV)[:, None])[:, None, None, :]
+    forms = {key: (lambda q, k, v, form=form: SegmentCrossMHAFuse(sq, sk, q, k, v, scale, form), (Q0, K0, V0), dO)
+             for key, form in (("wide", 1), ("split", 2), ("auto", 0))}
+    forms["sdpa"] = (lambda q, k, v: F.scaled_dot_product_attention(q, k, v, attn_mask=keep, scale=scale),
+                     (padq(Q0), padk(K0), padk(V0)), padq(dO))
+    if seeds == 0:
+        forms["self"] = (lambda q, k, v: SegmentMHAFuse(sk, q, k, v, scale), (Q0, K0, V0), dO)
+    times, last = {k: [] for k in forms}, {}
+    for it in range(args.warmup + args.steps):
+        for key, (fn, inputs, grad) in forms.items():           # alternating: all forms see the same machine state
+            leaves = [x.detach().requires_grad_(True) for x in inputs]
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            out = fn(*leaves)
+            grads = torch.autograd.grad(out, leaves, grad)
+            b.record()
+            torch.cuda.synchronize()
+            if it >= args.warmup:
+                times[key].append(a.elapsed_time(b) * 1e3)
+            last[key] = [out.detach()] + list(grads)
+    line = {"tool": "segment_cross_bench", "batch": name, "graphs": B, "seeds": seeds, "m_q": m_q, "m_k": m_k, "n_max": nmax, "h": h,
+            "f": f, "steps": args.steps}
+    for key in forms:
+        line[key + "_us"], line[key + "_us_min"] = round(float(np.median(times[key])), 1), round(float(np.min(times[key])), 1)
+        other = last[key]
+        if key == "sdpa":
+            unq, unk = (lambda x: x.transpose(1, 2)[qseg, qpos]), (lambda x: x.transpose(1, 2)[kseg, kpos])
+            other = [unq(other[0]), unq(other[1]), unk(other[2]), unk(other[3])]
+        if key != "wide":
+            line[key + "_max_diff"] = max(float((x - y).abs().max()) for x, y in zip(last["wide"], other))
     return line
 
 
