@@ -5,7 +5,8 @@ import torch
 import torch.nn as nn
 
 import fused_gtconv as fused_gt
-from DFGNN.operators.fused_gtconv import SegmentCrossMHAFuse, SegmentMHABiasFuse, SegmentMHAFuse, SegmentMHATBiasFuse
+from DFGNN.operators.fused_gtconv import (SegmentCrossMHAFuse, SegmentMHABiasFuse, SegmentMHAFuse, SegmentMHAGateFuse,
+                                          SegmentMHATBiasFuse)
 
 
 def segment_offsets(segments, device):
@@ -35,13 +36,18 @@ class GlobalMHA(nn.Module):
         self.v_proj = nn.Linear(in_size, out_size)
         self.out_proj = nn.Linear(out_size, out_size)
 
-    def forward(self, h, seg_ptr, fuse=True, bias=None, pair_types=None, pair_table=None):
+    def forward(self, h, seg_ptr, fuse=True, bias=None, pair_types=None, pair_table=None, gate=None, return_logits=False):
         """h [N, in]; seg_ptr: int32[n_seg + 1] offsets (a tensor kept across layers and steps is looked up, not rebuilt) or
         the batch's graph sizes.  bias: None or fp32 [heads, sum of n_g^2], added to the logits -- per head the graphs'
         packed row-major n_g x n_g blocks one after another (PairBias makes one from pair types).  pair_types [sum of n_g^2]
         (integers, best uint8) with pair_table fp32 [T, heads] instead of bias: the same bias, table.t()[:, pair_types],
         looked up inside the fused kernels for T <= 256 -- no plane is built and the table's gradient is summed there.
+        gate: None or fp32 [heads, sum of n_g^2] like bias (which it needs): the attention weights are multiplied by
+        sigmoid(gate) after the softmax.  return_logits (with a bias): -> (out, logits [heads, sum of n_g^2]), the logits
+        scale Q K^T + bias as an output whose gradient flows back (EGT's pair channel; see EGTAttention).
         fuse=False, or a head shape the fused pair does not serve: plain torch, graph by graph."""
+        if (gate is not None or return_logits) and (bias is None or pair_types is not None):
+            raise ValueError("gate and return_logits go with a bias plane")
         if (pair_types is None) != (pair_table is None):
             raise ValueError("pair_types and pair_table go together")
         if pair_types is not None and bias is not None:
@@ -50,7 +56,10 @@ class GlobalMHA(nn.Module):
         n = len(h)
         q, k, v = (p(h).reshape(n, self.num_heads, self.head_dim) for p in (self.q_proj, self.k_proj, self.v_proj))
         if fuse and h.is_cuda and fused_gt.segment_mha_applies(self.num_heads, self.head_dim):
-            if pair_types is not None:
+            if gate is not None or return_logits:
+                out = SegmentMHAGateFuse(seg_ptr, q.contiguous(), k.contiguous(), v.contiguous(), bias.contiguous(),
+                                         None if gate is None else gate.contiguous(), self.scaling, return_logits)
+            elif pair_types is not None:
                 if pair_table.size(0) <= fused_gt.SEGMENT_TBIAS_MAX_TYPES:
                     pair_types = pair_types.to(torch.uint8)   # (no host read; a no-op for uint8)
                 out = SegmentMHATBiasFuse(seg_ptr, q.contiguous(), k.contiguous(), v.contiguous(), pair_types.contiguous(),
@@ -62,21 +71,30 @@ class GlobalMHA(nn.Module):
         else:
             if pair_types is not None:
                 bias = pair_table.t()[:, pair_types.long()]
-            out = self.forward_plain(seg_ptr, q, k, v, bias)
+            out = self.forward_plain(seg_ptr, q, k, v, bias, gate, return_logits)
+        if return_logits:
+            return self.out_proj(out[0].reshape(n, -1)), out[1]
         return self.out_proj(out.reshape(n, -1))
 
-    def forward_plain(self, seg_ptr, q, k, v, bias=None):
-        outs = []
+    def forward_plain(self, seg_ptr, q, k, v, bias=None, gate=None, return_logits=False):
+        outs, logits = [], []
         ends = seg_ptr.tolist()
         at = 0
         for lo, hi in zip(ends[:-1], ends[1:]):
             s = torch.einsum("ihf,jhf->hij", q[lo:hi], k[lo:hi]) * self.scaling
+            n = hi - lo
             if bias is not None:
-                n = hi - lo
                 s = s + bias[:, at:at + n * n].reshape(bias.size(0), n, n)
-                at += n * n
-            outs.append(torch.einsum("hij,jhf->ihf", torch.softmax(s, dim=-1), v[lo:hi]))
-        return torch.cat(outs) if outs else torch.empty_like(q)
+            a = torch.softmax(s, dim=-1)
+            if gate is not None:
+                a = a * torch.sigmoid(gate[:, at:at + n * n].reshape(gate.size(0), n, n))
+            at += n * n
+            outs.append(torch.einsum("hij,jhf->ihf", a, v[lo:hi]))
+            logits.append(s.reshape(s.size(0), n * n))
+        out = torch.cat(outs) if outs else torch.empty_like(q)
+        if return_logits:
+            return out, (torch.cat(logits, dim=1) if logits else q.new_empty(q.size(1), 0))
+        return out
 
 
 class PairBias(nn.Module):
@@ -91,6 +109,27 @@ class PairBias(nn.Module):
 
     def forward(self, pair_types):
         return self.table.t()[:, pair_types]
+
+
+class EGTAttention(nn.Module):
+    """The attention of an Edge-augmented Graph Transformer layer (Hussain et al.): a feature per node PAIR gives every head a
+    bias on the logit and a sigmoid gate on the attention weight, and the logits update the pair channel:
+      x = scale Q K^T + W_b e,   node_out = W_o concat_heads((softmax_graph(x) * sigmoid(W_g e)) V),   pair_out = W_e x
+    pair_feat [sum of n_g^2, pair_dim] lists every graph's n x n pairs row-major, graph after graph -> (node_out [N, dim],
+    pair_out [sum of n_g^2, pair_dim]).  Fused (GlobalMHA, SegmentMHAGateFuse) nothing of size heads x n^2 is saved for the
+    backward besides the three planes themselves."""
+
+    def __init__(self, dim, pair_dim, heads):
+        super().__init__()
+        self.mha = GlobalMHA(dim, dim, heads)
+        self.pair_bias = nn.Linear(pair_dim, heads)
+        self.pair_gate = nn.Linear(pair_dim, heads)
+        self.pair_out = nn.Linear(heads, pair_dim)
+
+    def forward(self, x, pair_feat, seg_ptr, fuse=True):
+        bias, gate = self.pair_bias(pair_feat).t().contiguous(), self.pair_gate(pair_feat).t().contiguous()
+        node_out, logits = self.mha(x, seg_ptr, fuse=fuse, bias=bias, gate=gate, return_logits=True)
+        return node_out, self.pair_out(logits.t())
 
 
 class CrossMHA(nn.Module):

@@ -9,7 +9,7 @@ from .GT.gtconv_layer_gate import SparseMHA_gate  # noqa: F401
 from .GT.gtconv_layer_typed import SparseMHA_typed, preprocess_types  # noqa: F401
 from .GT.gtconv_layer_tbias import SparseMHA_tbias  # noqa: F401
 from .GT.gtconv_layer_forward import SparseMHA_forward  # noqa: F401
-from .GT.gtconv_layer_global import AttentionReadout, CrossMHA, GlobalMHA, PairBias  # noqa: F401
+from .GT.gtconv_layer_global import AttentionReadout, CrossMHA, EGTAttention, GlobalMHA, PairBias  # noqa: F401
 from .GT.gtconv_layer_rowstats import SparseMHA_rowstats  # noqa: F401
 from .model import Model, choose_Inproj  # noqa: F401
 from .util import (load_graphconv_layer, load_layer_AGNN, load_layer_DOTGAT, load_layer_GAT, load_layer_GATv2, load_layer_GatedGCN, load_layer_GT, load_prepfunc,  # noqa: F401

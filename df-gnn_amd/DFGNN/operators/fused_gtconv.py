@@ -193,6 +193,51 @@ def SegmentMHABiasFuse(seg_ptr, Q, K, V, bias, scale=1.0):
     return FusedSegmentMHABiasFunction.apply(bounds, row_off, Q, K, V, bias, scale)
 
 
+class FusedSegmentMHAGateFunction(torch.autograd.Function):
+    """FusedSegmentMHABiasFunction with a sigmoid gate on the attention weights and, on request, the logits as a second output
+    (include/dfgnn_segment_gate.h).  Saved between forward and backward: Q, K, V, bias, gate and the row statistics -- not the
+    logits, the softmax or the gates' sigmoid.  The backward passes NULL for every gradient nobody asked for, and NULL for
+    dlogits when the logit output received no gradient."""
+
+    @staticmethod
+    def forward(ctx, bounds, row_off, Q, K, V, bias, gate, scale, return_logits):
+        out, row_max, row_sum, logits = fused_gt.segment_mha_gate_forward(bounds, row_off, bias, gate, Q, K, V, scale,
+                                                                          need_logits=return_logits)
+        ctx.save_for_backward(bounds, row_off, Q, K, V, bias, row_max, row_sum, *(() if gate is None else (gate,)))
+        ctx.scale = scale
+        if not return_logits:
+            return out
+        ctx.set_materialize_grads(False)      # an unused output arrives as None, not as a plane of zeros
+        return out, logits
+
+    @staticmethod
+    def backward(ctx, grad_out, grad_logits=None):
+        bounds, row_off, Q, K, V, bias, row_max, row_sum, *rest = ctx.saved_tensors
+        gate = rest[0] if rest else None
+        if grad_out is None:
+            grad_out = torch.zeros_like(Q)
+        dQ, dK, dV, dbias, dgate = fused_gt.segment_mha_gate_backward(
+            bounds, row_off, bias, gate, Q, K, V, row_max, row_sum, grad_out.contiguous(),
+            None if grad_logits is None else grad_logits.contiguous(), ctx.scale,
+            need_dbias=ctx.needs_input_grad[5], need_dgate=ctx.needs_input_grad[6])
+        return None, None, dQ, dK, dV, dbias, dgate, None, None
+
+
+def SegmentMHAGateFuse(seg_ptr, Q, K, V, bias, gate, scale=1.0, return_logits=False):
+    """EGT-style attention: out = (softmax_graph(x) * sigmoid(gate)) V with x = scale Q K^T + bias, the gate acting after the
+    softmax.  bias and gate fp32 [h, n_pairs] in the layout of SegmentMHABiasFuse; gate None means no gate.  return_logits:
+    -> (out, logits) with logits = x [h, n_pairs], an output like any other -- its gradient flows back into Q, K and bias."""
+    m = Q.size(0)
+    bounds = fused_gt.segment_bounds(seg_ptr, m)
+    _, row_off = fused_gt.segment_pair_rows(seg_ptr, m)
+    needs = any(t is not None and t.requires_grad for t in (Q, K, V, bias, gate))
+    if not (torch.is_grad_enabled() and needs):
+        out, _, _, logits = fused_gt.segment_mha_gate_forward(bounds, row_off, bias, gate, Q, K, V, scale, stats=False,
+                                                              need_logits=return_logits)
+        return (out, logits) if return_logits else out
+    return FusedSegmentMHAGateFunction.apply(bounds, row_off, Q, K, V, bias, gate, scale, return_logits)
+
+
 class FusedSegmentMHATBiasFunction(torch.autograd.Function):
     """FusedSegmentMHABiasFunction with the bias looked up in the kernels: table[T, h] by the pair's type
     (include/dfgnn_segment_tbias.h).  Saved between forward and backward: Q, K, V, the types, the table and the row statistics;

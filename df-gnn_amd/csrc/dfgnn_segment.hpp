@@ -46,6 +46,11 @@
 // (W = 64: a slot and a bank of its own; smaller W for larger T: the 64 / W lanes of a slot take turns, a wave's DS
 // operations execute in issue order), the workgroup folds slots and waves in a fixed order into one partial [T] per work
 // item, and segment_tbias_reduce_kernel sums the partials of a head in a fixed order.
+//
+// GATES AND A LOGIT OUTPUT (include/dfgnn_segment_gate.h; instantiated in segment_gate.hip): the plane pair with
+// out_i = sum_j P_ij g_ij V_j, g = sigmoid(gate), and x itself as an output whose gradient re-enters: dS = P (g dP - t) + dlogits,
+// t_i = sum_j P_ij g_ij dP_ij.  Four more optional planes in the bias' layout and lane ownership (gate, logits, dlogits, dgate);
+// g is multiplied into the raw product dP before its scale, so g = 1 leaves every expression -- and every bit -- of the plane pair.
 #pragma once
 #include "dfgnn_dense.hpp"
 #include "dfgnn_launch.hpp"
@@ -67,7 +72,10 @@ struct SegCfg {
   static constexpr int kLds = kSegFixedLds + segment_tile_bytes(F, TR, ROW_WORDS);
   static_assert(TR % 32 == 0 && kLds <= kBlockLdsBudget, "a tile is whole 32-row k-blocks inside the LDS budget");
 };
-enum class SegKind { None, Plane, Typed };  // the bias of a logit: none, read from a plane, looked up by the pair's type
+// the bias of a logit: none, read from a plane, looked up by the pair's type; Gated: the plane pair with a sigmoid gate on the
+// attention weights and the logits as an output (below)
+enum class SegKind { None, Plane, Typed, Gated };
+constexpr bool seg_plane(SegKind k) { return k == SegKind::Plane || k == SegKind::Gated; }  // a bias plane is read
 constexpr int kSegCapFwd = 8192, kSegCapBwd = 4096;
 template <int FR> using SegFwdCfg = SegCfg<FR, 0, kSegCapFwd>;
 template <int FR> using SegDqCfg = SegCfg<FR, 0, kSegCapBwd>;
@@ -205,6 +213,17 @@ __device__ __forceinline__ void seg_bias_store4(float *__restrict__ dbias, long 
       if (j0 + r >= lo && j0 + r < hi) dbias[at + j0 + r] = d[r];
   }
 }
+
+// ---- pair gates and the logit output (SegKind::Gated) ---------------------------------------------------------------------
+// The bias planes plus four more in the same layout, each optional (null: wave-uniform tests inside the Gated instances).
+struct SegGate : SegBias {
+  const float *gate;     // fp32[h, n_pairs] or null: g = 1
+  float *dgate;          // (dQ kernel) or null
+  float *logits;         // (forward) or null
+  const float *dlogits;  // (backward) or null: no second stream into dS
+};
+// 1 / (1 + e^-x): e^-x = inf gives 0, e^-x = 0 gives 1 -- finite x of any size stays in [0, 1]
+__device__ __forceinline__ float seg_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + fast_exp(-x)); }
 
 // ---- the typed pair bias ----------------------------------------------------------------------------------------------
 constexpr int kSegMaxTypes = 256;                    // a type is a byte
@@ -345,7 +364,7 @@ __device__ __forceinline__ void segment_fwd_body(float *lds, int m, int h, float
   seg_rows_load<FR>(q, Q + hoff, hf, st.row, m, L);
   float mrun = -INFINITY, lrun = 0.f;
   long long bat = kSegNoBias;
-  if constexpr (KIND == SegKind::Plane)
+  if constexpr (seg_plane(KIND))
     if (st.row < m) bat = seg_bias_at(sb, head, st.row, st.lo, st.hi);
   [[maybe_unused]] float *tab = lds + C::kLds / 4;  // (Typed) the head's column of the table
   if constexpr (KIND == SegKind::Typed) {
@@ -362,11 +381,21 @@ __device__ __forceinline__ void segment_fwd_body(float *lds, int m, int h, float
     f32x4 S[NT];
     const float c = im.ainv * q.inv * scale;
     float mx = -INFINITY;
-    [[maybe_unused]] f32x4 B[KIND == SegKind::Plane ? NT : 1];  // the tile's bias: issued ahead of the products
-    if constexpr (KIND == SegKind::Plane) {
+    [[maybe_unused]] f32x4 B[seg_plane(KIND) ? NT : 1];  // the tile's bias: issued ahead of the products
+    if constexpr (seg_plane(KIND)) {
 #pragma unroll
       for (int jt = 0; jt < NT; ++jt)
         B[jt] = st.sees(t + 16 * jt, 16) ? seg_bias_load4(sb.bias, bat, t + 16 * jt + 4 * L.mq, st.lo, st.hi) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    [[maybe_unused]] f32x4 G[KIND == SegKind::Gated ? NT : 1];  // (Gated) the tile's gate values, loaded with the bias
+    [[maybe_unused]] bool gated = false;
+    if constexpr (KIND == SegKind::Gated) {
+      gated = sb.gate != nullptr;
+      if (gated) {
+#pragma unroll
+        for (int jt = 0; jt < NT; ++jt)
+          G[jt] = st.sees(t + 16 * jt, 16) ? seg_bias_load4(sb.gate, bat, t + 16 * jt + 4 * L.mq, st.lo, st.hi) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
     }
     [[maybe_unused]] unsigned ty[KIND == SegKind::Typed ? NT : 1];  // the tile's types, likewise; looked up under the products
     if constexpr (KIND == SegKind::Typed) {
@@ -382,12 +411,16 @@ __device__ __forceinline__ void segment_fwd_body(float *lds, int m, int h, float
       for (int r = 0; r < 4; ++r) {
         const int j = t + 16 * jt + 4 * L.mq + r;
         float s;
-        if constexpr (KIND == SegKind::Plane) s = fmaf(S[jt][r], c, B[jt][r]);
+        if constexpr (seg_plane(KIND)) s = fmaf(S[jt][r], c, B[jt][r]);
         else if constexpr (KIND == SegKind::Typed) s = fmaf(S[jt][r], c, bat == kSegNoBias ? 0.f : seg_table_at(tab, ty[jt], r, sb.T));
         else s = S[jt][r] * c;
+        if constexpr (KIND == SegKind::Gated) B[jt][r] = s;  // the logit itself, before the mask
         const float x = (seen && j >= st.lo && j < st.hi) ? s : -INFINITY;
         S[jt][r] = x;
         mx = fmaxf(mx, x);
+      }
+      if constexpr (KIND == SegKind::Gated) {  // logits = x, one store per valid pair (the mask of the loads)
+        if (sb.logits && seen) seg_bias_store4(sb.logits, bat, t + 16 * jt + 4 * L.mq, st.lo, st.hi, B[jt]);
       }
     }
     // online softmax: the running maximum and sum of the row, the accumulators rescaled only when the maximum moved
@@ -402,6 +435,8 @@ __device__ __forceinline__ void segment_fwd_body(float *lds, int m, int h, float
         const float p = fast_exp(S[jt][r] - base);  // exp(-inf) = 0 for the masked pairs
         S[jt][r] = p;
         sum += p;
+        if constexpr (KIND == SegKind::Gated)  // the second product takes e^{x - m} g, the row sum stays ungated
+          if (gated && bat != kSegNoBias) S[jt][r] = p * seg_sigmoid(G[jt][r]);
       }
     lrun = lrun * alpha + xor16_32_sum(sum);
     mrun = mnew;
@@ -427,19 +462,30 @@ __device__ __forceinline__ void segment_fwd_body(float *lds, int m, int h, float
   }
 }
 
-// P of this strip against the resident K tile, from the rows' saved statistics; masked pairs are 0
+// P of this strip against the resident K tile, from the rows' saved statistics; masked pairs are 0.  dP = <dO_i, V_j>.
+// (Gated) G[NT]: g of the same pairs, 1 where there is no gate (gate null, or a row without a place in the planes), and dP
+// comes back as g dP: the gate is folded into the raw product before its scale, so that g = 1 leaves the plane pair's bits
 template <class C, int FR, SegKind KIND = SegKind::None>
 __device__ __forceinline__ void seg_recompute_p(f32x4 (&S)[C::NT], f32x4 (&dP)[C::NT], const SegImages &im, int t,
                                                 const SegStrip &st, const SegRows<FR> &q, const SegRows<FR> &g, float scale,
                                                 float mx, float il, const LaneIds &L, const float *__restrict__ bias = nullptr,
                                                 long long bat = kSegNoBias, const SegTypedLane *tl = nullptr,
-                                                unsigned *ty = nullptr) {
+                                                unsigned *ty = nullptr, const float *__restrict__ gate = nullptr,
+                                                f32x4 *G = nullptr) {
   const float c = im.ainv * q.inv * scale, cd = im.binv * g.inv;
-  [[maybe_unused]] f32x4 B[KIND == SegKind::Plane ? C::NT : 1];  // the tile's bias: issued ahead of the products
-  if constexpr (KIND == SegKind::Plane) {
+  [[maybe_unused]] f32x4 B[seg_plane(KIND) ? C::NT : 1];  // the tile's bias: issued ahead of the products
+  if constexpr (seg_plane(KIND)) {
 #pragma unroll
     for (int jt = 0; jt < C::NT; ++jt)
       B[jt] = st.sees(t + 16 * jt, 16) ? seg_bias_load4(bias, bat, t + 16 * jt + 4 * L.mq, st.lo, st.hi) : f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  [[maybe_unused]] const bool gated = gate != nullptr && bat != kSegNoBias;
+  if constexpr (KIND == SegKind::Gated) {  // the gate values with the bias; turned into g under the products
+    if (gate) {
+#pragma unroll
+      for (int jt = 0; jt < C::NT; ++jt)
+        G[jt] = st.sees(t + 16 * jt, 16) ? seg_bias_load4(gate, bat, t + 16 * jt + 4 * L.mq, st.lo, st.hi) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
   }
   if constexpr (KIND == SegKind::Typed) {  // ty[NT]: the tile's types, the caller's to keep
 #pragma unroll
@@ -455,11 +501,15 @@ __device__ __forceinline__ void seg_recompute_p(f32x4 (&S)[C::NT], f32x4 (&dP)[C
     for (int r = 0; r < 4; ++r) {
       const int j = t + 16 * jt + 4 * L.mq + r;
       float e;
-      if constexpr (KIND == SegKind::Plane) e = fast_exp(fmaf(S[jt][r], c, B[jt][r]) - mx) * il;
+      if constexpr (seg_plane(KIND)) e = fast_exp(fmaf(S[jt][r], c, B[jt][r]) - mx) * il;
       else if constexpr (KIND == SegKind::Typed)
         e = fast_exp(fmaf(S[jt][r], c, tl->at == kSegNoBias ? 0.f : seg_table_at(tl->tab, ty[jt], r, tl->T)) - mx) * il;
       else e = fast_exp(S[jt][r] * c - mx) * il;
       S[jt][r] = (seen && j >= st.lo && j < st.hi) ? e : 0.f;
+      if constexpr (KIND == SegKind::Gated) {
+        G[jt][r] = gated ? seg_sigmoid(G[jt][r]) : 1.f;
+        dP[jt][r] *= G[jt][r];
+      }
       dP[jt][r] *= cd;
     }
   }
@@ -486,7 +536,7 @@ __device__ __forceinline__ void segment_dq_body(float *lds, int m, int h, float 
   const size_t si = (size_t)min(st.row, m - 1) * h + head;
   const float mx = row_max[si], rs = row_sum[si], il = rs > 0.f ? 1.f / rs : 0.f;
   long long bat = kSegNoBias;
-  if constexpr (KIND == SegKind::Plane)
+  if constexpr (seg_plane(KIND))
     if (st.row < m) bat = seg_bias_at(sb, head, st.row, st.lo, st.hi);
   // (Typed) behind the tile: the head's column of the table, then one dB table per wave, zeroed by its wave
   [[maybe_unused]] float *tab = lds + C::kLds / 4, *tabs = tab + kSegMaxTypes;
@@ -503,7 +553,7 @@ __device__ __forceinline__ void segment_dq_body(float *lds, int m, int h, float 
     }
   }
 
-  float tsum = 0.f;  // pass 1: t_i = sum_j P_ij dP_ij
+  float tsum = 0.f;  // pass 1: t_i = sum_j P_ij dP_ij (Gated: dP is g dP from here on)
   seg_tile_loop<C>(lds, K + hoff, V + hoff, hf, t0, t1, FR, [](int) {}, [](float *) {}, [&](int t, const SegImages &im) {
     if (!st.sees(t, TR)) return;
     const LaneIds L = lane_ids();
@@ -511,6 +561,9 @@ __device__ __forceinline__ void segment_dq_body(float *lds, int m, int h, float 
     if constexpr (KIND == SegKind::Typed) {
       unsigned ty[NT];
       seg_recompute_p<C, FR, KIND>(S, dP, im, t, st, q, g, scale, mx, il, L, nullptr, kSegNoBias, &tl, ty);
+    } else if constexpr (KIND == SegKind::Gated) {
+      f32x4 G[NT];
+      seg_recompute_p<C, FR, KIND>(S, dP, im, t, st, q, g, scale, mx, il, L, sb.bias, bat, nullptr, nullptr, sb.gate, G);
     } else {
       seg_recompute_p<C, FR, KIND>(S, dP, im, t, st, q, g, scale, mx, il, L, sb.bias, bat);
     }
@@ -522,7 +575,7 @@ __device__ __forceinline__ void segment_dq_body(float *lds, int m, int h, float 
   const float dl = xor16_32_sum(tsum);
   if (st.row < m && L.mq == 0) delta[si] = dl;
 
-  f32x4 dq[FT];  // pass 2: dS = P (dP - t), dQ += dS K
+  f32x4 dq[FT];  // pass 2: dS = P (dP - t), dQ += dS K (Gated: dS = P (g dP - t) + dlogits)
 #pragma unroll
   for (int ft = 0; ft < FT; ++ft) dq[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
   seg_tile_loop<C>(lds, K + hoff, V + hoff, hf, t0, t1, FR, [](int) {}, [](float *) {}, [&](int t, const SegImages &im) {
@@ -530,20 +583,52 @@ __device__ __forceinline__ void segment_dq_body(float *lds, int m, int h, float 
     const LaneIds L = lane_ids();
     f32x4 S[NT], dP[NT];
     [[maybe_unused]] unsigned ty[KIND == SegKind::Typed ? NT : 1];
+    [[maybe_unused]] f32x4 G[KIND == SegKind::Gated ? NT : 1], DL[KIND == SegKind::Gated ? NT : 1];
+    if constexpr (KIND == SegKind::Gated) {  // the second stream into dS, issued ahead of the products like the bias
+      if (sb.dlogits) {
+#pragma unroll
+        for (int jt = 0; jt < NT; ++jt)
+          DL[jt] = st.sees(t + 16 * jt, 16) ? seg_bias_load4(sb.dlogits, bat, t + 16 * jt + 4 * L.mq, st.lo, st.hi) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
     if constexpr (KIND == SegKind::Typed) seg_recompute_p<C, FR, KIND>(S, dP, im, t, st, q, g, scale, mx, il, L, nullptr, kSegNoBias, &tl, ty);
+    else if constexpr (KIND == SegKind::Gated) seg_recompute_p<C, FR, KIND>(S, dP, im, t, st, q, g, scale, mx, il, L, sb.bias, bat, nullptr, nullptr, sb.gate, G);
     else seg_recompute_p<C, FR, KIND>(S, dP, im, t, st, q, g, scale, mx, il, L, sb.bias, bat);
     float am = 0.f;
+    if constexpr (KIND == SegKind::Gated) {
+      // dgate = (g dP) P (1 - g) needs dP, P and g of the same pair: stored before dS takes P's registers
+      if (sb.dgate) {
 #pragma unroll
-    for (int jt = 0; jt < NT; ++jt)
+        for (int jt = 0; jt < NT; ++jt)
+          if (st.sees(t + 16 * jt, 16)) {
+            f32x4 dg;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        S[jt][r] *= dP[jt][r] - dl;
-        am = fmaxf(am, fabsf(S[jt][r]));
+            for (int r = 0; r < 4; ++r) dg[r] = dP[jt][r] * S[jt][r] * (1.f - G[jt][r]);
+            seg_bias_store4(sb.dgate, bat, t + 16 * jt + 4 * L.mq, st.lo, st.hi, dg);
+          }
       }
+      const bool second = sb.dlogits != nullptr;
+#pragma unroll
+      for (int jt = 0; jt < NT; ++jt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          S[jt][r] *= dP[jt][r] - dl;
+          if (second) S[jt][r] += DL[jt][r];  // (a masked pair loaded 0)
+          am = fmaxf(am, fabsf(S[jt][r]));    // the wave's dS scale is taken with dlogits in it
+        }
+    } else {
+#pragma unroll
+      for (int jt = 0; jt < NT; ++jt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          S[jt][r] *= dP[jt][r] - dl;
+          am = fmaxf(am, fabsf(S[jt][r]));
+        }
+    }
     if constexpr (KIND == SegKind::Typed) {  // dB += dS by type, in this wave's table
       if (sb.ws) seg_dtable_add<NT>(wtab, sb, S, ty, st, t, bat == kSegNoBias, L);
     }
-    if constexpr (KIND == SegKind::Plane) {  // dbias = dS, one store per valid pair (the mask of the loads)
+    if constexpr (seg_plane(KIND)) {  // dbias = dS, one store per valid pair (the mask of the loads)
       if (sb.dbias) {
 #pragma unroll
         for (int jt = 0; jt < NT; ++jt)
@@ -607,7 +692,7 @@ __device__ __forceinline__ void segment_dkv_body(float *lds, int m, int h, float
       xd = delta[si];
       xlo = t + tid < t1 ? tbounds[2 * i] : 0;  // a row past the range sees nothing
       xhi = t + tid < t1 ? tbounds[2 * i + 1] : 0;
-      if constexpr (KIND == SegKind::Plane) xat = seg_bias_at(sb, head, i, xlo, xhi);
+      if constexpr (seg_plane(KIND)) xat = seg_bias_at(sb, head, i, xlo, xhi);
       if constexpr (KIND == SegKind::Typed) xat = seg_types_at(sb, i, xlo, xhi);
     }
   };
@@ -637,7 +722,10 @@ __device__ __forceinline__ void segment_dkv_body(float *lds, int m, int h, float
       const bool seen = st.sees(t + 16 * u, 16);
       const int at = 16 * u + 4 * L.mq;
       [[maybe_unused]] f32x4 B = {0.f, 0.f, 0.f, 0.f};  // bias of (query at + r, key j): issued ahead of the products
-      if constexpr (KIND == SegKind::Plane) {
+      // (Gated) g and dlogits of the same pairs, single dwords like the bias: 1 and 0 where there is none
+      [[maybe_unused]] f32x4 Gq = {1.f, 1.f, 1.f, 1.f}, DLq = {0.f, 0.f, 0.f, 0.f};
+      [[maybe_unused]] unsigned inm = 0;  // (Gated) bit r: key j lies in the range of query at + r -- lo and hi are not kept under the products
+      if constexpr (seg_plane(KIND)) {
         if (seen) {
           const int4 al = *reinterpret_cast<const int4 *>(im.rows + 5 * TR + at), ah = *reinterpret_cast<const int4 *>(im.rows + 6 * TR + at);
           const int4 lo = *reinterpret_cast<const int4 *>(im.rows + 3 * TR + at), hi = *reinterpret_cast<const int4 *>(im.rows + 4 * TR + at);
@@ -646,7 +734,14 @@ __device__ __forceinline__ void segment_dkv_body(float *lds, int m, int h, float
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const long long a = (long long)(((unsigned long long)(unsigned)ahr[r] << 32) | (unsigned)alr[r]);
-            if (a != kSegNoBias && j >= lor[r] && j < hir[r]) B[r] = sb.bias[a + j];
+            if constexpr (KIND == SegKind::Gated) inm |= (j >= lor[r] && j < hir[r]) ? 1u << r : 0u;
+            if (a != kSegNoBias && j >= lor[r] && j < hir[r]) {
+              B[r] = sb.bias[a + j];
+              if constexpr (KIND == SegKind::Gated) {
+                if (sb.gate) Gq[r] = seg_sigmoid(sb.gate[a + j]);
+                if (sb.dlogits) DLq[r] = sb.dlogits[a + j];
+              }
+            }
           }
         }
       }
@@ -680,9 +775,18 @@ __device__ __forceinline__ void segment_dkv_body(float *lds, int m, int h, float
         float e;
         if constexpr (KIND != SegKind::None) e = fast_exp(fmaf(S[u][r], c, B[r]) - mxr[r]) * ilr[r];
         else e = fast_exp(S[u][r] * c - mxr[r]) * ilr[r];
-        const float p = (seen && j >= lor[r] && j < hir[r]) ? e : 0.f;
-        const float ds = p * (dP[u][r] * cd - dlr[r]);
-        S[u][r] = p;
+        bool in;
+        if constexpr (KIND == SegKind::Gated) in = (inm >> r) & 1u;  // (set only where seen)
+        else in = seen && j >= lor[r] && j < hir[r];
+        const float p = in ? e : 0.f;
+        float ds;
+        if constexpr (KIND == SegKind::Gated) {  // dV takes P g, dK the whole dS = P (g dP - t) + dlogits; g folded as in seg_recompute_p
+          ds = p * ((dP[u][r] * Gq[r]) * cd - dlr[r]) + DLq[r];
+          S[u][r] = p * Gq[r];
+        } else {
+          ds = p * (dP[u][r] * cd - dlr[r]);
+          S[u][r] = p;
+        }
         dP[u][r] = ds;
         am = fmaxf(am, fabsf(ds));
       }

@@ -131,6 +131,14 @@ SEGMENT_TBIAS_SIGNATURES = {
     "dfgnn_segment_mha_tbias_bwd": [_i, _i, _i, _f, _vp, _vp, ctypes.c_longlong, _vp, _i] + [_vp] * 14,
 }
 
+# the plane pair with pair gates and a logit output: include/dfgnn_segment_gate.h one to one (checked by
+# tests/test_segment_gate_host.py); all answer an int
+SEGMENT_GATE_SIGNATURES = {
+    "dfgnn_segment_gate_abi_version": [],
+    "dfgnn_segment_mha_gate_fwd": [_i, _i, _i, _f, _vp, _vp, ctypes.c_longlong] + [_vp] * 10,
+    "dfgnn_segment_mha_gate_bwd": [_i, _i, _i, _f, _vp, _vp, ctypes.c_longlong] + [_vp] * 16,
+}
+
 # the cross pair, queries and keys of two node arrays: include/dfgnn_segment_cross.h one to one (checked by
 # tests/test_segment_cross_host.py); all answer an int
 SEGMENT_CROSS_SIGNATURES = {
@@ -194,7 +202,7 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
         for name, argtypes in (list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(SEGMENT_SIGNATURES.items()) +
                                list(SEGMENT_BIAS_SIGNATURES.items()) + list(SEGMENT_TBIAS_SIGNATURES.items()) +
-                               list(SEGMENT_CROSS_SIGNATURES.items())):
+                               list(SEGMENT_CROSS_SIGNATURES.items()) + list(SEGMENT_GATE_SIGNATURES.items())):
             fn = getattr(L, name)  # AttributeError if the library is stale
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int

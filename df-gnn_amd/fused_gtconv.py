@@ -957,6 +957,44 @@ def segment_mha_bias_backward(bounds, row_off, bias, Q, K, V, row_max, row_sum, 
     return [dQ, dK, dV, dbias]
 
 
+# ---- pair gates and a logit output (include/dfgnn_segment_gate.h): EGT-style global attention ------------------------------
+# out = (softmax(x) * sigmoid(gate)) V with x = scale Q K^T + bias; gate [h, n_pairs] in the layout of bias, or None (g = 1).
+def _segment_gate_checks(bounds, row_off, bias, gate, Q, K, V, **like_Q):
+    m, h, f, n_pairs = _segment_bias_checks(bounds, row_off, bias, Q, K, V, **like_Q)
+    if gate is not None:
+        _family(Q, torch.float32, (h, n_pairs), {"gate": gate})
+    return m, h, f, n_pairs
+
+
+def segment_mha_gate_forward(bounds, row_off, bias, gate, Q, K, V, scale=1.0, stats=True, need_logits=False):
+    """-> [out, row_max[m, h], row_sum[m, h], logits[h, n_pairs]]: the statistics are None without `stats` (inference), the
+    logits x None without need_logits (then nothing of that size is written)."""
+    m, h, f, n_pairs = _segment_gate_checks(bounds, row_off, bias, gate, Q, K, V)
+    out = torch.empty_like(Q)
+    row_max, row_sum = (_empty(Q, m, h), _empty(Q, m, h)) if stats else (None, None)
+    logits = torch.empty_like(bias) if need_logits else None     # (every valid pair is written)
+    call("dfgnn_segment_mha_gate_fwd", "segment_mha_gate_forward", Q.device, m, h, f, float(scale), bounds, row_off, n_pairs,
+         bias, gate, Q, K, V, out, row_max, row_sum, logits)
+    return [out, row_max, row_sum, logits]
+
+
+def segment_mha_gate_backward(bounds, row_off, bias, gate, Q, K, V, row_max, row_sum, grad, dlogits=None, scale=1.0,
+                              need_dbias=True, need_dgate=True):
+    """-> [dQ, dK, dV, dbias, dgate]; dlogits [h, n_pairs] or None is the gradient that arrived at the logit output; dbias and
+    dgate are None where not needed (dgate also without a gate)."""
+    m, h, f, n_pairs = _segment_gate_checks(bounds, row_off, bias, gate, Q, K, V, grad=grad)
+    check_2d(Q, m, h, row_max=row_max, row_sum=row_sum)
+    if dlogits is not None:
+        _family(Q, torch.float32, (h, n_pairs), {"dlogits": dlogits})
+    delta = _empty(Q, m, h)
+    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
+    dbias = torch.empty_like(bias) if need_dbias else None
+    dgate = torch.empty_like(gate) if need_dgate and gate is not None else None
+    call("dfgnn_segment_mha_gate_bwd", "segment_mha_gate_backward", Q.device, m, h, f, float(scale), bounds, row_off, n_pairs,
+         bias, gate, Q, K, V, row_max, row_sum, grad, dlogits, dQ, dK, dV, dbias, dgate, delta)
+    return [dQ, dK, dV, dbias, dgate]
+
+
 # ---- the same pair with a TYPED pair bias (include/dfgnn_segment_tbias.h): the bias looked up in the kernels ----------------
 # types uint8[n_pairs] in the layout of one bias plane, shared by all heads; table fp32[T, h], T <= 256.
 SEGMENT_TBIAS_MAX_TYPES = 256

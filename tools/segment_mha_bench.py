@@ -26,8 +26,15 @@ queries per graph (0: the square row, the queries are the keys' own array), one 
   sdpa                the padded SDPA with [B, h, seeds, f] queries and the key-padding mask
   self                (square row only) SegmentMHAFuse on the same arrays
 one JSON line per (batch, seeds, shape), appended to profiles/segment_cross_bench.jsonl.
-usage: python3 tools/segment_mha_bench.py [--shapes 4x32,8x16,1x128] [--steps 30] [--bias | --tbias [--types 20] | --cross [--seeds 1,4,16,0]]
-(DESIGN.md 3.3k, 3.3l, 3.3m, 3.3n hold the tables)"""
+--gate: the pair with pair gates and a logit output (SegmentMHAGateFuse, include/dfgnn_segment_gate.h), one training step with
+the gradients of Q, K, V, bias and gate, the logits an output that receives a gradient of its own:
+  new    SegmentMHAGateFuse(seg_ptr, Q, K, V, bias, gate, return_logits=True)
+  torch  the padded form, (softmax(Q K^T scale + b) * sigmoid(g)) @ V on [B, h, n_max, n_max] with the logits kept (SDPA
+         cannot gate); the padding and the gather back are not timed
+  bias   the bias pair on the same Q, K, V, bias: the difference is the price of the two streams in and the two out
+one JSON line per (batch, shape), appended to profiles/segment_gate_bench.jsonl.
+usage: python3 tools/segment_mha_bench.py [--shapes 4x32,8x16,1x128] [--steps 30] [--bias | --gate | --tbias [--types 20] | --cross [--seeds 1,4,16,0]]
+(DESIGN.md 3.3k, 3.3l, 3.3m, 3.3n, 3.3o hold the tables)"""
 import argparse
 import json
 import os
@@ -41,7 +48,7 @@ import torch  # noqa: E402
 from torch.nn import functional as F  # noqa: E402
 
 from DFGNN.operators.fused_gtconv import (GTConvFuse_rowstats, SegmentCrossMHAFuse, SegmentMHABiasFuse, SegmentMHAFuse,  # noqa: E402
-                                          SegmentMHATBiasFuse)
+                                          SegmentMHAGateFuse, SegmentMHATBiasFuse)
 
 DEV = "cuda:0"
 BATCHES = {"zinc": (1024, 9, 37), "pattern": (256, 44, 188), "peptides": (128, 60, 240), "long": (16, 1000, 2000)}
@@ -75,17 +82,20 @@ def main():
     ap.add_argument("--bias-max-pairs", type=int, default=40_000_000, help="skip batches whose padded mask would be larger")
     ap.add_argument("--cross", action="store_true", help="time the cross pair's forms against padded SDPA (and the self pair)")
     ap.add_argument("--seeds", default="1,4,16,0", help="--cross: queries per graph, comma-separated; 0: queries = keys (square)")
+    ap.add_argument("--gate", action="store_true", help="time the gated pair with its logit output against padded torch and the bias pair")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, "profiles", "segment_cross_bench.jsonl" if args.cross else "segment_mha_bench.jsonl")
+    default = "segment_cross_bench.jsonl" if args.cross else "segment_gate_bench.jsonl" if args.gate else "segment_mha_bench.jsonl"
+    args.out = args.out or os.path.join(ROOT, "profiles", default)
     for name in args.batches.split(","):
         count, a, b = BATCHES[name]
         sizes = np.random.default_rng(7).integers(a, b + 1, size=count)
         for shape in args.shapes.split(","):
             h, f = (int(x) for x in shape.split("x"))
-            if (args.bias or args.tbias) and len(sizes) * int(sizes.max()) ** 2 > args.bias_max_pairs:
+            if (args.bias or args.tbias or args.gate) and len(sizes) * int(sizes.max()) ** 2 > args.bias_max_pairs:
                 continue
-            lines = [bench_cross(args, name, sizes, h, f, int(k)) for k in args.seeds.split(",")] if args.cross else [bench(args, name, sizes, h, f)]
+            lines = ([bench_cross(args, name, sizes, h, f, int(k)) for k in args.seeds.split(",")] if args.cross else
+                     [bench_gate(args, name, sizes, h, f)] if args.gate else [bench(args, name, sizes, h, f)])
             for line in lines:
                 print(json.dumps(line), flush=True)
                 with open(args.out, "a") as fh:
@@ -218,6 +228,62 @@ def bench_cross(args, name, sizes, h, f, seeds):
             other = [unq(other[0]), unq(other[1]), unk(other[2]), unk(other[3])]
         if key != "wide":
             line[key + "_max_diff"] = max(float((x - y).abs().max()) for x, y in zip(last["wide"], other))
+    return line
+
+
+def bench_gate(args, name, sizes, h, f):
+    """One training step of the gated pair with its logit output, of its padded torch form and of the bias pair."""
+    ends = np.concatenate([[0], np.cumsum(sizes)])
+    m, B, nmax, pairs = int(ends[-1]), len(sizes), int(sizes.max()), int((sizes.astype(np.int64) ** 2).sum())
+    seg_ptr = torch.tensor(ends, dtype=torch.int32, device=DEV)
+    gen = torch.Generator().manual_seed(5)
+    Q0, K0, V0, dO = (torch.randn(m, h, f, generator=gen).to(DEV) for _ in range(4))
+    bias0, gate0, dL = (torch.randn(h, pairs, generator=gen).to(DEV) for _ in range(3))
+    scale = f ** -0.5
+    n_t = torch.as_tensor(sizes, device=DEV)
+    seg = torch.repeat_interleave(torch.arange(B, device=DEV), n_t)
+    pos = torch.arange(m, device=DEV) - seg_ptr[seg.long()].long()
+    pad = lambda x: torch.zeros(B, nmax, h, f, device=DEV).index_put_((seg, pos), x).transpose(1, 2).contiguous()  # noqa: E731
+    keep = (torch.arange(nmax, device=DEV)[None, :] < n_t[:, None])[:, None, None, :]
+    n_of = n_t[seg]
+    prow = torch.repeat_interleave(torch.arange(m, device=DEV), n_of)
+    pcol = torch.arange(pairs, device=DEV) - torch.repeat_interleave(torch.cumsum(n_of, 0) - n_of, n_of)
+    at = (seg[prow], slice(None), pos[prow], pcol)               # pair (i, j) of graph b at [b, :, i - lo, j - lo]
+
+    def plane(x, fill=0.0):
+        p = torch.full((B, h, nmax, nmax), fill, device=DEV)
+        p[at] = x.t()
+        return p
+    mask0 = plane(bias0).masked_fill_(~keep, float("-inf"))
+
+    def padded(q, k, v, b, g):
+        x = q @ k.transpose(-1, -2) * scale + b
+        return (torch.softmax(x, dim=-1) * torch.sigmoid(g)) @ v, x
+    forms = {"new": (lambda q, k, v, b, g: SegmentMHAGateFuse(seg_ptr, q, k, v, b, g, scale, return_logits=True),
+                     (Q0, K0, V0, bias0, gate0), (dO, dL)),
+             "torch": (padded, (pad(Q0), pad(K0), pad(V0), mask0, plane(gate0)), (pad(dO), plane(dL))),
+             "bias": (lambda q, k, v, b: (SegmentMHABiasFuse(seg_ptr, q, k, v, b, scale),), (Q0, K0, V0, bias0), (dO,))}
+    times, last = {k: [] for k in forms}, {}
+    for it in range(args.warmup + args.steps):
+        for key, (fn, inputs, grad) in forms.items():           # alternating: all forms see the same machine state
+            leaves = [x.detach().requires_grad_(True) for x in inputs]
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            outs = fn(*leaves)
+            grads = torch.autograd.grad(outs, leaves, grad)
+            b.record()
+            torch.cuda.synchronize()
+            if it >= args.warmup:
+                times[key].append(a.elapsed_time(b) * 1e3)
+            last[key] = [o.detach() for o in outs] + list(grads)
+    line = {"tool": "segment_mha_bench_gate", "batch": name, "graphs": B, "m": m, "n_max": nmax, "pairs": pairs, "h": h, "f": f,
+            "steps": args.steps, "plane_mib": round(4 * h * pairs / 2 ** 20, 2)}
+    for key in forms:
+        line[key + "_us"], line[key + "_us_min"] = round(float(np.median(times[key])), 1), round(float(np.min(times[key])), 1)
+    unpad, unplane = (lambda x: x.transpose(1, 2)[seg, pos]), (lambda x: x[at].t())
+    o, lg, dq, dk, dv, db, dg = last["torch"]
+    other = [unpad(o), unplane(lg), unpad(dq), unpad(dk), unpad(dv), unplane(db), unplane(dg)]
+    line["torch_max_diff"] = max(float((x - y).abs().max()) for x, y in zip(last["new"], other))
     return line
 
 
